@@ -15,15 +15,25 @@ N > 1 (weak scaling): every rank owns B*Q rows of a N times larger problem (glob
 replicated value pyramid; the kernels write the local rows straight into the result, the peers' rows arrive by an
 in-place exchange that overlaps the next piece's kernels (RCCL); grad_value is summed only among the ranks that
 share a batch element (none while N divides B).  `value` = query rows (b, q) processed per second by the whole
-job, fwd+bwd.  The same run also times a STRONG-scaling leg under the key `strong_scaling_c5`: BASELINE configs[4]
-(B=4, Q=100 000, D=64, L=5, P=8, fp16) with its 400 000 rows split over the N ranks.
+job, fwd+bwd.  With `--full` the same run also times a STRONG-scaling leg under the key `strong_scaling_c5`:
+BASELINE configs[4] (B=4, Q=100 000, D=64, L=5, P=8, fp16) with its 400 000 rows split over the N ranks.
 
-The N=1 run also carries (same JSON line):
+A plain run does what the headline needs and nothing else: set-up, spin-up and W warm-up steps, the K timed steps,
+and the line (`metric`, `value`, `unit`, `ms_per_step` = `fwd_bwd_ms`, `dtype`, `config`, ...).  `--dump-outputs DIR`
+writes what the last timed step computed — the result and the three input gradients a caller of the step receives —
+as DIR/<name>.npy (float32, float64 for fp64 workloads; an array too large for its share of the 48 MiB budget is
+written as a fixed, seeded sample of its flattened elements).  The inputs are seeded, and the generator that draws the step's
+`rand_like(out)` is reseeded in front of the timed steps, so runs with the same arguments see the same inputs.
+
+`--full` adds everything else to the line: `fwd_ms` (K forward-only steps), `ms_per_step_cold_window`, the
+per-launch-group and per-kernel HIP-event times (`kernels`, `single_kernels`, `roofline`), peak memory, and (N=1):
   * `do_bench`: the reference's timing recipe for this workload (scripts/benchmark.py:38,52-54,90-94 — triton.testing.do_bench:
     >= 100 ms of warm-up, >= 1 s of repetitions, per-repetition device events, median + p20 / p80), once with the
     caches flushed between repetitions (cold, as do_bench does) and once back to back (warm);
   * `configs`: every other BASELINE.json config that fits one GPU (c1, c2 @ 1k / 5k, c3, c4): fwd_ms, fwd_bwd_ms,
-    per-launch-group microseconds with their roofline fraction and measured HBM traffic, peak memory.
+    per-launch-group microseconds with their roofline fraction and measured HBM traffic, peak memory;
+  * `cpu_baseline`, `decoder_real_pyramid`, `padded_value_rows`, `shard_compute_bound`, `triton_comparator`, and the
+    strong-scaling leg (every N).
 `ms_per_step` stays the K timed steps of the headline workload.
 
 `--backend gloo --device cpu` (with `--workload dryrun`) runs the whole N-rank control flow — sharding, both exchanges,
@@ -50,6 +60,31 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (guides/MI355X_MICROARCH.md)
 README_RTX2060_MS = {"fwd": 3.78, "fwd_bwd": 22.78}  # reference README.md:18-19 (Triton, RTX 2060)
 L1_PEAK_GBS = 64 * 256 * 2.4  # vector L1: 64 B/clk/CU x 256 CUs x 2.4 GHz = 39 322 GB/s (guides/MI355X_MICROARCH.md)
 LDS_PEAK_GBS = 256 * 256 * 2.4  # LDS, ds_read_b128: 256 B/clk/CU x 256 CUs x 2.4 GHz = 157 286 GB/s (same guide, "LDS")
+DUMP_BUDGET_BYTES = 48 * 2**20  # --dump-outputs: all arrays together stay below this
+DUMP_SAMPLE_SEED = 20240  # --dump-outputs: which elements of an array over its share of the budget are written
+
+
+def dump_sample(t, cap):
+    """`t` as a host array for --dump-outputs: float64 stays float64, every other dtype becomes float32.  At most `cap`
+    elements: a larger array is flattened and `cap` of its elements are written, at indices drawn (ascending) from a
+    generator seeded with DUMP_SAMPLE_SEED and the array's size — the same elements on every run."""
+    import numpy as np
+    import torch
+
+    x = t.detach()
+    x = x.double() if x.dtype == torch.float64 else x.float()
+    if x.numel() <= cap:
+        return x.cpu().numpy()
+    idx = np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, x.numel()]).choice(x.numel(), cap, replace=False))
+    return x.reshape(-1)[torch.from_numpy(idx).to(x.device)].cpu().numpy()
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def lds_row_fraction(wl, info):
@@ -686,6 +721,11 @@ def main():
     ap.add_argument("--workload", default="c2_q10k")
     ap.add_argument("--spin-up-ms", type=float, default=200.0,
                     help="untimed steps for this long before the W warm-up steps (0: none); see spin_up()")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: fwd_ms, per-kernel times, roofline, peak memory, the cold "
+                         "window and the optional legs below (each --no-* flag skips one of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result and the input gradients of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--xcd-map", type=int, default=None, help="override the blockIdx->(b,h) mapping (A/B runs)")
     ap.add_argument("--grad-value-sync", default="owners", choices=["owners", "all_reduce", "none"],
@@ -775,9 +815,11 @@ def main():
                                                            num_queries=gwl.Q, grad_value_sync=args.grad_value_sync,
                                                            overlap_chunks=exchange["chunks"])
 
-    def step():
+    def step(keep=None):
         out = op()
         out.backward(torch.rand_like(out))
+        if keep is not None:  # (the last timed step of a --dump-outputs run: what a caller of the step receives)
+            keep.update(out=out, grad_img=img.grad, grad_sampling_points=pts.grad, grad_attention_weights=attn.grad)
         img.grad = pts.grad = attn.grad = None
 
     def fwd_only():
@@ -792,7 +834,7 @@ def main():
         if on_gpu:
             torch.cuda.synchronize()
 
-    def timed(fn, n, collect=True):
+    def timed(fn, n, collect=True, keep=None):
         import gc
         if collect:
             gc.collect()  # (tens of ms during which the GPU idles: the headline measurement collects BEFORE its warm-up)
@@ -800,8 +842,10 @@ def main():
         try:
             barrier()
             t0 = time.perf_counter()
-            for _ in range(n):
+            for _ in range(n if keep is None else n - 1):
                 fn()
+            if keep is not None:
+                fn(keep)
             barrier()
             dt = time.perf_counter() - t0
         finally:
@@ -844,16 +888,27 @@ def main():
     spin = {"steps": 0}
 
     def measure():
+        """-> (ms per step, ms per forward-only step or None without --full, the --dump-outputs arrays or None)"""
         import gc
         gc.collect()
         spin["steps"] = spin_up(step)
         for _ in range(args.warmup):
             step()
+        torch.manual_seed(0)  # (the K steps' rand_like(out) gradients: the same in every run with the same arguments)
+        keep = {} if args.dump_outputs else None
         # ---- the timed region: exactly K steps of the un-instrumented public API, straight behind the warm-up ----
-        ms = timed(step, args.steps, collect=False) * 1e3 / args.steps
+        ms = timed(step, args.steps, collect=False, keep=keep) * 1e3 / args.steps
+        outs = None
+        if keep is not None:
+            cap = DUMP_BUDGET_BYTES // (len(keep) * 8)
+            outs = {k: dump_sample(t, cap if t.dtype == torch.float64 else 2 * cap) for k, t in keep.items()
+                    if t is not None}
+            del keep
+        if not args.full:
+            return ms, None, outs
         for _ in range(max(3, args.warmup // 2)):
             fwd_only()
-        return ms, timed(fwd_only, args.steps, collect=False) * 1e3 / args.steps
+        return ms, timed(fwd_only, args.steps, collect=False) * 1e3 / args.steps, outs
 
     def cold_window():
         """The protocol of rounds 1-4 (and of any caller that times a short burst on an idle GPU): the device idles,
@@ -876,16 +931,16 @@ def main():
         # faster one (config.exchange says which).
         exchange["chunks"] = 1
         guard.arm(600, "weak-scaling leg (all-gather exchange)")
-        ms_step, ms_fwd = measure()
+        ms_step, ms_fwd, outs = measure()
         guard.disarm()
         exchange_ms = {"all_gather": {"fwd_bwd_ms": ms_step, "fwd_ms": ms_fwd}}
     else:
-        ms_step, ms_fwd = measure()
-    # ---- the same K steps again with per-launch HIP events (KernelTimer splits the backward into one C-ABI call
-    #      per kernel group, so its two halves run back to back here instead of concurrently) ----
-    kern = {}
-    peak_mem = peak_ref = launch_info = None
-    if on_gpu:
+        ms_step, ms_fwd, outs = measure()
+    # ---- (--full) the same K steps again with per-launch HIP events (KernelTimer splits the backward into one C-ABI
+    #      call per kernel group, so its two halves run back to back here instead of concurrently) ----
+    kern, single = {}, {}
+    peak_mem = peak_ref = launch_info = ms_cold = None
+    if on_gpu and args.full:
         for _ in range(args.warmup):
             step()
         with KernelTimer() as kt:
@@ -893,7 +948,6 @@ def main():
         kern = kt.summary()
         torch.cuda.synchronize()
         # ... and once more with the library's own event pair around every single kernel (msda_profile_read)
-        single = {}
         try:
             _lib.set_option("profile", 1)
             for _ in range(args.warmup):  # (the first profiled launches create their event pairs: not measured)
@@ -920,11 +974,10 @@ def main():
             peak_ref += (torch.cuda.max_memory_allocated(dev) - start_mem) / 1e6 / reps
         fwd_only()
         launch_info = _lib.last_launch_info()
-    ms_cold = cold_window()
+    if args.full:
+        ms_cold = cold_window()
 
     if rank == 0:
-        kernels = kernel_table(wl, kern, load_traffic(args.workload))
-        sum_kernel_us = sum(k["avg_us"] for k in kernels.values())
         weak_note = ("" if world == 1 else
                      f" — WEAK scaling: every rank keeps {wl.Q} queries per batch element, the global problem has "
                      f"Q = {wl.Q} x {world} = {gwl.Q}")
@@ -936,7 +989,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_step,
-            "ms_per_step_cold_window": ms_cold,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -957,24 +1009,31 @@ def main():
                        "exchange": ("none (one rank)" if world == 1 else
                                     "one in-place all-gather" if exchange["chunks"] == 1 else
                                     "grouped point-to-point pieces overlapped with compute"),
-                       "backend": args.backend, "device": args.device},
-            "fwd_ms": ms_fwd,
+                       "backend": args.backend, "device": args.device,
+                       "full": args.full},
             "fwd_bwd_ms": ms_step,
-            "sum_kernel_us_fwd_bwd": round(sum_kernel_us, 2),
             "alg_fwd_bwd_GBs": round((wl.alg_fwd_bytes + wl.alg_bwd_bytes) / (ms_step * 1e-3) / 1e9, 1),
-            "effective_gather_GBs_fwd": round(wl.gather_fwd_bytes / (kernels["msda_fwd"]["avg_us"] * 1e-6) / 1e9, 1)
-            if "msda_fwd" in kernels else None,
-            "reference_readme_rtx2060_ms": README_RTX2060_MS,
-            "speedup_vs_reference_readme": {"fwd": README_RTX2060_MS["fwd"] / ms_fwd,
-                                            "fwd_bwd": README_RTX2060_MS["fwd_bwd"] / ms_step},
-            "kernels": kernels,
-            "peak_mem_MB": round(peak_mem / 1e6, 1) if peak_mem is not None else None,
-            "peak_mem_reference_recipe_MB": round(peak_ref, 1) if peak_ref is not None else None,
-            "peak_mem_note": "peak_mem_MB: max_memory_allocated over a step, inputs included; peak_mem_reference_recipe_MB: "
-                             "the reference's recipe (scripts/benchmark.py:158-172) — what one fwd+bwd allocates ON TOP of "
-                             "its resident inputs (result, rand_like gradient, three gradients, workspace); the reference's "
-                             "README quotes 166.14 MB for it",
         }
+        kernels = {}
+        if args.full:
+            kernels = kernel_table(wl, kern, load_traffic(args.workload))
+            result.update({
+                "ms_per_step_cold_window": ms_cold,
+                "fwd_ms": ms_fwd,
+                "sum_kernel_us_fwd_bwd": round(sum(k["avg_us"] for k in kernels.values()), 2),
+                "effective_gather_GBs_fwd": round(wl.gather_fwd_bytes / (kernels["msda_fwd"]["avg_us"] * 1e-6) / 1e9, 1)
+                if "msda_fwd" in kernels else None,
+                "reference_readme_rtx2060_ms": README_RTX2060_MS,
+                "speedup_vs_reference_readme": {"fwd": README_RTX2060_MS["fwd"] / ms_fwd,
+                                                "fwd_bwd": README_RTX2060_MS["fwd_bwd"] / ms_step},
+                "kernels": kernels,
+                "peak_mem_MB": round(peak_mem / 1e6, 1) if peak_mem is not None else None,
+                "peak_mem_reference_recipe_MB": round(peak_ref, 1) if peak_ref is not None else None,
+                "peak_mem_note": "peak_mem_MB: max_memory_allocated over a step, inputs included; peak_mem_reference_recipe_MB: "
+                                 "the reference's recipe (scripts/benchmark.py:158-172) — what one fwd+bwd allocates ON TOP of "
+                                 "its resident inputs (result, rand_like gradient, three gradients, workspace); the reference's "
+                                 "README quotes 166.14 MB for it",
+            })
         if on_gpu and single:
             salg = single_kernel_alg_bytes(wl)
             result["single_kernels"] = {
@@ -1042,7 +1101,7 @@ def main():
         #  forward cannot hide a piece's exchange — so this leg is what says whether that rule holds on real links)
         exchange["chunks"] = 4
         try:
-            ms2, fwd2 = measure()
+            ms2, fwd2, outs2 = measure()
             exchange_ms["pieces"] = {"fwd_bwd_ms": ms2, "fwd_ms": fwd2}
         except Exception as e:  # every rank sees the same RCCL error; a rank left waiting trips the guard
             ms2 = None
@@ -1051,18 +1110,24 @@ def main():
             exchange_ms["pieces"] = {"error": repr(e)[:300]}
         guard.disarm()
         if ms2 is not None and ms2 < ms_step:  # the all-reduced max over ranks: the same decision everywhere
-            ms_step, ms_fwd = ms2, fwd2
+            ms_step, ms_fwd, outs = ms2, fwd2, outs2
         else:
             exchange["chunks"] = 1
         if rank == 0:
             result.update(value=wl.B * wl.Q * world / (ms_step * 1e-3), ms_per_step=ms_step, fwd_bwd_ms=ms_step,
-                          fwd_ms=ms_fwd, exchange_ms=exchange_ms,
-                          alg_fwd_bwd_GBs=round((wl.alg_fwd_bytes + wl.alg_bwd_bytes) / (ms_step * 1e-3) / 1e9, 1),
-                          speedup_vs_reference_readme={"fwd": README_RTX2060_MS["fwd"] / ms_fwd,
-                                                       "fwd_bwd": README_RTX2060_MS["fwd_bwd"] / ms_step})
+                          exchange_ms=exchange_ms,
+                          alg_fwd_bwd_GBs=round((wl.alg_fwd_bytes + wl.alg_bwd_bytes) / (ms_step * 1e-3) / 1e9, 1))
+            if args.full:
+                result.update(fwd_ms=ms_fwd,
+                              speedup_vs_reference_readme={"fwd": README_RTX2060_MS["fwd"] / ms_fwd,
+                                                           "fwd_bwd": README_RTX2060_MS["fwd_bwd"] / ms_step})
             result["config"]["exchange"] = ("one in-place all-gather" if exchange["chunks"] == 1 else
                                             "grouped point-to-point pieces overlapped with compute")
-    if world == 1 and on_gpu and rank == 0:
+    if rank == 0 and outs is not None:
+        write_outputs(args.dump_outputs, outs)
+    outs = outs2 = None
+    # ---- (--full) the optional legs ----
+    if args.full and world == 1 and on_gpu and rank == 0:
         if not args.no_do_bench:
             def leg_do_bench():
                 return {"recipe": "triton.testing.do_bench semantics (reference scripts/benchmark.py:38,52-54): >=100 ms "
@@ -1075,7 +1140,7 @@ def main():
         if not args.no_cpu_baseline:
             optional("cpu_baseline", lambda: cpu_baseline(wl), False)
     strong_wl = "c5_stress" if on_gpu else "dryrun_strong"
-    run_strong = not args.no_strong_c5 and args.workload in ("c2_q10k", "dryrun")
+    run_strong = args.full and not args.no_strong_c5 and args.workload in ("c2_q10k", "dryrun")
     if run_strong and pieces_failed:
         # the communicator that just raised is not reused (its error state would only raise again)
         if rank == 0:
@@ -1092,12 +1157,12 @@ def main():
         guard.disarm()
         if on_gpu:
             torch.cuda.empty_cache()
-    if world == 1 and rank == 0 and not args.no_shard_compute and args.workload in ("c2_q10k", "dryrun"):
+    if args.full and world == 1 and rank == 0 and not args.no_shard_compute and args.workload in ("c2_q10k", "dryrun"):
         optional("shard_compute_bound",
                  lambda: shard_compute_leg(dev, "c5_stress" if on_gpu else "dryrun_strong", args.workload), False)
         if on_gpu:
             torch.cuda.empty_cache()
-    if world == 1 and on_gpu and rank == 0 and not args.no_configs and args.workload == "c2_q10k":
+    if args.full and world == 1 and on_gpu and rank == 0 and not args.no_configs and args.workload == "c2_q10k":
         def leg_configs():
             out = {}
             for name in ("c1_readme", "c2_q1k", "c2_q5k", "c2_q10k_zeros", "c3_ddetr_enc", "c3_ddetr_enc_local",
@@ -1112,7 +1177,7 @@ def main():
         optional("configs", leg_configs, False)
         optional("decoder_real_pyramid", lambda: real_pyramid_leg(dev), False)
         optional("padded_value_rows", lambda: padded_rows_leg(args.workload, dev), False)
-    if world == 1 and on_gpu and rank == 0 and not args.no_triton and args.workload == "c2_q10k":
+    if args.full and world == 1 and on_gpu and rank == 0 and not args.no_triton and args.workload == "c2_q10k":
         result["triton_comparator"] = triton_comparator_leg(args.workload, dev)
     if rank == 0:
         if failed_legs:

@@ -218,7 +218,7 @@ def _run_bench_dry(world, extra_env=None):
     env.update(extra_env or {})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world),
-           "--steps", "2", "--warmup", "1", "--backend", "gloo", "--device", "cpu", "--workload", "dryrun"]
+           "--steps", "2", "--warmup", "1", "--backend", "gloo", "--device", "cpu", "--workload", "dryrun", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     return res, [json.loads(ln) for ln in lines]
@@ -372,7 +372,7 @@ def test_bench_dry_run_world1_carries_the_shard_compute_leg():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--backend", "gloo", "--device", "cpu",
-           "--workload", "dryrun"]
+           "--workload", "dryrun", "--full"]
     res = subprocess.run(cmd, cwd=root, env=dict(os.environ, OMP_NUM_THREADS="2"), stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -386,6 +386,46 @@ def test_bench_dry_run_world1_carries_the_shard_compute_leg():
         assert leg[key]["2"]["ideal"] == (2 if key.startswith("strong") else 1)
     assert leg["strong_dryrun_strong"]["8"]["rows"] * 8 == leg["strong_dryrun_strong"]["1"]["rows"]
     assert leg["weak_dryrun"]["8"]["rows"] == leg["weak_dryrun"]["1"]["rows"]
+
+
+def _run_bench_world1(*extra):
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--backend", "gloo", "--device", "cpu",
+           "--workload", "dryrun", *extra]
+    res = subprocess.run(cmd, cwd=root, env=dict(os.environ, OMP_NUM_THREADS="2"), stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and none of the optional legs; --dump-outputs writes the last timed
+    step's result and input gradients, the same in two runs with the same arguments."""
+    from msda_triton_amd import synth
+    wl = synth.WORKLOADS["dryrun"]
+    runs = []
+    for tag in ("a", "b"):
+        r = _run_bench_world1("--dump-outputs", str(tmp_path / tag))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in r, key
+        assert r["steps"] == 3 and r["dtype"] == "f32" and r["config"]["full"] is False
+        assert abs(r["value"] - wl.B * wl.Q / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+        for key in ("fwd_ms", "kernels", "ms_per_step_cold_window", "strong_scaling_c5", "shard_compute_bound"):
+            assert key not in r, key
+        runs.append({f.name: np.load(f) for f in (tmp_path / tag).iterdir()})
+    shapes = {"out.npy": (wl.B, wl.Q, wl.H, wl.D), "grad_img.npy": (wl.B, wl.I, wl.H, wl.D),
+              "grad_sampling_points.npy": (wl.B, wl.Q, wl.H, wl.L, wl.P, 2),
+              "grad_attention_weights.npy": (wl.B, wl.Q, wl.H, wl.L, wl.P)}
+    assert set(runs[0]) == set(shapes)
+    for name, shape in shapes.items():
+        a, b = runs[0][name], runs[1][name]
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all() and np.abs(a).sum() > 0, name
+        np.testing.assert_array_equal(a, b)
 
 
 def test_argument_errors_of_the_row_sharded_operator():
