@@ -74,7 +74,7 @@
 extern "C" {
 #endif
 
-#define MSDA_ABI_VERSION 11
+#define MSDA_ABI_VERSION 12
 
 #if defined(__GNUC__)
 #define MSDA_API __attribute__((visibility("default")))
@@ -142,8 +142,31 @@ extern "C" {
                        void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D,          \
                        int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
                        int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);                    \
+    MSDA_API int msda_fwd_ragged_##SUF(const void *value, const int64_t *shapes, const void *loc,           \
+                       const void *attn, void *out, int64_t B, int64_t I, int64_t H, int64_t D,    \
+                       int64_t Q, int64_t L, const int32_t *points_per_level, int padding_mode,    \
+                       int align_corners, int64_t value_row_stride, void *stream);                 \
+    MSDA_API int msda_bwd_ragged_##SUF(const void *grad_out, const void *value, const int64_t *shapes,      \
+                       const void *loc, const void *attn, void *grad_value, void *grad_loc,        \
+                       void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,     \
+                       int64_t L, const int32_t *points_per_level, int padding_mode,               \
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,       \
                        void *workspace, int64_t workspace_bytes, void *stream);
 
+/*
+ * Per-level point counts (ABI 12, additive): msda_fwd_ragged_<dtype> / msda_bwd_ragged_<dtype> take the arguments of
+ * msda_fwd_<dtype> / msda_bwd_<dtype>, except that P becomes `points_per_level`, a HOST array of L counts P_l >= 1 (read
+ * during the call, never kept; a count below 1 is MSDA_ERR_BAD_ARG).  With S = sum_l P_l the sample axis is level-major:
+ *
+ *   loc        [B, Q, H, S, 2]     samples [start_l, start_l + P_l) of a (b, q, h) belong to level l
+ *   attn       [B, Q, H, S]        (grad_loc / grad_attn shaped alike)
+ *
+ * as the D-FINE / DEIMv2 decoders lay them out (decoder_n_points = [3, 6, 3] ...).  Every size check of the uniform
+ * entry points applies with L * P read as S; value_row_stride, MSDA_WS_RECORDS_IN_GRADS and MSDA_WS_PASSES(n) mean what
+ * they mean there, and the workspace comes from msda_bwd_ragged_workspace_bytes.  grad_value is bitwise reproducible
+ * while max_l P_l <= 1024.  The fused entry points keep one P for every level.
+ */
 MSDA_DECLARE(f32)
 MSDA_DECLARE(f16)
 MSDA_DECLARE(bf16)
@@ -206,6 +229,10 @@ MSDA_DECLARE_FUSED_STORAGE(f32_sf16)
 MSDA_API int64_t msda_bwd_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                           int64_t P, int elem_size, int value_elem_size, int64_t max_level_cells,
                                           int flags);
+/* ... msda_bwd_ragged_<dtype> (ABI 12; 0 for an unusable points_per_level) ... */
+MSDA_API int64_t msda_bwd_ragged_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                                 const int32_t *points_per_level, int elem_size, int value_elem_size,
+                                                 int64_t max_level_cells, int flags);
 /* ... and msda_bwd_fused_<dtype> (grad_value != NULL). */
 MSDA_API int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                                 int64_t P, int elem_size, int value_elem_size,
@@ -219,6 +246,9 @@ MSDA_API int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t H,
  */
 MSDA_API int msda_bwd_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P,
                                 int elem_size);
+/* ... for msda_bwd_ragged_<dtype> (ABI 12). */
+MSDA_API int msda_bwd_ragged_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                       const int32_t *points_per_level, int elem_size);
 
 /* Largest L*P the fused entry points accept for head dimension D and this element size (beyond it they return
  * MSDA_ERR_UNSUPPORTED and the caller composes the prologue around msda_fwd_/msda_bwd_<dtype>). */

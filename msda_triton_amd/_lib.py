@@ -15,7 +15,7 @@ LIB_NAME = "libmsda_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 PADDING_MODES = {"border": 0, "zeros": 1}
 WS_RECORDS_IN_GRADS = 1  # msda_bwd_workspace_bytes flag (include/msda_hip.h)
 
@@ -34,6 +34,8 @@ FUSED_STORAGE_SUFFIXES = ("f32_sbf16", "f32_sf16")
 EXPORTED_SYMBOLS = tuple(
     [f"msda_{d}_{s}" for d in ("fwd", "bwd", "fwd_fused", "bwd_fused") for s in DTYPE_SUFFIXES]
     + [f"msda_{d}_{s}" for d in ("fwd_fused", "bwd_fused") for s in FUSED_STORAGE_SUFFIXES]
+    + [f"msda_{d}_ragged_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES]
+    + ["msda_bwd_ragged_workspace_bytes", "msda_bwd_ragged_supported"]
     + ["msda_abi_version", "msda_last_error", "msda_set_option", "msda_get_option", "msda_bwd_workspace_bytes",
        "msda_bwd_fused_workspace_bytes", "msda_bwd_supported", "msda_fused_lp_limit", "msda_profile_read",
        "msda_last_launch_info"]
@@ -92,6 +94,13 @@ def load():
             gf = getattr(lib, f"msda_bwd_fused_{suf}")
             gf.restype = ci
             gf.argtypes = [vp] * 8 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
+            # per-level point counts (ABI 12): P becomes a host int32 array of L counts
+            fr = getattr(lib, f"msda_fwd_ragged_{suf}")
+            fr.restype = ci
+            fr.argtypes = [vp] * 5 + [i64] * 6 + [vp, ci, ci, i64, vp]
+            gr = getattr(lib, f"msda_bwd_ragged_{suf}")
+            gr.restype = ci
+            gr.argtypes = [vp] * 8 + [i64] * 6 + [vp, ci, ci, i64, i64, vp, i64, vp]
         for suf in FUSED_STORAGE_SUFFIXES:
             ff = getattr(lib, f"msda_fwd_fused_{suf}")
             ff.restype = ci
@@ -105,6 +114,10 @@ def load():
         lib.msda_bwd_fused_workspace_bytes.argtypes = [i64] * 7 + [ci, ci, i64, ci]
         lib.msda_bwd_supported.restype = ci
         lib.msda_bwd_supported.argtypes = [i64] * 7 + [ci]
+        lib.msda_bwd_ragged_workspace_bytes.restype = i64
+        lib.msda_bwd_ragged_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
+        lib.msda_bwd_ragged_supported.restype = ci
+        lib.msda_bwd_ragged_supported.argtypes = [i64] * 6 + [vp, ci]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64

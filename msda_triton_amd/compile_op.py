@@ -177,3 +177,81 @@ def compiled_fused_module_core(img, img_shapes, proj, reference_points, padding_
                                       padding_mode == "zeros", bool(align_corners), int(level_cells))
     return msda_fused_forward(img, img_shapes, proj, reference_points, padding_mode == "zeros", bool(align_corners),
                               int(level_cells))
+
+
+# ---------------------------------------------------------------------------------------------
+# per-level point counts (msda_fwd_ragged_ / msda_bwd_ragged_<dtype>): sampling points [B, Q, H, S, 2] and the counts as
+# an int list (a constant of the traced graph)
+# ---------------------------------------------------------------------------------------------
+@torch.library.custom_op("msda_amd::ragged_forward", mutates_args=(), device_types="cuda")
+def msda_ragged_forward(img: torch.Tensor, img_shapes: torch.Tensor, sampling_points: torch.Tensor,
+                        attention_weights: torch.Tensor, zeros: bool, align_corners: bool, points_per_level: list[int],
+                        level_cells: int = 0) -> torch.Tensor:
+    from .ragged import ragged_hip_fwd
+    return ragged_hip_fwd(img, img_shapes, sampling_points, attention_weights, _PAD[zeros], align_corners,
+                          tuple(points_per_level))
+
+
+@msda_ragged_forward.register_fake
+def _(img, img_shapes, sampling_points, attention_weights, zeros, align_corners, points_per_level, level_cells=0):
+    B, _, H, D = img.shape
+    return sampling_points.new_empty((B, sampling_points.shape[1], H, D))
+
+
+@torch.library.custom_op("msda_amd::ragged_backward", mutates_args=(), device_types="cuda")
+def msda_ragged_backward(out_grad: torch.Tensor, img: torch.Tensor, img_shapes: torch.Tensor,
+                         sampling_points: torch.Tensor, attention_weights: torch.Tensor, zeros: bool,
+                         align_corners: bool, points_per_level: list[int], need_value: bool, need_sample: bool,
+                         level_cells: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    from .ragged import ragged_hip_bwd
+    g_img, g_pts, g_att = ragged_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, _PAD[zeros],
+                                         align_corners, tuple(points_per_level), (need_value, need_sample, need_sample),
+                                         level_cells)
+    return (g_img if g_img is not None else img.new_empty(0),
+            g_pts if g_pts is not None else img.new_empty(0),
+            g_att if g_att is not None else img.new_empty(0))
+
+
+@msda_ragged_backward.register_fake
+def _(out_grad, img, img_shapes, sampling_points, attention_weights, zeros, align_corners, points_per_level, need_value,
+      need_sample, level_cells=0):
+    return (torch.empty_like(img, memory_format=torch.contiguous_format) if need_value else img.new_empty(0),
+            torch.empty_like(sampling_points, memory_format=torch.contiguous_format) if need_sample else img.new_empty(0),
+            torch.empty_like(attention_weights, memory_format=torch.contiguous_format) if need_sample else img.new_empty(0))
+
+
+def _ragged_setup_context(ctx, inputs, output):
+    img, img_shapes, sampling_points, attention_weights, zeros, align_corners, points_per_level, level_cells = inputs
+    ctx.save_for_backward(img, img_shapes, sampling_points, attention_weights)
+    ctx.zeros, ctx.align_corners, ctx.ppl, ctx.level_cells = zeros, align_corners, points_per_level, level_cells
+
+
+def _ragged_backward(ctx, out_grad):
+    img, img_shapes, sampling_points, attention_weights = ctx.saved_tensors
+    need_value = ctx.needs_input_grad[0]
+    need_sample = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+    g_img, g_pts, g_att = msda_ragged_backward(out_grad.contiguous(), img, img_shapes, sampling_points,
+                                               attention_weights, ctx.zeros, ctx.align_corners, ctx.ppl, need_value,
+                                               need_sample, ctx.level_cells)
+    return (g_img if need_value else None, None, g_pts if ctx.needs_input_grad[2] else None,
+            g_att if ctx.needs_input_grad[3] else None, None, None, None, None)
+
+
+msda_ragged_forward.register_autograd(_ragged_backward, setup_context=_ragged_setup_context)
+
+
+def compiled_ragged_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,
+                                                    align_corners, points_per_level, level_cells: int = 0):
+    """``ragged.ragged_multiscale_deformable_attention`` through the registered custom ops (traceable); fp32 under
+    autocast unless the caller passes the mixed storage (16-bit `img` next to fp32 sampling inputs)."""
+    F._padding_code(padding_mode)
+    ppl = [int(p) for p in points_per_level]
+    if torch.is_autocast_enabled("cuda"):
+        with torch.autocast("cuda", enabled=False):
+            keep = img.dtype in (torch.bfloat16, torch.float16) and sampling_points.dtype == torch.float32 and \
+                attention_weights.dtype == torch.float32
+            return msda_ragged_forward(img if keep else img.float(), img_shapes, sampling_points.float(),
+                                       attention_weights.float(), padding_mode == "zeros", bool(align_corners), ppl,
+                                       int(level_cells))
+    return msda_ragged_forward(img, img_shapes, sampling_points, attention_weights, padding_mode == "zeros",
+                               bool(align_corners), ppl, int(level_cells))

@@ -205,7 +205,7 @@ void set_error(const char *fmt, ...)
 extern "C" int msda_abi_version(void) { return MSDA_ABI_VERSION; }
 
 // the layout lives in a device header (msda_value_sorted.hpp); msda_f32.hip exposes its size formula
-extern "C" int64_t msda_bwd_workspace_bytes_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int, int64_t, int);
+extern "C" int64_t msda_bwd_workspace_bytes_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int, int64_t, int, int64_t);
 
 extern "C" int64_t msda_bwd_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                             int64_t P, int elem_size, int value_elem_size, int64_t max_level_cells,
@@ -214,7 +214,7 @@ extern "C" int64_t msda_bwd_workspace_bytes(int64_t B, int64_t I, int64_t H, int
     if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || L < 0 || P < 0) return 0;
     return msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, P, elem_size, (flags & MSDA_WS_RECORDS_IN_GRADS) ? 1 : 0,
                                          value_elem_size > 0 ? value_elem_size : elem_size, max_level_cells,
-                                         ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes());
+                                         ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), 0);
 }
 
 extern "C" int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
@@ -227,15 +227,15 @@ extern "C" int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t 
     (void)value_elem_size;
     const int64_t mat = (B * Q * H * L * P * 3 * (int64_t)elem_size + 255) / 256 * 256;
     return mat + msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, P, elem_size, 0, 0, max_level_cells,
-                                               ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes());
+                                               ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), 0);
 }
 
-extern "C" int msda_bwd_supported_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int);
+extern "C" int msda_bwd_supported_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t);
 
 extern "C" int msda_bwd_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int elem_size)
 {
     if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || L < 0 || P < 0 || elem_size <= 0) return 0;
-    return msda_bwd_supported_impl(B, I, H, D, Q, L, P, elem_size);
+    return msda_bwd_supported_impl(B, I, H, D, Q, L, P, elem_size, 0);
 }
 
 extern "C" int64_t msda_fused_lp_limit_impl(int64_t, int);

@@ -6,31 +6,36 @@ MSDA_DEFINE_ENTRY_POINTS(f32, float)
 // size of the backward workspace (shared by every dtype: the accumulate type decides the record sizes)
 extern "C" __attribute__((visibility("hidden"))) int64_t msda_bwd_workspace_bytes_impl(
     int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int elem_size, int records_in_grads,
-    int value_elem_size, int64_t max_level_cells, int passes)
+    int value_elem_size, int64_t max_level_cells, int passes, int64_t S)
 {
-    // problems the single-launch kernel takes need no workspace at all
-    const msda::Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
+    // problems the single-launch kernel takes need no workspace at all (S: samples per unit with per-level point counts,
+    // P their maximum; 0: L * P)
+    msda::Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
+    d.S = S;
     const bool small = elem_size == 8 ? msda::small_path_chosen<double>(d) : msda::small_path_chosen<float>(d);
     const size_t acc = elem_size == 8 ? 8 : 4;
     if (small) return 0;
     // passes over the batch (MSDA_WS_PASSES): the workspace of ceil(B / passes) batch elements, used once per group
     if (passes > 1 && B > 1) B = (B + passes - 1) / passes;
+    // records in the gradient buffers need every group's share of them 16-byte aligned (msda_launch.hpp)
+    if (!msda::records_fit_grads(d, B, (size_t)elem_size)) records_in_grads = 0;
     // the larger of the 16-byte-vector and the scalar layout: which one a call takes depends on the alignment of its
     // grad_out / grad_value pointers (a slice of a shard's buffers can be misaligned), and a workspace that is too
     // small would be rejected (MSDA_ERR_BAD_ARG)
     const bool rg = records_in_grads != 0 && msda::option_records_in_grads() != 0;
-    const size_t vec = msda::sorted_ws_layout(B, I, H, D, Q, L, P, acc, (size_t)elem_size, true, rg, (size_t)value_elem_size).total;
-    const size_t sca = msda::sorted_ws_layout(B, I, H, D, Q, L, P, acc, (size_t)elem_size, false, rg, (size_t)value_elem_size).total;
+    const size_t vec = msda::sorted_ws_layout(B, I, H, D, Q, L, msda::samples(d), acc, (size_t)elem_size, true, rg, (size_t)value_elem_size).total;
+    const size_t sca = msda::sorted_ws_layout(B, I, H, D, Q, L, msda::samples(d), acc, (size_t)elem_size, false, rg, (size_t)value_elem_size).total;
     return (int64_t)(vec > sca ? vec : sca);
 }
 
 // can grad_value be produced for these sizes at all (include/msda_hip.h: msda_bwd_supported)
 extern "C" __attribute__((visibility("hidden"))) int msda_bwd_supported_impl(int64_t B, int64_t I, int64_t H, int64_t D,
-                                                                           int64_t Q, int64_t L, int64_t P, int elem_size)
+                                                                           int64_t Q, int64_t L, int64_t P, int elem_size, int64_t S)
 {
-    const msda::Dims d{B, I, H, D, Q, L, P};
+    msda::Dims d{B, I, H, D, Q, L, P};
+    d.S = S;
     if (L > MSDA_MAX_LEVELS) return 0;
-    if (B * Q * H * D == 0 || L * P == 0 || I == 0) return 1;  // all-zero gradients
+    if (B * Q * H * D == 0 || msda::samples(d) == 0 || I == 0) return 1;  // all-zero gradients
     switch (elem_size) {
     case 8: return msda::sorted_fits<double>(d) || msda::small_fits<double>(d);
     case 2: return msda::sorted_fits<_Float16>(d) || msda::small_fits<_Float16>(d);
@@ -54,4 +59,30 @@ extern "C" __attribute__((visibility("hidden"))) int64_t msda_fused_lp_limit_imp
         if (sc < best) best = sc;
     }
     return best;
+}
+
+namespace msda {
+int option_ws_passes();
+}
+
+// per-level point counts (include/msda_hip.h): the sizes above with S = sum of points_per_level samples per unit and P their
+// maximum
+extern "C" int64_t msda_bwd_ragged_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                                   const int32_t *points_per_level, int elem_size, int value_elem_size,
+                                                   int64_t max_level_cells, int flags)
+{
+    int64_t pmax, S;
+    if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || msda::ragged_counts(points_per_level, L, pmax, S) != 0) return 0;
+    return msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, pmax, elem_size, (flags & MSDA_WS_RECORDS_IN_GRADS) ? 1 : 0,
+                                         value_elem_size > 0 ? value_elem_size : elem_size, max_level_cells,
+                                         ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), S);
+}
+
+extern "C" int msda_bwd_ragged_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                         const int32_t *points_per_level, int elem_size)
+{
+    int64_t pmax, S;
+    if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || elem_size <= 0 || msda::ragged_counts(points_per_level, L, pmax, S) != 0)
+        return 0;
+    return msda_bwd_supported_impl(B, I, H, D, Q, L, pmax, elem_size, S);
 }

@@ -87,6 +87,50 @@ struct Params {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char msda_smem[];
 
+// Per-level point counts (msda_*_ragged_<dtype>): the samples of a (b, q, h) unit are S = sum_l P_l, level-major — level l
+// owns [pst[l], pst[l + 1]).  Every per-sample index keeps the form q * H * S + sl (Params::LP holds S); only the way a
+// sample finds its level and the per-level loops change, through the three helpers below.  The ragged kernels take this
+// derived struct as their kernarg (the uniform kernels keep Params and their code); Params::P holds max_l P_l there, which
+// is what the host's LDS and workspace sizing read.
+struct RaggedParams : Params {
+    int pst[kMaxLevels + 1];  // first sample of every level, pst[L] = S
+};
+template <typename PP> constexpr bool kRagged = std::is_same<PP, RaggedParams>::value;
+
+// The level of sample sl.  Uniform: one float division.  Ragged: a scan over the level starts, which sit in the kernel's
+// arguments — scalar loads at constant offsets (the unrolled loop keeps every index a constant: no indexed copy of the
+// array in private memory) and one v_cmp + v_addc per level, the exit on L uniform.  That costs less on gfx950 than a
+// sample -> level table in LDS: the table would need a staging pass and a barrier, and each lookup a ds_read round trip
+// on the dependent path of every sample, against L - 1 (2 ... 3 for DETR pyramids) VALU pairs on operands in SGPRs.
+__device__ __forceinline__ int lvl_of(const Params &p, int sl, float inv_P) { return div_small(sl, p.P, inv_P); }
+__device__ __forceinline__ int lvl_of(const RaggedParams &p, int sl, float)
+{
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < kMaxLevels; ++k) {
+        if (k >= p.L) break;
+        l += sl >= p.pst[k] ? 1 : 0;
+    }
+    return l;
+}
+// First sample of level l (l uniform, 0 <= l <= L).
+__device__ __forceinline__ int lvl_start(const RaggedParams &p, int l)
+{
+    int s = 0;
+#pragma unroll
+    for (int k = 1; k <= kMaxLevels; ++k) {
+        if (k > l) break;
+        s = p.pst[k];
+    }
+    return s;
+}
+// ... where `uniform` is what the uniform kernel computes for it, in the form its code has always had.
+__device__ __forceinline__ int lvl_start(const Params &, int, int uniform) { return uniform; }
+__device__ __forceinline__ int lvl_start(const RaggedParams &p, int l, int) { return lvl_start(p, l); }
+// Points of level l (l uniform).
+__device__ __forceinline__ int lvl_points(const Params &p, int) { return p.P; }
+__device__ __forceinline__ int lvl_points(const RaggedParams &p, int l) { return lvl_start(p, l + 1) - lvl_start(p, l); }
+
 template <typename A> struct alignas(16) Rec4 {
     A v[4];
 };
@@ -333,8 +377,8 @@ template <typename T, int VEC, bool FUSED> constexpr int fwd_waves_per_eu()
 {
     return (sizeof(T) == 2 && (FUSED || VEC * sizeof(T) < 16)) || sizeof(typename Traits<T>::acc) == 8 ? 4 : 5;
 }
-template <typename T, int VEC, int G, bool FUSED, typename TV = T, int BLK = kBlock, bool LDSL = false, typename TS = T>
-__global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlock ? fwd_waves_per_eu<T, VEC, FUSED>() : 4))) void msda_fwd_kernel(const Params p)
+template <typename T, int VEC, int G, bool FUSED, typename TV = T, int BLK = kBlock, bool LDSL = false, typename TS = T, typename PP = Params>
+__global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlock ? fwd_waves_per_eu<T, VEC, FUSED>() : 4))) void msda_fwd_kernel(const PP p)
 {
     using SR = Traits<TS>;
     static_assert(FUSED || sizeof(TS) == sizeof(T), "a separate storage type exists for the module kernels only");
@@ -551,7 +595,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                     const int sl = s0 + (f - imul24(fu, sc));
                     const int fq = wq0 + fu;
                     if (fq < q_end_) {
-                        const int l = div_small(sl, p.P, inv_P);
+                        const int l = lvl_of(p, sl, inv_P);
                         const int sidx = imul24(fq, HLP) + sl;
                         A sx, sy, a;
                         if constexpr (FUSED) {  // everything was parked by phase 0
@@ -617,7 +661,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                     const uint4 *uo = w_off + imul24(wunit, scp);
                     const Rec4<A> *uw = w_rec + imul24(wunit, scp);
                     // samples [0, s_lds) of this trip gather from memory, [s_lds, sc) from the LDS-resident levels
-                    const int s_lds = LDSL ? min(max(imul24(fl, p.P) - s0, 0), sc) : sc;
+                    const int s_lds = LDSL ? min(max(lvl_start(p, fl, imul24(fl, p.P)) - s0, 0), sc) : sc;
 #ifdef MSDA_DEV  // ablations (msda_set_option("debug", mask)): 256 no memory gather, 512 no LDS gather
                     const int s_mem_end = (p.debug & 256) ? 0 : s_lds, s_lds_end = (p.debug & 512) ? s_lds : sc;
 #else
@@ -712,9 +756,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
 // phase 1 runs with 16 of 64 lanes doing anything), a unit's rows take twice the load instructions, all still in flight
 // together.  Measured (msda_launch.hpp): ahead by ~1 us at Q = 200-300 when the rows come from HBM, behind by 0.3-0.6 us
 // when they are cached — option "unit_waves", off by default.
-template <typename T, int VEC, typename TV = T, int U = 1>
+// PP = RaggedParams (per-level point counts): the level starts follow Params at the END of the kernarg, so the preloaded
+// arguments above (the first 14 dwords: a_* and the front of Params) are the same as the uniform kernel's.
+template <typename T, int VEC, typename TV = T, int U = 1, typename PP = Params>
 __global__ __launch_bounds__(kWave) void msda_fwd_unit_kernel(const void *a_loc, const void *a_attn, const int64_t *a_shapes, int a_LP, int a_L,
-                                                              int a_units, const Params p)
+                                                              int a_units, const PP p)
 {
     using A = typename Traits<T>::acc;
     using TR = Traits<T>;
@@ -767,7 +813,7 @@ __global__ __launch_bounds__(kWave) void msda_fwd_unit_kernel(const void *a_loc,
             }
         }
         if (sl < p.LP) {
-            const int l = div_small(sl, p.P, 1.0f / (float)p.P);
+            const int l = lvl_of(p, sl, 1.0f / (float)p.P);
             Taps<A> t;
             make_taps<A>(TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), tab->h[l], tab->w[l], tab->start[l], p.zeros, p.align, row_bytes, t, plane_off);
             const A a = TR::to_acc(at), wy0 = (A)1 - t.dy, wx0 = (A)1 - t.dx;
@@ -825,8 +871,8 @@ __global__ __launch_bounds__(kWave) void msda_fwd_unit_kernel(const void *a_loc,
 // three results are reduced over the unit's G lanes with DPP moves and written exactly once.
 // ==========================================================================================
 // LDSL (BLK = kBlockLds): the coarsest levels served from LDS, as in the forward (reduce-scatter units only).
-template <typename T, int VEC, int G, bool FUSED, typename TV = T, int BLK = kBlock, bool LDSL = false, typename TS = T>
-__global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const Params p)
+template <typename T, int VEC, int G, bool FUSED, typename TV = T, int BLK = kBlock, bool LDSL = false, typename TS = T, typename PP = Params>
+__global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
 {
     using SR = Traits<TS>;  // (FUSED only: storage of the projection, grad_out and grad_proj; see msda_fwd_kernel)
     static_assert(FUSED || sizeof(TS) == sizeof(T), "a separate storage type exists for the module kernels only");
@@ -941,7 +987,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const Params p)
     // in every trip (P = 4 / 8: every level; a staged level in front of it is simply not used)
     int fl = cs.first;
     if constexpr (LDSL) {
-        while (fl < p.L && (imul24(fl, p.P) % G) != 0) ++fl;
+        while (fl < p.L && (lvl_start(p, fl, imul24(fl, p.P)) % G) != 0) ++fl;
         if (p.sc < p.LP && (p.sc % G) != 0) fl = p.L;
     }
 
@@ -1039,7 +1085,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const Params p)
                 const int sl = s0 + (f - imul24(fu, sc));
                 const int fq = wq0 + fu;
                 if (fq < q_end_) {
-                    const int l = div_small(sl, p.P, inv_P);
+                    const int l = lvl_of(p, sl, inv_P);
                     const int sidx = imul24(fq, HLP) + sl;
                     const int lh = tab->h[l], lw = tab->w[l];
                     A px, py, a;
@@ -1241,7 +1287,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const Params p)
                         };
                         // samples [0, s_lds) of this trip gather from memory, [s_lds, sc) from the LDS-resident levels (the
                         // boundary is a multiple of G: `fl` was chosen that way)
-                        const int s_lds = LDSL ? min(max(imul24(fl, p.P) - s0, 0), sc) : sc;
+                        const int s_lds = LDSL ? min(max(lvl_start(p, fl, imul24(fl, p.P)) - s0, 0), sc) : sc;
                         for (int sb = 0; sb < s_lds; sb += G) batch(sb, std::false_type{});
                         if constexpr (LDSL)
                             for (int sb = s_lds; sb < sc; sb += G) batch(sb, std::true_type{});

@@ -64,7 +64,9 @@ template <typename K> inline void allow_big_lds(K kernel, std::atomic<uint64_t> 
 struct Dims {
     int64_t B, I, H, D, Q, L, P;
     int64_t cells = 0;  // the caller's max_level_cells argument: no level has more bilinear cells (0: unknown)
+    int64_t S = 0;      // samples per (b, q, h) unit with per-level point counts (P is then their maximum); 0: L * P
 };
+inline int64_t samples(const Dims &d) { return d.S > 0 ? d.S : d.L * d.P; }
 // ... or the process-wide promise (msda_set_option("level_cells", n)); 0: unknown
 inline int64_t level_cells_bound(const Dims &d) { return d.cells > 0 ? d.cells : (int64_t)option_level_cells(); }
 
@@ -84,9 +86,9 @@ inline int check_common(const Dims &d, int padding_mode, const void *const *ptrs
         return MSDA_ERR_TOO_MANY_LEVELS;
     }
     const int64_t lim = (int64_t)1 << 31;
-    if (d.I * d.H * d.D * (int64_t)sizeof(T) >= lim || d.B >= lim || d.Q >= lim || d.L * d.P >= (1 << 22) ||
-        d.B * d.H >= (1 << 28) || d.Q * d.H * d.L * d.P * 2 >= lim || d.Q * d.H * d.D * (int64_t)sizeof(T) >= lim || d.I >= (1 << 24) ||
-        d.Q >= (1 << 24) || d.H * d.L * d.P >= (1 << 24) || d.H * d.D * (int64_t)sizeof(T) >= (1 << 24)) {
+    if (d.I * d.H * d.D * (int64_t)sizeof(T) >= lim || d.B >= lim || d.Q >= lim || samples(d) >= (1 << 22) ||
+        d.B * d.H >= (1 << 28) || d.Q * d.H * samples(d) * 2 >= lim || d.Q * d.H * d.D * (int64_t)sizeof(T) >= lim || d.I >= (1 << 24) ||
+        d.Q >= (1 << 24) || d.H * samples(d) >= (1 << 24) || d.H * d.D * (int64_t)sizeof(T) >= (1 << 24)) {
         set_error("tensor too large for 32-bit plane offsets (I*H*D*sizeof = %lld bytes)",
                   (long long)(d.I * d.H * d.D * (int64_t)sizeof(T)));
         return MSDA_ERR_TOO_LARGE;
@@ -153,7 +155,7 @@ inline int touch_plan(const Dims &d)
 {
     const int o = option_touch();
     if (o != 1) return o;  // (2: forced)
-    return d.Q * d.L * d.P * 4 >= 2 * d.I && d.B * d.Q * d.H <= 65536;
+    return d.Q * samples(d) * 4 >= 2 * d.I && d.B * d.Q * d.H <= 65536;
 }
 // ... and, known once the grid is: only launches of ONE round of workgroups in which a workgroup touches at most 768 rows.
 // The touches go through the texture path in front of the workgroup's first samples (one row per lane: 64 tag look-ups per
@@ -326,7 +328,7 @@ template <typename T, int G, typename TV> inline LdsLevelsPlan lds_levels_plan(c
     return lds_levels_plan_rt(p, G, sizeof(typename Traits<T>::acc), sizeof(TV), aux, stage);
 }
 
-template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T> inline int launch_gather_lds(Params &p, const LdsLevelsPlan &pl, hipStream_t stream)
+template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T, typename PP = Params> inline int launch_gather_lds(PP &p, const LdsLevelsPlan &pl, hipStream_t stream)
 {
     // MODE as in launch_gather: the forward and sample-gradient kernels, plain (0, 1) and with the module prologue (2, 3)
     p.sc = pl.sc;
@@ -354,18 +356,18 @@ template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T> in
     }
     const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
     if constexpr (MODE == 0 || MODE == 2) {
-        auto kernel = msda_fwd_kernel<T, VEC, G, MODE == 2, TV, kBlockLds, true, std::conditional_t<MODE == 2, TS, T>>;
+        auto kernel = msda_fwd_kernel<T, VEC, G, MODE == 2, TV, kBlockLds, true, std::conditional_t<MODE == 2, TS, T>, PP>;
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlockLds), pl.lds, stream, p);
     } else {
-        auto kernel = msda_bwd_sample_kernel<T, VEC, G, MODE == 3, TV, kBlockLds, true, std::conditional_t<MODE == 3, TS, T>>;
+        auto kernel = msda_bwd_sample_kernel<T, VEC, G, MODE == 3, TV, kBlockLds, true, std::conditional_t<MODE == 3, TS, T>, PP>;
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlockLds), pl.lds, stream, p);
     }
     return (int)hipGetLastError();
 }
 
-template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T> inline int launch_gather(Params &p, hipStream_t stream)
+template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T, typename PP = Params> inline int launch_gather(PP &p, hipStream_t stream)
 {
     using A = typename Traits<T>::acc;
     constexpr int NU = kBlock / G;
@@ -392,13 +394,13 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
             const bool pairs_ok = gl <= kWave / 2 && (size_t)p.B * p.I * (size_t)p.v_row < ((size_t)1 << 31);
             if (pairs_ok && option_unit_waves() == 2) {
                 p.div_win = make_fast_div((uint32_t)p.Q);  // (the forward has no other use for this field)
-                auto kernel = msda_fwd_unit_kernel<T, VEC, TV, 2>;
+                auto kernel = msda_fwd_unit_kernel<T, VEC, TV, 2, PP>;
                 allow_big_lds(kernel, big_lds_unit2);
                 const size_t ulds = kGatherLdsFixed + (size_t)2 * 8 * p.LP * 4;
                 hipLaunchKernelGGL(kernel, dim3((unsigned)((units + 1) / 2)), dim3(kWave), ulds, stream, p.loc, p.attn, p.shapes, p.LP, p.L,
                                    (int)units, p);
             } else {
-                auto kernel = msda_fwd_unit_kernel<T, VEC, TV, 1>;
+                auto kernel = msda_fwd_unit_kernel<T, VEC, TV, 1, PP>;
                 allow_big_lds(kernel, big_lds_unit);
                 const size_t ulds = kGatherLdsFixed + (size_t)8 * p.LP * 4;
                 hipLaunchKernelGGL(kernel, dim3((unsigned)units), dim3(kWave), ulds, stream, p.loc, p.attn, p.shapes, p.LP, p.L, (int)units, p);
@@ -414,7 +416,7 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         // (fp32 arithmetic; the rows may be 16-bit — the mixed-storage and module-storage kernels: 8-byte pieces, half the LDS)
         const LdsLevelsPlan pl = lds_levels_plan_rt(p, G, sizeof(A), sizeof(TV), MODE == 3, MODE == 1, /*two planes*/ MODE != 1);
         // (not the plain sample-gradient kernel: it would give up its LDS-DMA prefetch for them — 92.9 against 92.7 us, a draw)
-        if (pl.use && (MODE < 2 || pl.sc == p.LP)) return launch_gather_lds<T, VEC, G, MODE, TV, TS>(p, pl, stream);
+        if (pl.use && (MODE < 2 || pl.sc == p.LP)) return launch_gather_lds<T, VEC, G, MODE, TV, TS, PP>(p, pl, stream);
     }
     size_t lds;
     plan_gather(NU, p.LP, sizeof(A), p.sc, lds, MODE == 3);
@@ -454,7 +456,7 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, p);
     } else if constexpr (MODE == 1) {
-        auto kernel = msda_bwd_sample_kernel<T, VEC, G, false, TV>;
+        auto kernel = msda_bwd_sample_kernel<T, VEC, G, false, TV, kBlock, false, T, PP>;
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, p);
     } else if constexpr (MODE == 2) {
@@ -462,14 +464,14 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, p);
     } else {
-        auto kernel = msda_fwd_kernel<T, VEC, G, false, TV>;
+        auto kernel = msda_fwd_kernel<T, VEC, G, false, TV, kBlock, false, T, PP>;
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, p);
     }
     return (int)hipGetLastError();
 }
 
-template <typename T, int VEC, int MODE, typename TV = T, typename TS = T> inline int dispatch_group(Params &p, hipStream_t stream)
+template <typename T, int VEC, int MODE, typename TV = T, typename TS = T, typename PP = Params> inline int dispatch_group(PP &p, hipStream_t stream)
 {
     const int lanes = (p.D + VEC - 1) / VEC;
     switch (pick_group(lanes)) {
@@ -481,7 +483,7 @@ template <typename T, int VEC, int MODE, typename TV = T, typename TS = T> inlin
     }
 }
 
-template <typename T, int MODE, typename TV = T, typename TS = T> inline int dispatch_gather(Params &p, bool vec_ok, hipStream_t stream)
+template <typename T, int MODE, typename TV = T, typename TS = T, typename PP = Params> inline int dispatch_gather(PP &p, bool vec_ok, hipStream_t stream)
 {
     constexpr int VECF = 16 / sizeof(T);  // channels per lane (mixed storage: the 16-bit value rows load as 8-byte pieces)
     // the 16-bit operators' forward: when the LDS-served-level variant would be taken, as units of 8-byte pieces (twice the
@@ -562,11 +564,11 @@ template <typename T> inline bool value_vec_ok(const Params &p)
     return aligned_to(p.grad_out, 16) && aligned_to(p.grad_value, 16) && (p.D % VECF) == 0;
 }
 
-template <typename T, typename TV = T, typename TS = T> inline int run_value_sorted(Params &p, const Dims &d, void *workspace, hipStream_t stream)
+template <typename T, typename TV = T, typename TS = T, typename PP = Params> inline int run_value_sorted(PP &p, const Dims &d, void *workspace, hipStream_t stream)
 {
     using A = typename Traits<T>::acc;
     const bool vec_ok = value_vec_ok<T>(p);
-    const SortedWsLayout w = sorted_ws_layout(d.B, d.I, d.H, d.D, d.Q, d.L, d.P, sizeof(A), sizeof(T), vec_ok, p.ent_alt0 != nullptr, sizeof(TV));
+    const SortedWsLayout w = sorted_ws_layout(d.B, d.I, d.H, d.D, d.Q, d.L, samples(d), sizeof(A), sizeof(T), vec_ok, p.ent_alt0 != nullptr, sizeof(TV));
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     p.ws_part = reinterpret_cast<int *>(ws + w.off_part);
     p.ws_blocktot = reinterpret_cast<int *>(ws + w.off_blocktot);
@@ -584,7 +586,7 @@ template <typename T, typename TV = T, typename TS = T> inline int run_value_sor
     p.win_cap = w.win_cap;
     p.cont_cap = w.cont_cap;
     p.nsplit = w.nsplit;
-    p.ent_cap = (int)((int64_t)w.q_round * d.L * d.P);
+    p.ent_cap = (int)((int64_t)w.q_round * samples(d));
     p.ent_n0 = w.ent_n0;  // (0 / 0 / 0 unless run_bwd offered the caller's gradient buffers: p.ent_alt0 / ent_alt1 / ent_alt2)
     p.ent_n1 = w.ent_n1;
     p.ent_n2 = w.ent_n2;
@@ -659,8 +661,8 @@ template <typename T, typename TV = T, typename TS = T> inline int run_value_sor
         g3_place = p.grid3d;
         map_place = p.xcd_map;
         static std::atomic<uint64_t> big_lds_lm{0}, big_lds_lm_small{0};
-        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlock>, big_lds_lm);
-        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlockSmall>, big_lds_lm_small);
+        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlock, PP>, big_lds_lm);
+        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlockSmall, PP>, big_lds_lm_small);
     }
     for (int r = 0; r < w.rounds; ++r) {  // one round unless Q is so large that a plane's grad_out rows leave L2
         p.q_begin = r * w.q_round;
@@ -671,11 +673,11 @@ template <typename T, typename TV = T, typename TS = T> inline int run_value_sor
         p.cell_cap = cell_cap_pm;
         {
             const ProfileScope prof("msda_cell_pass_kernel<count>", stream);
-            hipLaunchKernelGGL((msda_cell_pass_kernel<T, false>), gcell, dim3(kCellBlock), cell_lds, stream, p);
+            hipLaunchKernelGGL((msda_cell_pass_kernel<T, false, PP>), gcell, dim3(kCellBlock), cell_lds, stream, p);
         }
         {
             const ProfileScope prof("msda_cell_scan_kernel", stream);
-            hipLaunchKernelGGL((msda_cell_scan_kernel<T>), dim3((unsigned)scan_blocks), dim3(kScanCells), 0, stream, p);
+            hipLaunchKernelGGL((msda_cell_scan_kernel<T>), dim3((unsigned)scan_blocks), dim3(kScanCells), 0, stream, static_cast<const Params &>(p));
         }
         {
         const ProfileScope prof_place(place_lm ? "msda_cell_place_lm_kernel" : "msda_cell_pass_kernel<place>", stream);
@@ -684,11 +686,11 @@ template <typename T, typename TV = T, typename TS = T> inline int run_value_sor
             p.xcd_map = map_place;
             p.cell_cap = place_cells;
             if (place_small)
-                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlockSmall>), gplace, dim3(kPlaceBlockSmall), (size_t)place_cells * 4, stream, p);
+                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlockSmall, PP>), gplace, dim3(kPlaceBlockSmall), (size_t)place_cells * 4, stream, p);
             else
-                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlock>), gplace, dim3(kPlaceBlock), (size_t)place_cells * 4, stream, p);
+                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlock, PP>), gplace, dim3(kPlaceBlock), (size_t)place_cells * 4, stream, p);
         } else {
-            hipLaunchKernelGGL((msda_cell_pass_kernel<T, true>), gcell, dim3(kCellBlock), cell_lds, stream, p);
+            hipLaunchKernelGGL((msda_cell_pass_kernel<T, true, PP>), gcell, dim3(kCellBlock), cell_lds, stream, p);
         }
         }
         int rc = (int)hipGetLastError();
@@ -726,7 +728,7 @@ inline void fill_params(Params &p, const Dims &d, int padding_mode, int align_co
     p.Q = (int)d.Q;
     p.L = (int)d.L;
     p.P = (int)d.P;
-    p.LP = (int)(d.L * d.P);
+    p.LP = (int)samples(d);
     p.zeros = padding_mode == MSDA_PADDING_ZEROS;
     p.align = align_corners != 0;
     p.xcd_map = option_xcd_map();
@@ -739,19 +741,53 @@ inline void fill_params(Params &p, const Dims &d, int padding_mode, int align_co
     p.div_h = make_fast_div((uint32_t)d.H);
 }
 
-template <typename T, typename TV = T>
+// Per-level point counts (msda_*_ragged_<dtype>): the host array `ppl` of L counts, each >= 1.  Checks it and returns the
+// largest count (the kernels' Params::P) and the sum S; a negative MSDA_ERR_* when it is unusable.
+inline int ragged_counts(const int32_t *ppl, int64_t L, int64_t &pmax, int64_t &S)
+{
+    pmax = S = 0;
+    if (L < 0 || (L > 0 && ppl == nullptr)) {
+        set_error("points_per_level: null pointer or negative L");
+        return MSDA_ERR_BAD_ARG;
+    }
+    if (L > MSDA_MAX_LEVELS) {
+        set_error("L = %lld > %d levels", (long long)L, MSDA_MAX_LEVELS);
+        return MSDA_ERR_TOO_MANY_LEVELS;
+    }
+    for (int64_t l = 0; l < L; ++l) {
+        if (ppl[l] < 1) {
+            set_error("points_per_level[%lld] = %d: every level needs at least one point", (long long)l, (int)ppl[l]);
+            return MSDA_ERR_BAD_ARG;
+        }
+        pmax = ppl[l] > pmax ? ppl[l] : pmax;
+        S += ppl[l];
+    }
+    return 0;
+}
+inline void fill_level_starts(RaggedParams &p, const int32_t *ppl, int64_t L)
+{
+    p.pst[0] = 0;
+    for (int64_t l = 0; l < L; ++l) p.pst[l + 1] = p.pst[l] + ppl[l];
+    for (int64_t l = L + 1; l <= kMaxLevels; ++l) p.pst[l] = p.pst[L];
+}
+inline void fill_level_starts(Params &, const int32_t *, int64_t) {}
+
+// PP = RaggedParams: per-level point counts `ppl` (ragged_counts checked them; P is their maximum)
+template <typename T, typename TV = T, typename PP = Params>
 int run_fwd(const void *value, const int64_t *shapes, const void *loc, const void *attn, void *out, int64_t B,
             int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int padding_mode, int align_corners,
-            int64_t value_row_stride, void *stream_)
+            int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr)
 {
-    const Dims d{B, I, H, D, Q, L, P};
+    Dims d{B, I, H, D, Q, L, P};
+    if (ppl != nullptr)
+        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const size_t out_bytes = (size_t)(B * Q * H * D) * sizeof(T);
     if (out_bytes == 0) return 0;  // nothing to produce
     const void *ptrs[] = {out};
     int rc = check_common<T>(d, padding_mode, ptrs, 1);
     if (rc) return rc;
-    if (L * P == 0 || I == 0) {  // empty sum
+    if (samples(d) == 0 || I == 0) {  // empty sum
         return (int)hipMemsetAsync(out, 0, out_bytes, stream);
     }
     const void *ptrs2[] = {value, shapes, loc, attn};
@@ -762,13 +798,14 @@ int run_fwd(const void *value, const int64_t *shapes, const void *loc, const voi
         set_error("misaligned buffer");
         return MSDA_ERR_MISALIGNED;
     }
-    Params p{};
+    PP p{};
     p.value = value;
     p.shapes = shapes;
     p.loc = loc;
     p.attn = attn;
     p.out = out;
     fill_params(p, d, padding_mode, align_corners);
+    fill_level_starts(p, ppl, L);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.touch = touch_plan(d);
@@ -842,7 +879,7 @@ template <typename T> inline size_t small_need_bytes(const Dims &d, bool vec)
     return small_lds_bytes((size_t)small_cell_cap(d), (size_t)(d.Q * d.P), sizeof(A), vecw);
 }
 
-template <typename T, int VEC, int G, typename TV = T, typename TS = T> inline int launch_value_small(Params &p, size_t lds, hipStream_t stream)
+template <typename T, int VEC, int G, typename TV = T, typename TS = T, typename PP = Params> inline int launch_value_small(PP &p, size_t lds, hipStream_t stream)
 {
     dim3 grid;
     if (!plane_grid(p, p.B * p.H, (int64_t)p.L * p.small_ns, grid)) {
@@ -850,13 +887,13 @@ template <typename T, int VEC, int G, typename TV = T, typename TS = T> inline i
         return MSDA_ERR_TOO_LARGE;
     }
     static std::atomic<uint64_t> big_lds_done{0};
-    allow_big_lds(msda_value_small_kernel<T, VEC, G, TV, TS>, big_lds_done);
+    allow_big_lds(msda_value_small_kernel<T, VEC, G, TV, TS, PP>, big_lds_done);
     const ProfileScope prof("msda_value_small_kernel", stream);
-    hipLaunchKernelGGL((msda_value_small_kernel<T, VEC, G, TV, TS>), grid, dim3(kSmallBlock), lds, stream, p);
+    hipLaunchKernelGGL((msda_value_small_kernel<T, VEC, G, TV, TS, PP>), grid, dim3(kSmallBlock), lds, stream, p);
     return (int)hipGetLastError();
 }
 
-template <typename T, int VEC, typename TV = T, typename TS = T> inline int dispatch_value_small_group(Params &p, size_t lds, hipStream_t stream)
+template <typename T, int VEC, typename TV = T, typename TS = T, typename PP = Params> inline int dispatch_value_small_group(PP &p, size_t lds, hipStream_t stream)
 {
     const int lanes = (p.D + VEC - 1) / VEC;
     switch (pick_group(lanes)) {
@@ -868,7 +905,7 @@ template <typename T, int VEC, typename TV = T, typename TS = T> inline int disp
     }
 }
 
-template <typename T, typename TV = T, typename TS = T> inline int run_value_small(Params &p, const Dims &d, hipStream_t stream)
+template <typename T, typename TV = T, typename TS = T, typename PP = Params> inline int run_value_small(PP &p, const Dims &d, hipStream_t stream)
 {
     constexpr int VECF = 16 / sizeof(T);
     const bool vec_ok = value_vec_ok<T>(p);
@@ -922,9 +959,9 @@ template <typename T, typename TV> inline int64_t value_batch_per_pass(const Par
     for (int64_t passes = 1;; passes *= 2) {  // (until one batch element per pass)
         const int64_t per = (d.B + passes - 1) / passes;
         const bool rg = p.ent_alt0 != nullptr;
-        size_t need = sorted_ws_layout(per, d.I, d.H, d.D, d.Q, d.L, d.P, sizeof(A), sizeof(T), value_vec_ok<T>(p), rg, sizeof(TV)).total;
+        size_t need = sorted_ws_layout(per, d.I, d.H, d.D, d.Q, d.L, samples(d), sizeof(A), sizeof(T), value_vec_ok<T>(p), rg, sizeof(TV)).total;
         if (passes > 1) {  // (a later group's pointers may be aligned differently: the larger of the two layouts, as the size query)
-            const size_t other = sorted_ws_layout(per, d.I, d.H, d.D, d.Q, d.L, d.P, sizeof(A), sizeof(T), !value_vec_ok<T>(p), rg, sizeof(TV)).total;
+            const size_t other = sorted_ws_layout(per, d.I, d.H, d.D, d.Q, d.L, samples(d), sizeof(A), sizeof(T), !value_vec_ok<T>(p), rg, sizeof(TV)).total;
             if (other > need) need = other;
         }
         if ((uint64_t)workspace_bytes >= need) return per;
@@ -933,8 +970,17 @@ template <typename T, typename TV> inline int64_t value_batch_per_pass(const Par
     return 0;
 }
 
-template <typename T, typename TV = T, typename TS = T>
-inline int run_value(Params &p, const Dims &d, void *workspace, int64_t workspace_bytes, hipStream_t stream)
+// MSDA_WS_RECORDS_IN_GRADS with `per` batch elements per pass: every group's share of grad_loc / grad_attn must start on a
+// 16-byte boundary.  One pass: always.  Several: required of ONE batch element's share, so that the answer does not
+// depend on which group size the call ends up with — the workspace query sizes for ceil(B / n) with any n, the call
+// takes the fewest power-of-two passes that fit the workspace it is given, and both must agree.
+inline bool records_fit_grads(const Dims &d, int64_t per, size_t elem)
+{
+    return per >= d.B || ((size_t)(d.Q * d.H * samples(d)) * elem) % 16 == 0;
+}
+
+template <typename T, typename TV = T, typename TS = T, typename PP = Params>
+inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_bytes, hipStream_t stream)
 {
     using A = typename Traits<T>::acc;
     const int64_t B = d.B, I = d.I, H = d.H, D = d.D, Q = d.Q, L = d.L, P = d.P;
@@ -954,11 +1000,11 @@ inline int run_value(Params &p, const Dims &d, void *workspace, int64_t workspac
         note_launch(7, (int)((B + per - 1) / per));
         for (int64_t b0 = 0; b0 < B && rc == 0; b0 += per) {
             const int64_t nb = per < B - b0 ? per : B - b0;
-            Params pg = p;
+            PP pg = p;
             Dims dg = d;
             dg.B = nb;
             pg.B = (int)nb;
-            const size_t ns0 = (size_t)(b0 * Q * H * L * P);
+            const size_t ns0 = (size_t)(b0 * Q * H * samples(d));
             pg.loc = static_cast<const unsigned char *>(p.loc) + ns0 * 2 * sizeof(T);
             pg.attn = static_cast<const unsigned char *>(p.attn) + ns0 * sizeof(T);
             pg.grad_out = static_cast<const unsigned char *>(p.grad_out) + (size_t)(b0 * Q * H * D) * sizeof(TS);
@@ -977,10 +1023,10 @@ inline int run_value(Params &p, const Dims &d, void *workspace, int64_t workspac
         return MSDA_ERR_UNSUPPORTED;
     } else {
         // (the size msda_bwd_workspace_bytes reports: the larger of the vector and the scalar layout)
-        const size_t v1 = sorted_ws_layout(B, I, H, D, Q, L, P, sizeof(A), sizeof(T), true).total;
-        const size_t v0 = sorted_ws_layout(B, I, H, D, Q, L, P, sizeof(A), sizeof(T), false).total;
-        const size_t m1 = sorted_ws_layout(1, I, H, D, Q, L, P, sizeof(A), sizeof(T), true).total;
-        const size_t m0 = sorted_ws_layout(1, I, H, D, Q, L, P, sizeof(A), sizeof(T), false).total;
+        const size_t v1 = sorted_ws_layout(B, I, H, D, Q, L, samples(d), sizeof(A), sizeof(T), true).total;
+        const size_t v0 = sorted_ws_layout(B, I, H, D, Q, L, samples(d), sizeof(A), sizeof(T), false).total;
+        const size_t m1 = sorted_ws_layout(1, I, H, D, Q, L, samples(d), sizeof(A), sizeof(T), true).total;
+        const size_t m0 = sorted_ws_layout(1, I, H, D, Q, L, samples(d), sizeof(A), sizeof(T), false).total;
         set_error("grad_value needs a 256-byte aligned workspace of msda_bwd_workspace_bytes(...) = %zu bytes (at least %zu: one "
                   "batch element per pass); got %lld", v1 > v0 ? v1 : v0, m1 > m0 ? m1 : m0, (long long)(workspace ? workspace_bytes : 0));
         return MSDA_ERR_BAD_ARG;
@@ -989,19 +1035,21 @@ inline int run_value(Params &p, const Dims &d, void *workspace, int64_t workspac
     return rc;
 }
 
-template <typename T, typename TV = T>
+template <typename T, typename TV = T, typename PP = Params>
 int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, const void *loc, const void *attn,
             void *grad_value, void *grad_loc, void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,
             int64_t L, int64_t P, int padding_mode, int align_corners, int64_t max_level_cells, int64_t value_row_stride,
-            void *workspace, int64_t workspace_bytes, void *stream_)
+            void *workspace, int64_t workspace_bytes, void *stream_, const int32_t *ppl = nullptr)
 {
-    const Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
+    Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
+    if (ppl != nullptr)
+        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc = check_common<T>(d, padding_mode, nullptr, 0);
     if (rc) return rc;
     const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
-    const size_t ns = (size_t)(B * Q * H * L * P);
-    if (B * Q * H * D == 0 || L * P == 0 || I == 0) {  // no sample touches anything: all gradients are zero
+    const size_t ns = (size_t)(B * Q * H * samples(d));
+    if (B * Q * H * D == 0 || samples(d) == 0 || I == 0) {  // no sample touches anything: all gradients are zero
         hipError_t e = hipSuccess;
         if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
         if (e == hipSuccess && ns && grad_loc) e = hipMemsetAsync(grad_loc, 0, ns * 2 * sizeof(T), stream);
@@ -1023,7 +1071,7 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
         set_error("misaligned buffer");
         return MSDA_ERR_MISALIGNED;
     }
-    Params p{};
+    PP p{};
     p.value = value;
     p.shapes = shapes;
     p.loc = loc;
@@ -1033,6 +1081,7 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
     p.grad_loc = grad_loc;
     p.grad_attn = grad_attn;
     fill_params(p, d, padding_mode, align_corners);
+    fill_level_starts(p, ppl, L);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     // Both halves wanted, one after the other: the sorted records are dead once the gather has run and grad_loc /
@@ -1041,12 +1090,20 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
     // into grad_value itself, which only the finish kernel writes, behind the gather (single-round problems).  The
     // workspace layout shrinks accordingly (msda_bwd_workspace_bytes with MSDA_WS_RECORDS_IN_GRADS); a caller that
     // passes the full size loses nothing.
-    const bool records_in_grads = want_sample && want_value && option_records_in_grads() != 0 && option_overlap() != 1 &&
-                                  aligned_to(grad_loc, 16) && aligned_to(grad_attn, 16) && aligned_to(grad_value, 16);
+    bool records_in_grads = want_sample && want_value && option_records_in_grads() != 0 && option_overlap() != 1 &&
+                            aligned_to(grad_loc, 16) && aligned_to(grad_attn, 16) && aligned_to(grad_value, 16);
     if (records_in_grads) {
         p.ent_alt0 = grad_loc;
         p.ent_alt1 = grad_attn;
         p.ent_alt2 = grad_value;
+        // several passes over the batch: group g's records start g * per * Q * H * S samples into grad_loc / grad_attn,
+        // which must be 16-byte aligned too (an odd S makes that common with per-level point counts); otherwise the
+        // records stay in the workspace — which msda_bwd_workspace_bytes sizes by the same rule (records_fit_grads)
+        const int64_t per = value_batch_per_pass<T, TV>(p, d, workspace, workspace_bytes);
+        if (per > 0 && !records_fit_grads(d, per, sizeof(T))) {
+            records_in_grads = false;
+            p.ent_alt0 = p.ent_alt1 = p.ent_alt2 = nullptr;
+        }
     }
     const bool vec_sample = aligned_to(value, 16) && aligned_to(grad_out, 16) && p.v_row % 16 == 0;
     // The two halves of the backward are independent: when both are wanted, grad_loc/grad_attn run on a
@@ -1224,6 +1281,33 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                       grad_ref_partial, B, I, H, D, Q, L, P, ref_dim, padding_mode,              \
                                       align_corners, max_level_cells, value_row_stride, workspace,               \
                                       workspace_bytes, stream);                                                  \
+    }                                                                                                            \
+    extern "C" int msda_fwd_ragged_##SUF(const void *value, const int64_t *shapes, const void *loc, const void *attn, \
+                                         void *out, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, \
+                                         const int32_t *points_per_level, int padding_mode, int align_corners,    \
+                                         int64_t value_row_stride, void *stream)                                 \
+    {                                                                                                            \
+        int64_t pmax, S;                                                                                         \
+        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
+        if (rc) return rc;                                                                                       \
+        return msda::run_fwd<T, TV, msda::RaggedParams>(value, shapes, loc, attn, out, B, I, H, D, Q, L, pmax,   \
+                                                        padding_mode, align_corners, value_row_stride, stream,   \
+                                                        points_per_level);                                       \
+    }                                                                                                            \
+    extern "C" int msda_bwd_ragged_##SUF(const void *grad_out, const void *value, const int64_t *shapes,        \
+                                         const void *loc, const void *attn, void *grad_value, void *grad_loc,   \
+                                         void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, \
+                                         int64_t L, const int32_t *points_per_level, int padding_mode,           \
+                                         int align_corners, int64_t max_level_cells, int64_t value_row_stride,   \
+                                         void *workspace, int64_t workspace_bytes, void *stream)                 \
+    {                                                                                                            \
+        int64_t pmax, S;                                                                                         \
+        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
+        if (rc) return rc;                                                                                       \
+        return msda::run_bwd<T, TV, msda::RaggedParams>(grad_out, value, shapes, loc, attn, grad_value, grad_loc, \
+                                                        grad_attn, B, I, H, D, Q, L, pmax, padding_mode,         \
+                                                        align_corners, max_level_cells, value_row_stride,        \
+                                                        workspace, workspace_bytes, stream, points_per_level);   \
     }
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to

@@ -183,6 +183,107 @@ public:
     }
 };
 
+// Per-level point counts (msda_fwd_ragged_ / msda_bwd_ragged_<dtype>, ABI 12): sampling points [B, Q, H, S, 2], attention
+// weights [B, Q, H, S], `counts` the L point counts (host numbers; the Python caller checked them and that they are not
+// all equal).  The same node as MSDAFunction otherwise: decoder-sized calls spend more host time than device time.
+using FwdRaggedFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
+                            int64_t, int64_t, int64_t, const int32_t *, int, int, int64_t, void *);
+using BwdRaggedFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *, void *,
+                            int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int, int, int64_t,
+                            int64_t, void *, int64_t, void *);
+std::pair<FwdRaggedFn, BwdRaggedFn> ragged_fns_for(at::ScalarType t, at::ScalarType c)
+{
+    if (t != c) {
+        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
+                          "unsupported dtype combination: value ", t, " with ", c);
+        if (t == at::kBFloat16) return {msda_fwd_ragged_f32_vbf16, msda_bwd_ragged_f32_vbf16};
+        return {msda_fwd_ragged_f32_vf16, msda_bwd_ragged_f32_vf16};
+    }
+    switch (t) {
+    case at::kFloat: return {msda_fwd_ragged_f32, msda_bwd_ragged_f32};
+    case at::kHalf: return {msda_fwd_ragged_f16, msda_bwd_ragged_f16};
+    case at::kBFloat16: return {msda_fwd_ragged_bf16, msda_bwd_ragged_bf16};
+    case at::kDouble: return {msda_fwd_ragged_f64, msda_bwd_ragged_f64};
+    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
+    }
+}
+
+class MSDARaggedFunction : public torch::autograd::Function<MSDARaggedFunction> {
+public:
+    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
+                              const at::Tensor &pts_, const at::Tensor &att_, int64_t padding_mode, bool align_corners,
+                              int64_t level_cells, const std::vector<int64_t> &counts)
+    {
+        const auto [img, vrow] = value_rows(img_);
+        const at::Tensor pts = pts_.contiguous(), att = att_.contiguous();
+        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        at::Tensor out = at::empty({B, Q, H, D}, pts.options());
+        const c10::DeviceGuard guard(img.device());
+        check_rc(ragged_fns_for(img.scalar_type(), pts.scalar_type())
+                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(), out.data_ptr(), B,
+                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), (int)padding_mode, align_corners ? 1 : 0, vrow,
+                            current_stream(img)),
+                 "msda_fwd_ragged");
+        ctx->save_for_backward({img, shapes, pts, att});
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["align_corners"] = align_corners;
+        ctx->saved_data["level_cells"] = level_cells;
+        ctx->saved_data["vrow"] = vrow;
+        ctx->saved_data["counts"] = counts;
+        return out;
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
+                                                   torch::autograd::variable_list grads)
+    {
+        const auto saved = ctx->get_saved_variables();
+        const at::Tensor &img = saved[0], &shapes = saved[1], &pts = saved[2], &att = saved[3];
+        const int64_t vrow = ctx->saved_data["vrow"].toInt();
+        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
+        const bool align_corners = ctx->saved_data["align_corners"].toBool();
+        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
+        const auto counts = ctx->saved_data["counts"].toIntVector();
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        const int64_t L = (int64_t)ppl.size();
+        at::Tensor gout = grads[0].contiguous();
+        if (gout.scalar_type() != pts.scalar_type()) gout = gout.to(pts.scalar_type());
+        const bool want_value = ctx->needs_input_grad(0);
+        const bool want_sample = ctx->needs_input_grad(2) || ctx->needs_input_grad(3);
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
+        at::Tensor g_img, g_pts, g_att, ws;
+        int64_t ws_bytes = 0;
+        if (want_sample) {
+            g_pts = at::empty_like(pts);
+            g_att = at::empty_like(att);
+        }
+        if (want_value) {
+            g_img = at::empty(img.sizes(), img.options());
+            const bool in_grads = want_sample && reinterpret_cast<uintptr_t>(g_pts.data_ptr()) % 16 == 0 &&
+                                  reinterpret_cast<uintptr_t>(g_att.data_ptr()) % 16 == 0 &&
+                                  reinterpret_cast<uintptr_t>(g_img.data_ptr()) % 16 == 0 && msda_get_option("overlap") != 1;
+            ws_bytes = msda_bwd_ragged_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)pts.element_size(),
+                                                       (int)img.element_size(), level_cells,
+                                                       in_grads ? MSDA_WS_RECORDS_IN_GRADS : 0);
+            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
+        }
+        if (want_value || want_sample) {
+            const c10::DeviceGuard guard(img.device());
+            check_rc(ragged_fns_for(img.scalar_type(), pts.scalar_type())
+                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(),
+                                 want_value ? g_img.data_ptr() : nullptr, want_sample ? g_pts.data_ptr() : nullptr,
+                                 want_sample ? g_att.data_ptr() : nullptr, B, I, H, D, Q, L, ppl.data(), padding_mode,
+                                 align_corners ? 1 : 0, level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr, ws_bytes,
+                                 current_stream(img)),
+                     "msda_bwd_ragged");
+        }
+        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_pts : at::Tensor(),
+                                           ctx->needs_input_grad(3) ? g_att : at::Tensor(), at::Tensor(), at::Tensor(),
+                                           at::Tensor(), at::Tensor()});
+    }
+};
+
 // The module core with its prologue fused in (msda_fwd_fused_ / msda_bwd_fused_<dtype>).  The caller has checked
 // L*P <= msda_fused_lp_limit(D, element size): the library then never declines.
 class MSDAFusedFunction : public torch::autograd::Function<MSDAFusedFunction> {
@@ -462,6 +563,12 @@ at::Tensor msda(const at::Tensor &img, const at::Tensor &shapes, const at::Tenso
     return MSDAFunction::apply(img, shapes, pts, att, padding_mode, align_corners, level_cells);
 }
 
+at::Tensor msda_ragged(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &pts, const at::Tensor &att,
+                       int64_t padding_mode, bool align_corners, int64_t level_cells, const std::vector<int64_t> &counts)
+{
+    return MSDARaggedFunction::apply(img, shapes, pts, att, padding_mode, align_corners, level_cells, counts);
+}
+
 at::Tensor msda_fused(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj, const at::Tensor &ref,
                       int64_t padding_mode, bool align_corners, int64_t level_cells)
 {
@@ -476,6 +583,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("msda", &msda, "multi-scale deformable attention (forward; differentiable)", pybind11::arg("img"),
           pybind11::arg("shapes"), pybind11::arg("sampling_points"), pybind11::arg("attention_weights"),
           pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells") = 0);
+    m.def("msda_ragged", &msda_ragged, "per-level point counts: sampling points [B,Q,H,S,2] (forward; differentiable)",
+          pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("sampling_points"),
+          pybind11::arg("attention_weights"), pybind11::arg("padding_mode"), pybind11::arg("align_corners"),
+          pybind11::arg("level_cells"), pybind11::arg("points_per_level"));
     m.def("msda_fused", &msda_fused, "module core with the softmax / sampling-point prologue fused in (differentiable)",
           pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
           pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells") = 0);

@@ -32,7 +32,7 @@ constexpr int kPlaceCellsTwoPerCu = 19456;  // LDS table cells (76 KB) that stil
 // fwd+bwd unchanged within noise — against 715 us for the one-wave-per-slice kernel of round 3 this replaces.  Lanes
 // of ONE wave instruction that hit the same cell are ranked by the LDS hardware in a fixed order.  grad_value of the
 // sorted pipeline is therefore bitwise reproducible by default wherever this pass runs.
-template <typename T, int TB> __global__ __launch_bounds__(TB) void msda_cell_place_lm_kernel(const Params p)
+template <typename T, int TB, typename PP = Params> __global__ __launch_bounds__(TB) void msda_cell_place_lm_kernel(const PP p)
 {
     using A = typename Traits<T>::acc;
     using TR = Traits<T>;
@@ -50,12 +50,14 @@ template <typename T, int TB> __global__ __launch_bounds__(TB) void msda_cell_pl
     const int qa = min(p.q_end, p.q_begin + k * qper), qb = min(p.q_end, qa + qper);
     if (qb <= qa) return;
     // thread -> (point, query lane): one pass of the workgroup covers dq queries' P samples of this level
-    const int pt = tid % p.P, tq = tid / p.P, dq = TB / p.P;
+    // (per-level counts: the level's P_l points, from its first sample on)
+    const int lP = lvl_points(p, l);
+    const int pt = tid % lP, tq = tid / lP, dq = TB / lP;
     const bool active = tq < dq;
     const size_t plane_s0 = ((size_t)b * p.Q * p.H + h) * p.LP;
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
     const T *attn = static_cast<const T *>(p.attn) + plane_s0;
-    const int HLP = p.H * p.LP, sl = l * p.P + pt;
+    const int HLP = p.H * p.LP, sl = lvl_start(p, l, l * p.P) + pt;
 
     // ---- level geometry: scalar loads (uniform addresses), as load_level_table computes it ----
     int lh = 0, lw = 0, cs = 0, ps = 0, plane_nc = 0;

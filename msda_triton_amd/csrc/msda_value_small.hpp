@@ -44,8 +44,8 @@ inline size_t small_lds_bytes(size_t cells, size_t samples, size_t acc_bytes, si
     return o + 64;
 }
 
-template <typename T, int VEC, int G, typename TV = T, typename TG = T>  // TV: storage type of grad_value, TG: of grad_out
-__global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const Params p)
+template <typename T, int VEC, int G, typename TV = T, typename TG = T, typename PP = Params>  // TV: storage type of grad_value, TG: of grad_out
+__global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP p)
 {
     using A = typename Traits<T>::acc;
     using TR = Traits<T>;
@@ -72,9 +72,11 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const Par
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
     const T *attn = static_cast<const T *>(p.attn) + plane_s0;
     const int HLP = p.H * p.LP;
-    const int dq = p.P <= kSmallBlock ? kSmallBlock / p.P : 1;
-    const bool active = p.P <= kSmallBlock && tid < dq * p.P;
-    const int pt = active ? tid % p.P : 0, q0 = active ? tid / p.P : 0;
+    // the level's points and its first sample (uniform: P and lvl * P; per-level counts: P_l and the level's start)
+    const int lP = lvl_points(p, lvl), lS = lvl_start(p, lvl, lvl * p.P);
+    const int dq = lP <= kSmallBlock ? kSmallBlock / lP : 1;
+    const bool active = lP <= kSmallBlock && tid < dq * lP;
+    const int pt = active ? tid % lP : 0, q0 = active ? tid / lP : 0;
     // This thread's samples, fetched ONCE and up front — before the level table is waited for, their addresses do not
     // need it — (both walks below reuse them): the kernel is a chain of latencies inside one workgroup, so every
     // global round trip saved counts.  Problems this kernel is chosen for have at most kPre samples per thread;
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const Par
         pre_xy[k].v[0] = pre_xy[k].v[1] = pre_a[k] = TR::from_acc((A)0);
         const int q = q0 + k * dq;
         if (pre && q < p.Q) {
-            const int sidx = q * HLP + lvl * p.P + pt;
+            const int sidx = q * HLP + lS + pt;
             pre_xy[k] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx);
             pre_a[k] = attn[sidx];
         }
@@ -146,13 +148,13 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const Par
                 if (q0 + k * dq < p.Q) one(q0 + k * dq, pre_xy[k], pre_a[k]);
         } else if (active) {
             for (int q = q0; q < p.Q; q += dq) {
-                const int sidx = q * HLP + lvl * p.P + pt;
+                const int sidx = q * HLP + lS + pt;
                 one(q, *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx), attn[sidx]);
             }
-        } else if (p.P > kSmallBlock) {
+        } else if (lP > kSmallBlock) {
             for (int q = 0; q < p.Q; ++q)
-                for (int pp = tid; pp < p.P; pp += kSmallBlock) {
-                    const int sidx = q * HLP + lvl * p.P + pp;
+                for (int pp = tid; pp < lP; pp += kSmallBlock) {
+                    const int sidx = q * HLP + lS + pp;
                     one(q, *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx), attn[sidx]);
                 }
         }
@@ -227,12 +229,12 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const Par
                 s_rec[pos[k]] = r;
             }
         };
-        if (p.P <= kSmallBlock && (p.Q + dq - 1) / dq <= kPre) {  // (uniform) the prefetched samples: one batch
+        if (lP <= kSmallBlock && (p.Q + dq - 1) / dq <= kPre) {  // (uniform) the prefetched samples: one batch
             int qs[kPre];
 #pragma unroll
             for (int k = 0; k < kPre; ++k) qs[k] = pre && q0 + k * dq < p.Q ? q0 + k * dq : -1;
             batch(wid, std::integral_constant<int, kPre>{}, qs, pre_xy, pre_a);
-        } else if (p.P <= kSmallBlock) {
+        } else if (lP <= kSmallBlock) {
             const int rounds = (p.Q + kPre * dq - 1) / (kPre * dq);
             for (int r = 0; r < rounds; ++r) {
                 int qs[kPre];
@@ -244,7 +246,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const Par
                     qs[k] = active && q < p.Q ? q : -1;
                     xys[k].v[0] = xys[k].v[1] = ats[k] = TR::from_acc((A)0);
                     if (qs[k] >= 0) {
-                        const int sidx = q * HLP + lvl * p.P + pt;
+                        const int sidx = q * HLP + lS + pt;
                         xys[k] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx);
                         ats[k] = attn[sidx];
                     }
@@ -254,14 +256,14 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const Par
         } else {
             int it = 0;
             for (int q = 0; q < p.Q; ++q)
-                for (int pp0 = 0; pp0 < p.P; pp0 += kSmallBlock, ++it) {
+                for (int pp0 = 0; pp0 < lP; pp0 += kSmallBlock, ++it) {
                     const int pp = pp0 + tid;
-                    int qs[1] = {pp < p.P ? q : -1};
+                    int qs[1] = {pp < lP ? q : -1};
                     Pack<T, 2> xys[1];
                     T ats[1];
                     xys[0].v[0] = xys[0].v[1] = ats[0] = TR::from_acc((A)0);
                     if (qs[0] >= 0) {
-                        const int sidx = q * HLP + lvl * p.P + pp;
+                        const int sidx = q * HLP + lS + pp;
                         xys[0] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx);
                         ats[0] = attn[sidx];
                     }

@@ -162,8 +162,8 @@ __device__ __forceinline__ bool sample_cell(A x, A y, int h, int w, int cstart, 
 // A thread keeps ONE (level, point) slot for its whole walk (the active threads are a multiple of L*P), so the
 // level's constants sit in registers and the loop body is the coordinate math, one LDS atomic and (K3) one store.
 // ------------------------------------------------------------------------------------------
-template <typename T, bool PLACE>
-__global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const Params p)
+template <typename T, bool PLACE, typename PP = Params>
+__global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const PP p)
 {
     using A = typename Traits<T>::acc;
     using TR = Traits<T>;
@@ -210,9 +210,13 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const Params
             while (l_lo < p.L - 1 && tab->cstart[l_lo + 1] <= c0) ++l_lo;           // last level starting at or before c0
             while (l_hi > l_lo && tab->cstart[l_hi] >= c0 + n) --l_hi;               // ... and before the chunk's end
         }
-        const int LPt = fixed ? (l_hi - l_lo + 1) * p.P : p.LP;
+        int LPt = fixed ? (l_hi - l_lo + 1) * p.P : p.LP, s_lo = l_lo * p.P;
+        if constexpr (kRagged<PP>) {  // the trip's levels own the samples [start of l_lo, start of l_hi + 1)
+            s_lo = lvl_start(p, l_lo);
+            if (fixed) LPt = lvl_start(p, l_hi + 1) - s_lo;
+        }
         const int dq = fixed ? kCellBlock / LPt : 1;
-        const int sl0 = fixed ? l_lo * p.P + tid % LPt : 0, tq = fixed ? tid / LPt : 0;
+        const int sl0 = fixed ? s_lo + tid % LPt : 0, tq = fixed ? tid / LPt : 0;
         const bool active = fixed && tq < dq;
         for (int i = tid; i < n; i += kCellBlock) {
             int v = 0;
@@ -234,7 +238,7 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const Params
             }
         };
         if (active) {
-            const int l = sl0 / p.P;
+            const int l = kRagged<PP> ? lvl_of(p, sl0, 0.0f) : sl0 / p.P;
             const int lw = tab->w[l], lh = tab->h[l], cs = tab->cstart[l], ps = tab->start[l];
             int q = qa + tq;
             int sidx = q * HLP + sl0;
@@ -297,7 +301,7 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const Params
         } else if (!fixed) {
             for (int q = qa; q < qb; ++q) {
                 for (int sl = tid; sl < p.LP; sl += kCellBlock) {
-                    const int l = sl / p.P;
+                    const int l = kRagged<PP> ? lvl_of(p, sl, 0.0f) : sl / p.P;
                     const int sidx = q * HLP + sl;
                     const Pack<T, 2> xy = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx);
                     int cell;
@@ -899,7 +903,7 @@ inline int gather_group_lanes(int64_t D, size_t elem_bytes, bool vec)
 // records_in_grads: the caller's grad_loc / grad_attn buffers (of elem_bytes elements) and — single-round problems —
 // its grad_value buffer (of value_elem_bytes elements; 0: elem_bytes) hold the records of as many planes as fit them
 // (MSDA_WS_RECORDS_IN_GRADS); ent_n0 / ent_n1 / ent_n2 say how many
-inline SortedWsLayout sorted_ws_layout(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P,
+inline SortedWsLayout sorted_ws_layout(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t LP,
                                        size_t acc_bytes, size_t elem_bytes, bool vec = true, bool records_in_grads = false,
                                        size_t value_elem_bytes = 0)
 {
@@ -912,7 +916,7 @@ inline SortedWsLayout sorted_ws_layout(int64_t B, int64_t I, int64_t H, int64_t 
     // this way (rounds of 16k queries) did not speed the gather up.
     int64_t q_round = Q;
     {
-        const int64_t per_query = (int64_t)pairs * L * P * (acc_bytes == 8 ? 32 : 16);
+        const int64_t per_query = (int64_t)pairs * LP * (acc_bytes == 8 ? 32 : 16);
         const int64_t budget = (int64_t)1 << 30;
         if (per_query > 0 && Q * per_query > budget + budget / 4) {
             const int64_t rounds = (Q * per_query + budget - 1) / budget;
@@ -925,7 +929,7 @@ inline SortedWsLayout sorted_ws_layout(int64_t B, int64_t I, int64_t H, int64_t 
     w.q_round = (int)q_round;
     w.rounds = (int)((Q + q_round - 1) / q_round);
     if (w.rounds < 1) w.rounds = 1;
-    const size_t samples = (size_t)(q_round * L * P);  // per plane and round
+    const size_t samples = (size_t)(q_round * LP);  // per plane and round
     w.nc_cap = (int)(2 * I + 2 * L);             // (w+1)(h+1) <= 2wh + 2 per level
     w.nblk_cap = (w.nc_cap + kScanCells - 1) / kScanCells;
     const int gl = gather_group_lanes(D, elem_bytes, vec);
@@ -968,7 +972,7 @@ inline SortedWsLayout sorted_ws_layout(int64_t B, int64_t I, int64_t H, int64_t 
     w.ent_n0 = w.ent_n1 = w.ent_n2 = 0;
     if (records_in_grads && samples > 0) {
         const size_t plane_bytes = samples * entry_bytes;
-        const size_t loc_bytes = (size_t)(B * Q * H * L * P) * 2 * elem_bytes, attn_bytes = loc_bytes / 2;
+        const size_t loc_bytes = (size_t)(B * Q * H * LP) * 2 * elem_bytes, attn_bytes = loc_bytes / 2;
         const size_t value_bytes = (size_t)(B * I * H * D) * (value_elem_bytes ? value_elem_bytes : elem_bytes);
         size_t n0 = loc_bytes / plane_bytes, n1 = attn_bytes / plane_bytes, n2 = w.rounds == 1 ? value_bytes / plane_bytes : 0;
         if (n0 > pairs) n0 = pairs;

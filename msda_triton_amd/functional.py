@@ -448,10 +448,18 @@ def hip_multiscale_deformable_attention(
     padding_mode: Literal["border", "zeros"],
     align_corners: bool,
     level_shapes=None,
+    points_per_level=None,
 ) -> torch.Tensor:
     """GPU path.  Same contract as the reference's ``triton_multiscale_deformable_attention``
     (frontend.py:71-105): ``ValueError`` on unsupported dtype or non-GPU inputs.  ``level_shapes`` (an addition): the
-    pyramid's (h, w) pairs as host numbers, see :func:`level_cells_of`."""
+    pyramid's (h, w) pairs as host numbers, see :func:`level_cells_of`.  ``points_per_level``: see
+    :func:`multiscale_deformable_attention`."""
+    if points_per_level is not None:
+        if img.device.type != "cuda":
+            raise ValueError(f"hip_multiscale_deformable_attention needs GPU tensors, but `img` is on {img.device}.")
+        from .ragged import ragged_multiscale_deformable_attention
+        return ragged_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,
+                                                      align_corners, points_per_level, level_shapes)
     # Fast path (the small decoder / README shapes spend more host time than device time per call): every check below
     # as one conjunction; whatever fails it — or needs the Python Function — takes the checks that carry the messages.
     dev, dt, shp, ish = img.device, sampling_points.dtype, sampling_points.shape, img.shape
@@ -797,6 +805,7 @@ def multiscale_deformable_attention(
     padding_mode: Literal["border", "zeros"],
     align_corners: bool,
     level_shapes=None,
+    points_per_level=None,
 ) -> torch.Tensor:
     """Differentiable multiscale deformable attention.
 
@@ -813,6 +822,10 @@ def multiscale_deformable_attention(
             Face's ``spatial_shapes_list``).  ``img_shapes`` lives on the device and is never read back, so without
             this the backward must assume the largest level ``num_image`` pixels can form; with it, decoder-sized
             calls over real-image pyramids take the single-launch grad_value kernel (see :func:`level_cells_of`).
+        points_per_level: optional, not in the reference — a point count per level (D-FINE / DEIMv2's
+            ``num_points_list``).  Then ``sampling_points`` is ``[batch, num_queries, num_heads, S, 2]`` and
+            ``attention_weights`` ``[batch, num_queries, num_heads, S]`` with ``S = sum(points_per_level)``, level-major
+            (samples ``[start_l, start_l + P_l)`` belong to level ``l``).  Equal counts take the uniform call on a view.
 
     Returns:
         ``[batch, num_queries, num_heads, num_channels]``.
@@ -820,6 +833,10 @@ def multiscale_deformable_attention(
     Tensors on an AMD GPU ("cuda" device type on ROCm) run the hand-written gfx950 kernels and
     never fall back; host tensors run the plain-PyTorch formulation.
     """
+    if points_per_level is not None:
+        from .ragged import ragged_multiscale_deformable_attention
+        return ragged_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,
+                                                      align_corners, points_per_level, level_shapes)
     if img.device.type == "cuda":
         return hip_multiscale_deformable_attention(
             img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners, level_shapes)

@@ -10,6 +10,11 @@ which is this operator with ``padding_mode="zeros"``, ``align_corners=False`` fo
 the (head, channel) axes — the parity demo of the reference's README (README.md:25-37).
 ``level_start_index`` and ``im2col_step`` are accepted and ignored (level starts are derived from the
 shapes in-kernel, exactly as the reference does, kernels.py:58-62).
+
+D-FINE / DEIMv2 (``transformers/models/{d_fine,deimv2}/modeling_*.py``) instead keep their core as an instance
+attribute, ``module.ms_deformable_attn_core(value, spatial_shapes_list, sampling_locations, attention_weights,
+num_points_list, method)`` with a point count per level; :func:`ms_deformable_attn_core` is that function over the
+per-level-count kernels (``method="default"`` only: zeros padding, ``align_corners=False``).
 """
 from __future__ import annotations
 
@@ -56,13 +61,59 @@ class MultiScaleDeformableAttention(nn.Module):
         return out.flatten(2)
 
 
+_SHAPES_CACHE: dict = {}  # (shapes tuple, device) -> int64 [L, 2] tensor: no host-to-device copy per call
+
+
+def _shapes_tensor(shapes_list, device) -> torch.Tensor:
+    key = (tuple((int(h), int(w)) for h, w in shapes_list), str(device))
+    t = _SHAPES_CACHE.get(key)
+    if t is None:
+        t = _SHAPES_CACHE[key] = torch.tensor(key[0], dtype=torch.int64, device=device)
+    return t
+
+
+def ms_deformable_attn_core(value: torch.Tensor, spatial_shapes_list, sampling_locations: torch.Tensor,
+                            attention_weights: torch.Tensor, num_points_list, method: str = "default") -> torch.Tensor:
+    """transformers' ``multi_scale_deformable_attention_v2`` (D-FINE / DEIMv2) for ``method="default"``: value
+    ``[B, I, H, D]``, the level shapes as host numbers, sampling locations ``[B, Q, H, S, 2]``, attention weights
+    ``[B, Q, H, S]``, ``num_points_list`` the L point counts (S their sum).  Returns ``[B, Q, H * D]``."""
+    if method != "default":
+        raise ValueError(f"ms_deformable_attn_core serves method='default' only, got {method!r}")
+    level_shapes = [(int(h), int(w)) for h, w in spatial_shapes_list]
+    shapes = _shapes_tensor(level_shapes, value.device)
+    counts = [int(p) for p in num_points_list]
+    dtype = value.dtype
+    if value.device.type == "cuda" and dtype in (torch.bfloat16, torch.float16) and \
+            sampling_locations.dtype == torch.float32 and attention_weights.dtype == torch.float32:
+        # the mixed storage, as MultiScaleDeformableAttention.forward above
+        autocast = _autocast_on()
+        with torch.autocast("cuda", enabled=False):
+            out = multiscale_deformable_attention(value, shapes, sampling_locations, attention_weights, "zeros", False,
+                                                  level_shapes=level_shapes, points_per_level=counts)
+        return (out if autocast else out.to(dtype)).flatten(2)
+    if sampling_locations.dtype != dtype:
+        sampling_locations = sampling_locations.to(dtype)
+    if attention_weights.dtype != dtype:
+        attention_weights = attention_weights.to(dtype)
+    out = multiscale_deformable_attention(value, shapes, sampling_locations, attention_weights, "zeros", False,
+                                          level_shapes=level_shapes, points_per_level=counts)
+    return out.flatten(2)
+
+
 def replace_hf_msda(model: nn.Module) -> int:
-    """Swap every HF ``MultiScaleDeformableAttention`` submodule of ``model`` for the adapter.
-    Returns the number of modules replaced."""
+    """Swap every HF ``MultiScaleDeformableAttention`` submodule of ``model`` for the adapter, and set
+    :func:`ms_deformable_attn_core` on every module that carries an ``ms_deformable_attn_core`` attribute with
+    ``decoder_method == "default"`` (D-FINE / DEIMv2; ``"discrete"`` modules are left alone).  Returns the number of
+    modules replaced or patched."""
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
             if type(child).__name__ == "MultiScaleDeformableAttention" and not isinstance(child, MultiScaleDeformableAttention):
                 setattr(parent, name, MultiScaleDeformableAttention())
                 count += 1
+    for module in model.modules():
+        if hasattr(module, "ms_deformable_attn_core") and getattr(module, "decoder_method", None) == "default" and \
+                module.ms_deformable_attn_core is not ms_deformable_attn_core:
+            module.ms_deformable_attn_core = ms_deformable_attn_core
+            count += 1
     return count
