@@ -152,7 +152,17 @@ extern "C" {
                        void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,     \
                        int64_t L, const int32_t *points_per_level, int padding_mode,               \
                        int align_corners, int64_t max_level_cells, int64_t value_row_stride,       \
-                       void *workspace, int64_t workspace_bytes, void *stream);
+                       void *workspace, int64_t workspace_bytes, void *stream);                    \
+    MSDA_API int msda_fwd_discrete_##SUF(const void *value, const int64_t *shapes, const void *loc,         \
+                       const void *attn, void *out, int64_t B, int64_t I, int64_t H, int64_t D,    \
+                       int64_t Q, int64_t L, const int32_t *points_per_level,                      \
+                       int64_t value_row_stride, void *stream);                                    \
+    MSDA_API int msda_bwd_discrete_##SUF(const void *grad_out, const void *value, const int64_t *shapes,    \
+                       const void *loc, const void *attn, void *grad_value, void *grad_attn,       \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,           \
+                       const int32_t *points_per_level, int64_t max_level_cells,                   \
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes,         \
+                       void *stream);
 
 /*
  * Per-level point counts (ABI 12, additive): msda_fwd_ragged_<dtype> / msda_bwd_ragged_<dtype> take the arguments of
@@ -166,6 +176,27 @@ extern "C" {
  * entry points applies with L * P read as S; value_row_stride, MSDA_WS_RECORDS_IN_GRADS and MSDA_WS_PASSES(n) mean what
  * they mean there, and the workspace comes from msda_bwd_ragged_workspace_bytes.  grad_value is bitwise reproducible
  * while max_l P_l <= 1024.  The fused entry points keep one P for every level.
+ *
+ * Discrete (nearest-pixel) sampling — ADDITIONS WITHIN ABI 12: no existing signature changes and MSDA_ABI_VERSION stays
+ * 12, so a caller PROBES FOR THESE BY SYMBOL (dlsym / hasattr) instead of by version; a library built before them simply
+ * lacks them.  msda_fwd_discrete_<dtype> / msda_bwd_discrete_<dtype> take the ragged layout above (`points_per_level`,
+ * loc [B, Q, H, S, 2], attn [B, Q, H, S]; the uniform layout is the same call with equal counts).  Every sample reads
+ * exactly ONE value row:
+ *
+ *   ix = clamp(trunc(x * w + 0.5), 0, w - 1)      iy = clamp(trunc(y * h + 0.5), 0, h - 1)
+ *   out[b, q, head, :] += attn * value[b, start_l + iy * w + ix, head, :]
+ *
+ * (transformers' multi_scale_deformable_attention_v2(method="discrete"); not grid_sample's "nearest").  The index is
+ * computed in fp32 from the stored coordinate (fp64 for f64) as a rounded multiply followed by a rounded add — never a
+ * fused multiply-add, so the pixel is the one the same expression picks on the host — and clamped in floating point
+ * before the conversion: out-of-range and infinite coordinates take the edge pixel, NaN some in-range pixel.  There is
+ * no padding_mode / align_corners argument (they have no meaning here) and no grad_loc (the sampling points get no
+ * gradient).  msda_bwd_discrete_<dtype> writes grad_value [B, I, H, D] (dense) and grad_attn [B, Q, H, S]; EITHER MAY BE
+ * NULL.  grad_value runs the bilinear call's cell pipelines on one-corner records (no floating-point atomics, bitwise
+ * reproducible while max_l P_l <= 1024), so their limits carry over: msda_bwd_discrete_supported says whether it exists
+ * for a shape (I < 2^22 ...), msda_bwd_discrete_workspace_bytes sizes its workspace (flags: 0 | MSDA_WS_PASSES(n);
+ * MSDA_WS_RECORDS_IN_GRADS is ignored — there is no grad_loc buffer to lend).  Errors as everywhere: a null buffer or a
+ * count below 1 is MSDA_ERR_BAD_ARG, L > MSDA_MAX_LEVELS is MSDA_ERR_TOO_MANY_LEVELS, and nothing is launched.
  */
 MSDA_DECLARE(f32)
 MSDA_DECLARE(f16)
@@ -233,6 +264,11 @@ MSDA_API int64_t msda_bwd_workspace_bytes(int64_t B, int64_t I, int64_t H, int64
 MSDA_API int64_t msda_bwd_ragged_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                                  const int32_t *points_per_level, int elem_size, int value_elem_size,
                                                  int64_t max_level_cells, int flags);
+/* ... msda_bwd_discrete_<dtype> (within ABI 12, probe by symbol; flags: 0 | MSDA_WS_PASSES(n); 0 for an unusable
+ * points_per_level and for every shape msda_bwd_discrete_supported answers 0 for) ... */
+MSDA_API int64_t msda_bwd_discrete_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                                   const int32_t *points_per_level, int elem_size, int value_elem_size,
+                                                   int64_t max_level_cells, int flags);
 /* ... and msda_bwd_fused_<dtype> (grad_value != NULL). */
 MSDA_API int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                                 int64_t P, int elem_size, int value_elem_size,
@@ -249,6 +285,9 @@ MSDA_API int msda_bwd_supported(int64_t B, int64_t I, int64_t H, int64_t D, int6
 /* ... for msda_bwd_ragged_<dtype> (ABI 12). */
 MSDA_API int msda_bwd_ragged_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                        const int32_t *points_per_level, int elem_size);
+/* ... for msda_bwd_discrete_<dtype>'s grad_value (within ABI 12, probe by symbol). */
+MSDA_API int msda_bwd_discrete_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                         const int32_t *points_per_level, int elem_size);
 
 /* Largest L*P the fused entry points accept for head dimension D and this element size (beyond it they return
  * MSDA_ERR_UNSUPPORTED and the caller composes the prologue around msda_fwd_/msda_bwd_<dtype>). */
@@ -331,9 +370,9 @@ MSDA_API int msda_profile_read(char *buf, int cap);
 MSDA_API int msda_get_option(const char *key);
 /* Measurement only (ABI 11): which variants the most recent launches took (process-wide; bench.py reads it to say how many
  * of the forward's rows came from LDS).  Keys: "fwd_variant" 0 = 256-thread kernel, 1 = LDS-served coarse levels, 2 = one
- * wave per unit;  "fwd_lds_level_bytes" LDS bytes per plane set aside for level rows (the kernel keeps the longest suffix
+ * wave per unit, 3 = the discrete-sampling forward (msda_fwd_discrete_<dtype>);  "fwd_lds_level_bytes" LDS bytes per plane set aside for level rows (the kernel keeps the longest suffix
  * of the level list that fits);  "fwd_lds_planes";  "fwd_workgroups";  "sample_variant", "sample_lds_level_bytes" the same
- * for the sample-gradient kernel;  "value_path" 1 = single-launch kernel, 2 = sorted pipeline;  "value_passes" its passes
+ * for the sample-gradient kernel (2 = the discrete attention-weight gradient);  "value_path" 1 = single-launch kernel, 2 = sorted pipeline;  "value_passes" its passes
  * over the batch.  Unknown key: MSDA_ERR_BAD_ARG. */
 MSDA_API int msda_last_launch_info(const char *key);
 

@@ -36,6 +36,8 @@ EXPORTED_SYMBOLS = tuple(
     + [f"msda_{d}_{s}" for d in ("fwd_fused", "bwd_fused") for s in FUSED_STORAGE_SUFFIXES]
     + [f"msda_{d}_ragged_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES]
     + ["msda_bwd_ragged_workspace_bytes", "msda_bwd_ragged_supported"]
+    + [f"msda_{d}_discrete_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES]
+    + ["msda_bwd_discrete_workspace_bytes", "msda_bwd_discrete_supported"]
     + ["msda_abi_version", "msda_last_error", "msda_set_option", "msda_get_option", "msda_bwd_workspace_bytes",
        "msda_bwd_fused_workspace_bytes", "msda_bwd_supported", "msda_fused_lp_limit", "msda_profile_read",
        "msda_last_launch_info"]
@@ -118,6 +120,22 @@ def load():
         lib.msda_bwd_ragged_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
         lib.msda_bwd_ragged_supported.restype = ci
         lib.msda_bwd_ragged_supported.argtypes = [i64] * 6 + [vp, ci]
+        # discrete sampling: additions within ABI 12, so a library built before them lacks the symbols (has_discrete)
+        if hasattr(lib, "msda_bwd_discrete_supported"):
+            for suf in DTYPE_SUFFIXES:
+                fd = getattr(lib, f"msda_fwd_discrete_{suf}")
+                fd.restype = ci
+                # (value, shapes, loc, attn, out, B, I, H, D, Q, L, points_per_level, value_row_stride, stream)
+                fd.argtypes = [vp] * 5 + [i64] * 6 + [vp, i64, vp]
+                gd = getattr(lib, f"msda_bwd_discrete_{suf}")
+                gd.restype = ci
+                # (grad_out, value, shapes, loc, attn, grad_value, grad_attn, B ... L, points_per_level, max_level_cells,
+                #  value_row_stride, workspace, workspace_bytes, stream)
+                gd.argtypes = [vp] * 7 + [i64] * 6 + [vp, i64, i64, vp, i64, vp]
+            lib.msda_bwd_discrete_workspace_bytes.restype = i64
+            lib.msda_bwd_discrete_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
+            lib.msda_bwd_discrete_supported.restype = ci
+            lib.msda_bwd_discrete_supported.argtypes = [i64] * 6 + [vp, ci]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -135,6 +153,16 @@ def load():
             raise MSDALibraryError(f"{LIB_NAME} has ABI version {got}, this package expects {ABI_VERSION}; rebuild it")
         _lib = lib
     return _lib
+
+
+def load_discrete():
+    """The handle, for a discrete-sampling call: raises when the loaded library predates those entry points (they are
+    additions within ABI 12, found by symbol)."""
+    lib = load()
+    if not hasattr(lib, "msda_bwd_discrete_supported"):
+        raise MSDALibraryError(f"{LIB_PATH} has no discrete-sampling entry points (msda_fwd_discrete_<dtype> ...): it "
+                               "was built from older sources; rebuild the library")
+    return lib
 
 
 def check(rc: int, what: str) -> None:

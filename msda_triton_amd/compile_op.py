@@ -255,3 +255,68 @@ def compiled_ragged_multiscale_deformable_attention(img, img_shapes, sampling_po
                                        int(level_cells))
     return msda_ragged_forward(img, img_shapes, sampling_points, attention_weights, padding_mode == "zeros",
                                bool(align_corners), ppl, int(level_cells))
+
+
+# ---------------------------------------------------------------------------------------------
+# discrete (nearest-pixel) sampling (msda_fwd_discrete_ / msda_bwd_discrete_<dtype>): the ragged layout, no padding mode,
+# no gradient for the sampling points
+# ---------------------------------------------------------------------------------------------
+@torch.library.custom_op("msda_amd::discrete_forward", mutates_args=(), device_types="cuda")
+def msda_discrete_forward(img: torch.Tensor, img_shapes: torch.Tensor, sampling_points: torch.Tensor,
+                          attention_weights: torch.Tensor, points_per_level: list[int],
+                          level_cells: int = 0) -> torch.Tensor:
+    from .discrete import discrete_hip_fwd
+    return discrete_hip_fwd(img, img_shapes, sampling_points, attention_weights, tuple(points_per_level))
+
+
+@msda_discrete_forward.register_fake
+def _(img, img_shapes, sampling_points, attention_weights, points_per_level, level_cells=0):
+    B, _, H, D = img.shape
+    return sampling_points.new_empty((B, sampling_points.shape[1], H, D))
+
+
+@torch.library.custom_op("msda_amd::discrete_backward", mutates_args=(), device_types="cuda")
+def msda_discrete_backward(out_grad: torch.Tensor, img: torch.Tensor, img_shapes: torch.Tensor,
+                           sampling_points: torch.Tensor, attention_weights: torch.Tensor, points_per_level: list[int],
+                           need_value: bool, need_attn: bool, level_cells: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    from .discrete import discrete_hip_bwd
+    g_img, g_att = discrete_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights,
+                                    tuple(points_per_level), (need_value, need_attn), level_cells)
+    return (g_img if g_img is not None else img.new_empty(0), g_att if g_att is not None else img.new_empty(0))
+
+
+@msda_discrete_backward.register_fake
+def _(out_grad, img, img_shapes, sampling_points, attention_weights, points_per_level, need_value, need_attn, level_cells=0):
+    return (torch.empty_like(img, memory_format=torch.contiguous_format) if need_value else img.new_empty(0),
+            torch.empty_like(attention_weights, memory_format=torch.contiguous_format) if need_attn else img.new_empty(0))
+
+
+def _discrete_setup_context(ctx, inputs, output):
+    img, img_shapes, sampling_points, attention_weights, points_per_level, level_cells = inputs
+    ctx.save_for_backward(img, img_shapes, sampling_points, attention_weights)
+    ctx.ppl, ctx.level_cells = points_per_level, level_cells
+
+
+def _discrete_backward(ctx, out_grad):
+    img, img_shapes, sampling_points, attention_weights = ctx.saved_tensors
+    need_value, need_attn = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+    g_img, g_att = msda_discrete_backward(out_grad.contiguous(), img, img_shapes, sampling_points, attention_weights,
+                                          ctx.ppl, need_value, need_attn, ctx.level_cells)
+    return (g_img if need_value else None, None, None, g_att if need_attn else None, None, None)
+
+
+msda_discrete_forward.register_autograd(_discrete_backward, setup_context=_discrete_setup_context)
+
+
+def compiled_discrete_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights,
+                                                      points_per_level, level_cells: int = 0):
+    """``discrete.discrete_multiscale_deformable_attention`` through the registered custom ops (traceable); fp32 under
+    autocast unless the caller passes the mixed storage (16-bit `img` next to fp32 sampling inputs)."""
+    ppl = [int(p) for p in points_per_level]
+    if torch.is_autocast_enabled("cuda"):
+        with torch.autocast("cuda", enabled=False):
+            keep = img.dtype in (torch.bfloat16, torch.float16) and sampling_points.dtype == torch.float32 and \
+                attention_weights.dtype == torch.float32
+            return msda_discrete_forward(img if keep else img.float(), img_shapes, sampling_points.float(),
+                                         attention_weights.float(), ppl, int(level_cells))
+    return msda_discrete_forward(img, img_shapes, sampling_points, attention_weights, ppl, int(level_cells))

@@ -86,3 +86,20 @@ extern "C" int msda_bwd_ragged_supported(int64_t B, int64_t I, int64_t H, int64_
         return 0;
     return msda_bwd_supported_impl(B, I, H, D, Q, L, pmax, elem_size, S);
 }
+
+// discrete sampling (include/msda_hip.h): the same cell pipelines on one-corner records, which always stay in the workspace
+extern "C" int64_t msda_bwd_discrete_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                                     const int32_t *points_per_level, int elem_size, int value_elem_size,
+                                                     int64_t max_level_cells, int flags)
+{
+    // (0 where msda_bwd_discrete_supported says no: there is no grad_value call to size a workspace for)
+    if (elem_size <= 0 || !msda_bwd_ragged_supported(B, I, H, D, Q, L, points_per_level, elem_size)) return 0;
+    return msda_bwd_ragged_workspace_bytes(B, I, H, D, Q, L, points_per_level, elem_size, value_elem_size, max_level_cells,
+                                           flags & ~MSDA_WS_RECORDS_IN_GRADS);
+}
+
+extern "C" int msda_bwd_discrete_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                           const int32_t *points_per_level, int elem_size)
+{
+    return msda_bwd_ragged_supported(B, I, H, D, Q, L, points_per_level, elem_size);
+}

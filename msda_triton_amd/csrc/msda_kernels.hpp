@@ -95,7 +95,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char msda_smem[];
 struct RaggedParams : Params {
     int pst[kMaxLevels + 1];  // first sample of every level, pst[L] = S
 };
-template <typename PP> constexpr bool kRagged = std::is_same<PP, RaggedParams>::value;
+template <typename PP> constexpr bool kRagged = std::is_base_of<RaggedParams, PP>::value;  // (also the discrete kernarg, msda_discrete.hpp)
 
 // The level of sample sl.  Uniform: one float division.  Ragged: a scan over the level starts, which sit in the kernel's
 // arguments — scalar loads at constant offsets (the unrolled loop keeps every index a constant: no indexed copy of the
@@ -130,6 +130,28 @@ __device__ __forceinline__ int lvl_start(const RaggedParams &p, int l, int) { re
 // Points of level l (l uniform).
 __device__ __forceinline__ int lvl_points(const Params &p, int) { return p.P; }
 __device__ __forceinline__ int lvl_points(const RaggedParams &p, int l) { return lvl_start(p, l + 1) - lvl_start(p, l); }
+
+// ---- discrete (nearest-pixel) sampling: the kernarg type and the index rule, shared by msda_discrete.hpp's kernels and the
+// grad_value cell passes ----
+// the kernarg of every discrete instantiation: the ragged one (level starts behind Params) under a type of its own, so
+// that the cell passes of the grad_value pipelines pick the discrete cell rule (cell_of, msda_value_sorted.hpp); the kernels of their own are in msda_discrete.hpp and the
+// bilinear instantiations — Params, RaggedParams — keep their code
+struct DiscreteParams : RaggedParams {};
+
+// The pixel of coordinate x on an axis of n pixels.  A ROUNDED MULTIPLY FOLLOWED BY A ROUNDED ADD: the host computes
+// x * n + 0.5 that way, and a fused multiply-add rounds once — for x * n within half an ulp of k + 0.5 it lands on the
+// other side of the integer and picks the neighbouring pixel.  The translation units are built with -ffp-contract=fast,
+// under which neither a pragma nor __fmul_rn keeps the two apart, so the product passes through an empty asm statement:
+// the compiler cannot see through it and there is nothing left to fuse.  Clamped in floating point before the
+// conversion (as make_taps): far-out-of-range, infinite and NaN coordinates cannot overflow the integer (NaN: pixel 0).
+// trunc and the clamp commute (integer bounds, trunc monotone), and the conversion truncates.
+template <typename A> __device__ __forceinline__ int discrete_pixel(A x, int n)
+{
+    A t = x * (A)n;
+    asm("" : "+v"(t));
+    t = t + (A)0.5;
+    return (int)fmin_t(fmax_t(t, (A)0), (A)(n - 1));
+}
 
 template <typename A> struct alignas(16) Rec4 {
     A v[4];

@@ -9,6 +9,7 @@
 #include "msda_value_sorted.hpp"
 #include "msda_value_place.hpp"
 #include "msda_value_small.hpp"
+#include "msda_discrete.hpp"
 
 namespace msda {
 
@@ -611,8 +612,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     // (the count pass keeps its per-block totals behind the cell table)
     const size_t cell_lds = sizeof(LevelTab) + ((size_t)p.cell_cap + (size_t)p.nblk_cap) * sizeof(int);
     static std::atomic<uint64_t> big_lds_count{0}, big_lds_place{0};
-    allow_big_lds(msda_cell_pass_kernel<T, false>, big_lds_count);
-    allow_big_lds(msda_cell_pass_kernel<T, true>, big_lds_place);
+    allow_big_lds(msda_cell_pass_kernel<T, false, PP>, big_lds_count);  // (the instantiation that is launched)
+    allow_big_lds(msda_cell_pass_kernel<T, true, PP>, big_lds_place);
     const int64_t scan_blocks = (int64_t)p.nblk_cap * npairs;
     if (scan_blocks >= ((int64_t)1 << 31)) {
         set_error("grid too large");
@@ -979,6 +980,11 @@ inline bool records_fit_grads(const Dims &d, int64_t per, size_t elem)
     return per >= d.B || ((size_t)(d.Q * d.H * samples(d)) * elem) % 16 == 0;
 }
 
+// the size query that belongs to the entry point family of this kernarg type (for the error text below)
+inline const char *ws_query_name(const Params &) { return "msda_bwd_workspace_bytes"; }
+inline const char *ws_query_name(const RaggedParams &) { return "msda_bwd_ragged_workspace_bytes"; }
+inline const char *ws_query_name(const DiscreteParams &) { return "msda_bwd_discrete_workspace_bytes"; }
+
 template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_bytes, hipStream_t stream)
 {
@@ -1027,8 +1033,8 @@ inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_by
         const size_t v0 = sorted_ws_layout(B, I, H, D, Q, L, samples(d), sizeof(A), sizeof(T), false).total;
         const size_t m1 = sorted_ws_layout(1, I, H, D, Q, L, samples(d), sizeof(A), sizeof(T), true).total;
         const size_t m0 = sorted_ws_layout(1, I, H, D, Q, L, samples(d), sizeof(A), sizeof(T), false).total;
-        set_error("grad_value needs a 256-byte aligned workspace of msda_bwd_workspace_bytes(...) = %zu bytes (at least %zu: one "
-                  "batch element per pass); got %lld", v1 > v0 ? v1 : v0, m1 > m0 ? m1 : m0, (long long)(workspace ? workspace_bytes : 0));
+        set_error("grad_value needs a 256-byte aligned workspace of %s(...) = %zu bytes (at least %zu: one "
+                  "batch element per pass); got %lld", ws_query_name(p), v1 > v0 ? v1 : v0, m1 > m0 ? m1 : m0, (long long)(workspace ? workspace_bytes : 0));
         return MSDA_ERR_BAD_ARG;
     }
     if (rc > 0) set_error("backward (grad_value) launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -1147,6 +1153,147 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
             rc = jrc;
         }
     }
+    return rc;
+}
+
+// ---- discrete (nearest-pixel) sampling: msda_{fwd,bwd}_discrete_<dtype>, kernels in msda_discrete.hpp ----
+// MODE 0: the forward, 1: the attention-weight gradient.  G lanes per unit from D as everywhere (pick_group); the
+// workgroups are cut per (b, head) plane, kBlock / G units each.
+template <typename T, int VEC, int G, int MODE, typename TV> inline int launch_discrete(DiscreteParams &p, hipStream_t stream)
+{
+    constexpr int NU = kBlock / G;
+    p.nqc = (p.Q + NU - 1) / NU;
+    dim3 grid;
+    if (!plane_grid(p, p.B * p.H, p.nqc, grid)) {
+        set_error("grid too large");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    if (MODE == 0) {
+        note_launch(0, 3);
+        note_launch(1, 0);
+        note_launch(2, 1);
+        note_launch(3, (int)(grid.x * grid.y * grid.z));
+        const ProfileScope prof("msda_fwd_discrete_kernel", stream);
+        hipLaunchKernelGGL((msda_fwd_discrete_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
+    } else {
+        note_launch(4, 2);
+        note_launch(5, 0);
+        const ProfileScope prof("msda_bwd_discrete_attn_kernel", stream);
+        hipLaunchKernelGGL((msda_bwd_discrete_attn_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
+    }
+    return (int)hipGetLastError();
+}
+template <typename T, int VEC, int MODE, typename TV> inline int dispatch_discrete_group(DiscreteParams &p, hipStream_t stream)
+{
+    switch (pick_group((p.D + VEC - 1) / VEC)) {
+    case 4: return launch_discrete<T, VEC, 4, MODE, TV>(p, stream);
+    case 8: return launch_discrete<T, VEC, 8, MODE, TV>(p, stream);
+    case 16: return launch_discrete<T, VEC, 16, MODE, TV>(p, stream);
+    case 32: return launch_discrete<T, VEC, 32, MODE, TV>(p, stream);
+    default: return launch_discrete<T, VEC, 64, MODE, TV>(p, stream);
+    }
+}
+template <typename T, int MODE, typename TV> inline int dispatch_discrete(DiscreteParams &p, bool vec_ok, hipStream_t stream)
+{
+    constexpr int VECF = 16 / sizeof(T);
+    if (vec_ok && (p.D % VECF) == 0) return dispatch_discrete_group<T, VECF, MODE, TV>(p, stream);
+    return dispatch_discrete_group<T, 1, MODE, TV>(p, stream);
+}
+
+// `ppl`: the L per-level point counts (host), each >= 1; S their sum
+template <typename T, typename TV = T>
+int run_fwd_discrete(const void *value, const int64_t *shapes, const void *loc, const void *attn, void *out, int64_t B,
+                     int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, const int32_t *ppl, int64_t value_row_stride,
+                     void *stream_)
+{
+    int64_t pmax, S;
+    int rc = ragged_counts(ppl, L, pmax, S);
+    if (rc) return rc;
+    Dims d{B, I, H, D, Q, L, pmax};
+    d.S = S;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t out_bytes = (size_t)(B * Q * H * D) * sizeof(T);
+    if (out_bytes == 0) return 0;  // nothing to produce
+    const void *ptrs[] = {out};
+    rc = check_common<T>(d, MSDA_PADDING_BORDER, ptrs, 1);
+    if (rc) return rc;
+    if (samples(d) == 0 || I == 0) return (int)hipMemsetAsync(out, 0, out_bytes, stream);  // empty sum
+    const void *ptrs2[] = {value, shapes, loc, attn};
+    rc = check_common<T>(d, MSDA_PADDING_BORDER, ptrs2, 4);
+    if (rc) return rc;
+    if (!aligned_to(value, sizeof(TV)) || !aligned_to(out, sizeof(T)) || !aligned_to(loc, 2 * sizeof(T)) ||
+        !aligned_to(attn, sizeof(T)) || !aligned_to(shapes, 8)) {
+        set_error("misaligned buffer");
+        return MSDA_ERR_MISALIGNED;
+    }
+    DiscreteParams p{};
+    p.value = value;
+    p.shapes = shapes;
+    p.loc = loc;
+    p.attn = attn;
+    p.out = out;
+    fill_params(p, d, MSDA_PADDING_BORDER, 0);
+    fill_level_starts(p, ppl, L);
+    p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
+    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
+    const bool vec_ok = aligned_to(value, 16) && aligned_to(out, 16) && p.v_row % 16 == 0;
+    rc = dispatch_discrete<T, 0, TV>(p, vec_ok, stream);
+    if (rc > 0) set_error("discrete forward launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return rc;
+}
+
+// grad_value and / or grad_attn (either may be null); the sampling points have no gradient in this mode
+template <typename T, typename TV = T>
+int run_bwd_discrete(const void *grad_out, const void *value, const int64_t *shapes, const void *loc, const void *attn,
+                     void *grad_value, void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                     const int32_t *ppl, int64_t max_level_cells, int64_t value_row_stride, void *workspace,
+                     int64_t workspace_bytes, void *stream_)
+{
+    int64_t pmax, S;
+    int rc = ragged_counts(ppl, L, pmax, S);
+    if (rc) return rc;
+    Dims d{B, I, H, D, Q, L, pmax, max_level_cells > 0 ? max_level_cells : 0};
+    d.S = S;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    rc = check_common<T>(d, MSDA_PADDING_BORDER, nullptr, 0);
+    if (rc) return rc;
+    const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
+    const size_t ns = (size_t)(B * Q * H * samples(d));
+    if (B * Q * H * D == 0 || samples(d) == 0 || I == 0) {  // no sample touches anything: all gradients are zero
+        hipError_t e = hipSuccess;
+        if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
+        if (e == hipSuccess && ns && grad_attn) e = hipMemsetAsync(grad_attn, 0, ns * sizeof(T), stream);
+        return (int)e;
+    }
+    const void *ptrs[] = {grad_out, value, shapes, loc, attn};
+    rc = check_common<T>(d, MSDA_PADDING_BORDER, ptrs, 5);
+    if (rc) return rc;
+    if (!aligned_to(value, sizeof(TV)) || !aligned_to(grad_out, sizeof(T)) || !aligned_to(grad_value, sizeof(TV)) ||
+        !aligned_to(loc, 2 * sizeof(T)) || !aligned_to(attn, sizeof(T)) || !aligned_to(grad_attn, sizeof(T)) ||
+        !aligned_to(shapes, 8)) {
+        set_error("misaligned buffer");
+        return MSDA_ERR_MISALIGNED;
+    }
+    DiscreteParams p{};
+    p.value = value;
+    p.shapes = shapes;
+    p.loc = loc;
+    p.attn = attn;
+    p.grad_out = grad_out;
+    p.grad_value = grad_value;
+    p.grad_attn = grad_attn;
+    fill_params(p, d, MSDA_PADDING_BORDER, 0);
+    fill_level_starts(p, ppl, L);
+    p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
+    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
+    if (grad_attn != nullptr) {
+        const bool vec_ok = aligned_to(value, 16) && aligned_to(grad_out, 16) && p.v_row % 16 == 0;
+        rc = dispatch_discrete<T, 1, TV>(p, vec_ok, stream);
+        if (rc > 0) set_error("discrete backward (grad_attn) launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (rc) return rc;
+    }
+    // the records stay in the workspace (there is no grad_loc buffer to lend: msda_bwd_discrete_workspace_bytes sizes for that)
+    if (grad_value != nullptr) rc = run_value<T, TV, T, DiscreteParams>(p, d, workspace, workspace_bytes, stream);
     return rc;
 }
 
@@ -1308,6 +1455,25 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                                         grad_attn, B, I, H, D, Q, L, pmax, padding_mode,         \
                                                         align_corners, max_level_cells, value_row_stride,        \
                                                         workspace, workspace_bytes, stream, points_per_level);   \
+    }                                                                                                            \
+    extern "C" int msda_fwd_discrete_##SUF(const void *value, const int64_t *shapes, const void *loc,           \
+                                           const void *attn, void *out, int64_t B, int64_t I, int64_t H,         \
+                                           int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level,     \
+                                           int64_t value_row_stride, void *stream)                               \
+    {                                                                                                            \
+        return msda::run_fwd_discrete<T, TV>(value, shapes, loc, attn, out, B, I, H, D, Q, L, points_per_level,  \
+                                             value_row_stride, stream);                                          \
+    }                                                                                                            \
+    extern "C" int msda_bwd_discrete_##SUF(const void *grad_out, const void *value, const int64_t *shapes,      \
+                                           const void *loc, const void *attn, void *grad_value, void *grad_attn, \
+                                           int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,     \
+                                           const int32_t *points_per_level, int64_t max_level_cells,             \
+                                           int64_t value_row_stride, void *workspace, int64_t workspace_bytes,   \
+                                           void *stream)                                                         \
+    {                                                                                                            \
+        return msda::run_bwd_discrete<T, TV>(grad_out, value, shapes, loc, attn, grad_value, grad_attn, B, I, H, \
+                                             D, Q, L, points_per_level, max_level_cells, value_row_stride,       \
+                                             workspace, workspace_bytes, stream);                                \
     }
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to

@@ -284,6 +284,92 @@ public:
     }
 };
 
+// Discrete (nearest-pixel) sampling (msda_fwd_discrete_ / msda_bwd_discrete_<dtype>, additions within ABI 12): the ragged
+// layout, one pixel per sample, no padding mode, no gradient for the sampling points.  A node of its own for the reason
+// MSDARaggedFunction has one: decoder-sized calls spend more host time than device time.
+using FwdDiscreteFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
+                              int64_t, int64_t, int64_t, const int32_t *, int64_t, void *);
+using BwdDiscreteFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *, int64_t,
+                              int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int64_t, int64_t, void *, int64_t,
+                              void *);
+std::pair<FwdDiscreteFn, BwdDiscreteFn> discrete_fns_for(at::ScalarType t, at::ScalarType c)
+{
+    if (t != c) {
+        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
+                          "unsupported dtype combination: value ", t, " with ", c);
+        if (t == at::kBFloat16) return {msda_fwd_discrete_f32_vbf16, msda_bwd_discrete_f32_vbf16};
+        return {msda_fwd_discrete_f32_vf16, msda_bwd_discrete_f32_vf16};
+    }
+    switch (t) {
+    case at::kFloat: return {msda_fwd_discrete_f32, msda_bwd_discrete_f32};
+    case at::kHalf: return {msda_fwd_discrete_f16, msda_bwd_discrete_f16};
+    case at::kBFloat16: return {msda_fwd_discrete_bf16, msda_bwd_discrete_bf16};
+    case at::kDouble: return {msda_fwd_discrete_f64, msda_bwd_discrete_f64};
+    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
+    }
+}
+
+class MSDADiscreteFunction : public torch::autograd::Function<MSDADiscreteFunction> {
+public:
+    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
+                              const at::Tensor &pts_, const at::Tensor &att_, int64_t level_cells,
+                              const std::vector<int64_t> &counts)
+    {
+        const auto [img, vrow] = value_rows(img_);
+        const at::Tensor pts = pts_.contiguous(), att = att_.contiguous();
+        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        at::Tensor out = at::empty({B, Q, H, D}, pts.options());
+        const c10::DeviceGuard guard(img.device());
+        check_rc(discrete_fns_for(img.scalar_type(), pts.scalar_type())
+                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(), out.data_ptr(), B,
+                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), vrow, current_stream(img)),
+                 "msda_fwd_discrete");
+        ctx->save_for_backward({img, shapes, pts, att});
+        ctx->saved_data["level_cells"] = level_cells;
+        ctx->saved_data["vrow"] = vrow;
+        ctx->saved_data["counts"] = counts;
+        return out;
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
+                                                   torch::autograd::variable_list grads)
+    {
+        const auto saved = ctx->get_saved_variables();
+        const at::Tensor &img = saved[0], &shapes = saved[1], &pts = saved[2], &att = saved[3];
+        const int64_t vrow = ctx->saved_data["vrow"].toInt();
+        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
+        const auto counts = ctx->saved_data["counts"].toIntVector();
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        const int64_t L = (int64_t)ppl.size();
+        at::Tensor gout = grads[0].contiguous();
+        if (gout.scalar_type() != pts.scalar_type()) gout = gout.to(pts.scalar_type());
+        const bool want_value = ctx->needs_input_grad(0), want_attn = ctx->needs_input_grad(3);
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
+        at::Tensor g_img, g_att, ws;
+        int64_t ws_bytes = 0;
+        if (want_attn) g_att = at::empty_like(att);
+        if (want_value) {
+            g_img = at::empty(img.sizes(), img.options());
+            ws_bytes = msda_bwd_discrete_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)pts.element_size(),
+                                                         (int)img.element_size(), level_cells, 0);
+            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
+        }
+        if (want_value || want_attn) {
+            const c10::DeviceGuard guard(img.device());
+            check_rc(discrete_fns_for(img.scalar_type(), pts.scalar_type())
+                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(),
+                                 want_value ? g_img.data_ptr() : nullptr, want_attn ? g_att.data_ptr() : nullptr, B, I, H, D,
+                                 Q, L, ppl.data(), level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr, ws_bytes,
+                                 current_stream(img)),
+                     "msda_bwd_discrete");
+        }
+        // (the sampling points: no gradient in this mode)
+        return once_differentiable(grads, {g_img, at::Tensor(), at::Tensor(), g_att, at::Tensor(), at::Tensor()});
+    }
+};
+
 // The module core with its prologue fused in (msda_fwd_fused_ / msda_bwd_fused_<dtype>).  The caller has checked
 // L*P <= msda_fused_lp_limit(D, element size): the library then never declines.
 class MSDAFusedFunction : public torch::autograd::Function<MSDAFusedFunction> {
@@ -569,6 +655,12 @@ at::Tensor msda_ragged(const at::Tensor &img, const at::Tensor &shapes, const at
     return MSDARaggedFunction::apply(img, shapes, pts, att, padding_mode, align_corners, level_cells, counts);
 }
 
+at::Tensor msda_discrete(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &pts, const at::Tensor &att,
+                         int64_t level_cells, const std::vector<int64_t> &counts)
+{
+    return MSDADiscreteFunction::apply(img, shapes, pts, att, level_cells, counts);
+}
+
 at::Tensor msda_fused(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj, const at::Tensor &ref,
                       int64_t padding_mode, bool align_corners, int64_t level_cells)
 {
@@ -587,6 +679,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("sampling_points"),
           pybind11::arg("attention_weights"), pybind11::arg("padding_mode"), pybind11::arg("align_corners"),
           pybind11::arg("level_cells"), pybind11::arg("points_per_level"));
+    m.def("msda_discrete", &msda_discrete,
+          "discrete (nearest-pixel) sampling over the per-level-count layout (forward; differentiable in img and weights)",
+          pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("sampling_points"),
+          pybind11::arg("attention_weights"), pybind11::arg("level_cells"), pybind11::arg("points_per_level"));
     m.def("msda_fused", &msda_fused, "module core with the softmax / sampling-point prologue fused in (differentiable)",
           pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
           pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells") = 0);

@@ -128,8 +128,7 @@ template <typename T, int TB, typename PP = Params> __global__ __launch_bounds__
                     uint32_t cellw;
                     A dx, dy;
                     rel[j] = 0xFFFFFFFFu;
-                    if (active && q < qb && sample_cell<A>(TR::to_acc(xy[j].v[0]), TR::to_acc(xy[j].v[1]), lh, lw, 0, ps, l, p.zeros,
-                                                           p.align, cell, cellw, dx, dy)) {
+                    if (active && q < qb && cell_of<A>(p, TR::to_acc(xy[j].v[0]), TR::to_acc(xy[j].v[1]), lh, lw, 0, ps, l, cell, cellw, dx, dy)) {
                         const unsigned rr = (unsigned)(cell - c0);
                         if (rr < (unsigned)n) rel[j] = rr;
                     }
@@ -149,7 +148,7 @@ template <typename T, int TB, typename PP = Params> __global__ __launch_bounds__
                     int cell;
                     uint32_t cellw;
                     A dx, dy;
-                    sample_cell<A>(TR::to_acc(xy[j].v[0]), TR::to_acc(xy[j].v[1]), lh, lw, 0, ps, l, p.zeros, p.align, cell, cellw, dx, dy);
+                    cell_of<A>(p, TR::to_acc(xy[j].v[0]), TR::to_acc(xy[j].v[1]), lh, lw, 0, ps, l, cell, cellw, dx, dy);
                     entries[pos[j]] = Entry<A>::pack((uint32_t)q, cellw, TR::to_acc(at[j]), dx, dy);
                 }
             }

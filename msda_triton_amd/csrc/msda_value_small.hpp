@@ -138,7 +138,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
             int cell;
             uint32_t cellw;
             A dx, dy;
-            if (sample_cell<A>(TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), lh, lw, 0, 0, 0, p.zeros, p.align, cell, cellw, dx, dy) &&
+            if (cell_of<A>(p, TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), lh, lw, 0, 0, 0, cell, cellw, dx, dy) &&
                 cell < ncl)
                 visit(q, TR::to_acc(at), cell, dx, dy);
         };
@@ -208,8 +208,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
 #pragma unroll
             for (int k = 0; k < N; ++k) {
                 uint32_t cellw;
-                ok[k] = qs[k] >= 0 && sample_cell<A>(TR::to_acc(xys[k].v[0]), TR::to_acc(xys[k].v[1]), lh, lw, 0, 0, 0, p.zeros,
-                                                     p.align, cell[k], cellw, dx[k], dy[k]) && cell[k] < ncl;
+                ok[k] = qs[k] >= 0 && cell_of<A>(p, TR::to_acc(xys[k].v[0]), TR::to_acc(xys[k].v[1]), lh, lw, 0, 0, 0, cell[k], cellw, dx[k], dy[k]) && cell[k] < ncl;
             }
             while (__hip_atomic_load(&s_turn, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != my) __builtin_amdgcn_s_sleep(1);
             int pos[N];

@@ -157,6 +157,32 @@ __device__ __forceinline__ bool sample_cell(A x, A y, int h, int w, int cstart, 
     return true;
 }
 
+// The cell passes' view of it: which rule puts a sample into a cell follows from the kernarg type.  Params / RaggedParams:
+// the bilinear cell above, under the call's padding mode and align_corners.
+template <typename A>
+__device__ __forceinline__ bool cell_of(const Params &p, A x, A y, int h, int w, int cstart, int start, int level, int &cell,
+                                        uint32_t &cellw, A &dx, A &dy)
+{
+    return sample_cell<A>(x, y, h, w, cstart, start, level, p.zeros, p.align, cell, cellw, dx, dy);
+}
+// DiscreteParams (msda_kernels.hpp): the cell whose corner 00 is the sample's ONE pixel (ix, iy), with dx = dy = 0 — the
+// record's whole weight goes to that corner (the cells x0 = w - 1 / y0 = h - 1 exist: "border" padding puts clamped samples
+// there in just this form).  The validity bits are the cell's geometry, as above, so the gather and finish kernels see
+// nothing new: the other corners receive rows of zeros.  Every sample has a pixel (the index is clamped).
+template <typename A>
+__device__ __forceinline__ bool cell_of(const DiscreteParams &, A x, A y, int h, int w, int cstart, int start, int level,
+                                        int &cell, uint32_t &cellw, A &dx, A &dy)
+{
+    const int ix = discrete_pixel<A>(x, w), iy = discrete_pixel<A>(y, h);
+    dx = dy = (A)0;
+    cell = cstart + (int)mul24((uint32_t)(iy + 1), (uint32_t)(w + 1)) + (ix + 1);
+    const bool xv1 = ix + 1 < w, yv1 = iy + 1 < h;
+    const uint32_t valid = 1u | ((uint32_t)xv1 << 1) | ((uint32_t)yv1 << 2) | ((uint32_t)(xv1 && yv1) << 3);
+    const uint32_t pixq = (uint32_t)((int)kPixBias + start + (int)mul24((uint32_t)(iy + 1), (uint32_t)w) - w + ix);
+    cellw = (pixq & kPixMask) | ((uint32_t)level << kLevelShift) | (valid << 28);
+    return true;
+}
+
 // ------------------------------------------------------------------------------------------
 // K1 / K3: one pass over the samples of a (plane, query slice).  PLACE=false counts, true places.
 // A thread keeps ONE (level, point) slot for its whole walk (the active threads are a multiple of L*P), so the
@@ -262,8 +288,7 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const PP p)
                         int cell;
                         uint32_t cellw;
                         A dx, dy;
-                        if (qk < qb && sample_cell<A>(TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), lh, lw, cs, ps, l, p.zeros,
-                                                      p.align, cell, cellw, dx, dy))
+                        if (qk < qb && cell_of<A>(p, TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), lh, lw, cs, ps, l, cell, cellw, dx, dy))
                             visit(qk, cell, cellw, dx, dy, (A)0);
                     }
                     q += RING * dq;
@@ -290,7 +315,7 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const PP p)
                 int cell;
                 uint32_t cellw;
                 A dx, dy;
-                if (sample_cell<A>(TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), lh, lw, cs, ps, l, p.zeros, p.align, cell, cellw,
+                if (cell_of<A>(p, TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), lh, lw, cs, ps, l, cell, cellw,
                                    dx, dy))
                     visit(q, cell, cellw, dx, dy, TR::to_acc(at));
                 q = qn;
@@ -307,8 +332,8 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const PP p)
                     int cell;
                     uint32_t cellw;
                     A dx, dy;
-                    if (sample_cell<A>(TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), tab->h[l], tab->w[l], tab->cstart[l],
-                                       tab->start[l], l, p.zeros, p.align, cell, cellw, dx, dy))
+                    if (cell_of<A>(p, TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), tab->h[l], tab->w[l], tab->cstart[l],
+                                       tab->start[l], l, cell, cellw, dx, dy))
                         visit(q, cell, cellw, dx, dy, PLACE ? TR::to_acc(attn[sidx]) : (A)0);
                 }
             }

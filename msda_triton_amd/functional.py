@@ -806,6 +806,7 @@ def multiscale_deformable_attention(
     align_corners: bool,
     level_shapes=None,
     points_per_level=None,
+    sampling_mode: Literal["bilinear", "discrete"] = "bilinear",
 ) -> torch.Tensor:
     """Differentiable multiscale deformable attention.
 
@@ -826,6 +827,11 @@ def multiscale_deformable_attention(
             ``num_points_list``).  Then ``sampling_points`` is ``[batch, num_queries, num_heads, S, 2]`` and
             ``attention_weights`` ``[batch, num_queries, num_heads, S]`` with ``S = sum(points_per_level)``, level-major
             (samples ``[start_l, start_l + P_l)`` belong to level ``l``).  Equal counts take the uniform call on a view.
+        sampling_mode: optional, not in the reference — ``"bilinear"`` (default) or ``"discrete"``: every sample reads the
+            one pixel ``(clamp(trunc(x * w + 0.5), 0, w - 1), clamp(trunc(y * h + 0.5), 0, h - 1))`` and nothing is
+            interpolated (transformers' ``method="discrete"``; see :mod:`msda_triton_amd.discrete`).  Accepted only with
+            ``padding_mode="border"``, ``align_corners=False`` (neither has a meaning there), with or without
+            ``points_per_level``; ``sampling_points`` gets no gradient (``None``).
 
     Returns:
         ``[batch, num_queries, num_heads, num_channels]``.
@@ -833,6 +839,12 @@ def multiscale_deformable_attention(
     Tensors on an AMD GPU ("cuda" device type on ROCm) run the hand-written gfx950 kernels and
     never fall back; host tensors run the plain-PyTorch formulation.
     """
+    if sampling_mode != "bilinear":
+        if sampling_mode != "discrete":
+            raise ValueError(f'`sampling_mode` should be "bilinear" or "discrete", but got {sampling_mode!r}.')
+        from .discrete import discrete_multiscale_deformable_attention
+        return discrete_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,
+                                                        align_corners, points_per_level, level_shapes)
     if points_per_level is not None:
         from .ragged import ragged_multiscale_deformable_attention
         return ragged_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,

@@ -15,6 +15,8 @@ D-FINE / DEIMv2 (``transformers/models/{d_fine,deimv2}/modeling_*.py``) instead 
 attribute, ``module.ms_deformable_attn_core(value, spatial_shapes_list, sampling_locations, attention_weights,
 num_points_list, method)`` with a point count per level; :func:`ms_deformable_attn_core` is that function over the
 per-level-count kernels (``method="default"`` only: zeros padding, ``align_corners=False``).
+:func:`ms_deformable_attn_core_v2` serves both of transformers' methods — ``"default"`` as above and ``"discrete"`` (one
+rounded pixel per sample, :mod:`msda_triton_amd.discrete`) — and is what ``replace_hf_msda(model, discrete=True)`` sets.
 """
 from __future__ import annotations
 
@@ -79,6 +81,24 @@ def ms_deformable_attn_core(value: torch.Tensor, spatial_shapes_list, sampling_l
     ``[B, Q, H, S]``, ``num_points_list`` the L point counts (S their sum).  Returns ``[B, Q, H * D]``."""
     if method != "default":
         raise ValueError(f"ms_deformable_attn_core serves method='default' only, got {method!r}")
+    return _core(value, spatial_shapes_list, sampling_locations, attention_weights, num_points_list, "bilinear")
+
+
+def ms_deformable_attn_core_v2(value: torch.Tensor, spatial_shapes_list, sampling_locations: torch.Tensor,
+                               attention_weights: torch.Tensor, num_points_list, method: str = "default") -> torch.Tensor:
+    """transformers' ``multi_scale_deformable_attention_v2`` for both of its methods, with the signature the D-FINE /
+    DEIMv2 decoders call: ``"default"`` is :func:`ms_deformable_attn_core`; ``"discrete"`` reads the one pixel
+    ``clamp(trunc(x * w + 0.5), 0, w - 1)`` / ``clamp(trunc(y * h + 0.5), 0, h - 1)`` per sample and gives the sampling
+    locations no gradient, as transformers' own."""
+    if method not in ("default", "discrete"):
+        raise ValueError(f"ms_deformable_attn_core_v2 serves method='default' and 'discrete', got {method!r}")
+    return _core(value, spatial_shapes_list, sampling_locations, attention_weights, num_points_list,
+                 "discrete" if method == "discrete" else "bilinear")
+
+
+def _core(value, spatial_shapes_list, sampling_locations, attention_weights, num_points_list, mode):
+    # bilinear: transformers samples with zeros padding; discrete: no padding mode ("border" is what the call accepts)
+    pad = "zeros" if mode == "bilinear" else "border"
     level_shapes = [(int(h), int(w)) for h, w in spatial_shapes_list]
     shapes = _shapes_tensor(level_shapes, value.device)
     counts = [int(p) for p in num_points_list]
@@ -88,23 +108,24 @@ def ms_deformable_attn_core(value: torch.Tensor, spatial_shapes_list, sampling_l
         # the mixed storage, as MultiScaleDeformableAttention.forward above
         autocast = _autocast_on()
         with torch.autocast("cuda", enabled=False):
-            out = multiscale_deformable_attention(value, shapes, sampling_locations, attention_weights, "zeros", False,
-                                                  level_shapes=level_shapes, points_per_level=counts)
+            out = multiscale_deformable_attention(value, shapes, sampling_locations, attention_weights, pad, False,
+                                                  level_shapes=level_shapes, points_per_level=counts, sampling_mode=mode)
         return (out if autocast else out.to(dtype)).flatten(2)
     if sampling_locations.dtype != dtype:
         sampling_locations = sampling_locations.to(dtype)
     if attention_weights.dtype != dtype:
         attention_weights = attention_weights.to(dtype)
-    out = multiscale_deformable_attention(value, shapes, sampling_locations, attention_weights, "zeros", False,
-                                          level_shapes=level_shapes, points_per_level=counts)
+    out = multiscale_deformable_attention(value, shapes, sampling_locations, attention_weights, pad, False,
+                                          level_shapes=level_shapes, points_per_level=counts, sampling_mode=mode)
     return out.flatten(2)
 
 
-def replace_hf_msda(model: nn.Module) -> int:
+def replace_hf_msda(model: nn.Module, discrete: bool = False) -> int:
     """Swap every HF ``MultiScaleDeformableAttention`` submodule of ``model`` for the adapter, and set
     :func:`ms_deformable_attn_core` on every module that carries an ``ms_deformable_attn_core`` attribute with
-    ``decoder_method == "default"`` (D-FINE / DEIMv2; ``"discrete"`` modules are left alone).  Returns the number of
-    modules replaced or patched."""
+    ``decoder_method == "default"`` (D-FINE / DEIMv2; ``"discrete"`` modules are left alone).  With ``discrete=True``
+    (opt-in) modules whose ``decoder_method`` is ``"discrete"`` are patched too, with
+    :func:`ms_deformable_attn_core_v2`.  Returns the number of modules replaced or patched."""
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -115,5 +136,10 @@ def replace_hf_msda(model: nn.Module) -> int:
         if hasattr(module, "ms_deformable_attn_core") and getattr(module, "decoder_method", None) == "default" and \
                 module.ms_deformable_attn_core is not ms_deformable_attn_core:
             module.ms_deformable_attn_core = ms_deformable_attn_core
+            count += 1
+        elif discrete and hasattr(module, "ms_deformable_attn_core") and \
+                getattr(module, "decoder_method", None) == "discrete" and \
+                module.ms_deformable_attn_core is not ms_deformable_attn_core_v2:
+            module.ms_deformable_attn_core = ms_deformable_attn_core_v2
             count += 1
     return count
