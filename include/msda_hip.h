@@ -162,7 +162,17 @@ extern "C" {
                        int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,           \
                        const int32_t *points_per_level, int64_t max_level_cells,                   \
                        int64_t value_row_stride, void *workspace, int64_t workspace_bytes,         \
-                       void *stream);
+                       void *stream);                                                              \
+    MSDA_API int msda_fwd_fused_ragged_##SUF(const void *value, const int64_t *shapes, const void *proj,\
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,          \
+                       int padding_mode, int align_corners, int64_t value_row_stride, void *stream);\
+    MSDA_API int msda_bwd_fused_ragged_##SUF(const void *grad_out, const void *value,               \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
+                       int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,\
+                       int padding_mode, int align_corners, int64_t max_level_cells,                \
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * Per-level point counts (ABI 12, additive): msda_fwd_ragged_<dtype> / msda_bwd_ragged_<dtype> take the arguments of
@@ -175,7 +185,26 @@ extern "C" {
  * as the D-FINE / DEIMv2 decoders lay them out (decoder_n_points = [3, 6, 3] ...).  Every size check of the uniform
  * entry points applies with L * P read as S; value_row_stride, MSDA_WS_RECORDS_IN_GRADS and MSDA_WS_PASSES(n) mean what
  * they mean there, and the workspace comes from msda_bwd_ragged_workspace_bytes.  grad_value is bitwise reproducible
- * while max_l P_l <= 1024.  The fused entry points keep one P for every level.
+ * while max_l P_l <= 1024.
+ *
+ * The module's fused pair with per-level counts — ADDITIONS WITHIN ABI 12, probed by symbol like the discrete entry points
+ * below: msda_fwd_fused_ragged_<suffix> / msda_bwd_fused_ragged_<suffix> take the arguments of msda_fwd_fused_<suffix> /
+ * msda_bwd_fused_<suffix> with P replaced by `points_per_level`, for the same eight suffixes (f32, f16, bf16, f64,
+ * f32_vbf16, f32_vf16, f32_sbf16, f32_sf16):
+ *
+ *   proj       [B, Q, H, S, 3]     (x offset, y offset, attention logit) per sample, level-major; grad_proj shaped alike
+ *   weights    softmax of the logits over all S samples of a (b, q, h) unit
+ *   ref_dim 2  point = ref + (ox / shapes[l][0], oy / shapes[l][1])             (the stored (h, w) order, as the uniform pair)
+ *   ref_dim 4  point = ref_xy + (ox, oy) * ref_wh / (2 * P_l)                   with the count of the sample's OWN level
+ *
+ * (D-FINE's offset * num_points_scale * ref_wh * offset_scale with num_points_scale = 1 / P_l, offset_scale = 0.5).
+ * grad_ref_partial is [B, Q, H, ref_dim] as there.  All S samples of a unit must fit one LDS pass (S <=
+ * msda_fused_lp_limit(D, elem_size)) and L must be at most 8 (the fused kernels' level scan is bounded, to keep their
+ * scalar registers out of scratch memory): otherwise MSDA_ERR_UNSUPPORTED and nothing is launched — compose the prologue
+ * around msda_fwd_ragged_ / msda_bwd_ragged_<dtype> then.  value_row_stride,
+ * max_level_cells and MSDA_WS_PASSES(n) mean what they mean in the uniform fused calls; the workspace comes from
+ * msda_bwd_fused_ragged_workspace_bytes, and grad_value runs the ragged operator's pipelines (bitwise reproducible while
+ * max_l P_l <= 1024).
  *
  * Discrete (nearest-pixel) sampling — ADDITIONS WITHIN ABI 12: no existing signature changes and MSDA_ABI_VERSION stays
  * 12, so a caller PROBES FOR THESE BY SYMBOL (dlsym / hasattr) instead of by version; a library built before them simply
@@ -227,7 +256,17 @@ MSDA_DECLARE(f32_vf16)
                        void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D,              \
                        int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,                  \
                        int align_corners, int64_t max_level_cells, int64_t value_row_stride,            \
-                       void *workspace, int64_t workspace_bytes, void *stream);
+                       void *workspace, int64_t workspace_bytes, void *stream);                        \
+    MSDA_API int msda_fwd_fused_ragged_##SUF(const void *value, const int64_t *shapes, const void *proj,\
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,          \
+                       int padding_mode, int align_corners, int64_t value_row_stride, void *stream);\
+    MSDA_API int msda_bwd_fused_ragged_##SUF(const void *grad_out, const void *value,               \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
+                       int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,\
+                       int padding_mode, int align_corners, int64_t max_level_cells,                \
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);
 MSDA_DECLARE_FUSED_STORAGE(f32_sbf16)
 MSDA_DECLARE_FUSED_STORAGE(f32_sf16)
 #undef MSDA_DECLARE_FUSED_STORAGE
@@ -269,6 +308,11 @@ MSDA_API int64_t msda_bwd_ragged_workspace_bytes(int64_t B, int64_t I, int64_t H
 MSDA_API int64_t msda_bwd_discrete_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                                    const int32_t *points_per_level, int elem_size, int value_elem_size,
                                                    int64_t max_level_cells, int flags);
+/* ... msda_bwd_fused_ragged_<suffix> (grad_value != NULL; within ABI 12, probe by symbol; flags: 0 | MSDA_WS_PASSES(n);
+ * elem_size: of the arithmetic type — 4 for the f32_s* suffixes; 0 for an unusable points_per_level) ... */
+MSDA_API int64_t msda_bwd_fused_ragged_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                                       const int32_t *points_per_level, int elem_size,
+                                                       int value_elem_size, int64_t max_level_cells, int flags);
 /* ... and msda_bwd_fused_<dtype> (grad_value != NULL). */
 MSDA_API int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                                 int64_t P, int elem_size, int value_elem_size,

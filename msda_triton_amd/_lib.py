@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = tuple(
     + ["msda_bwd_ragged_workspace_bytes", "msda_bwd_ragged_supported"]
     + [f"msda_{d}_discrete_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES]
     + ["msda_bwd_discrete_workspace_bytes", "msda_bwd_discrete_supported"]
+    + [f"msda_{d}_fused_ragged_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+    + ["msda_bwd_fused_ragged_workspace_bytes"]
     + ["msda_abi_version", "msda_last_error", "msda_set_option", "msda_get_option", "msda_bwd_workspace_bytes",
        "msda_bwd_fused_workspace_bytes", "msda_bwd_supported", "msda_fused_lp_limit", "msda_profile_read",
        "msda_last_launch_info"]
@@ -136,6 +138,19 @@ def load():
             lib.msda_bwd_discrete_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
             lib.msda_bwd_discrete_supported.restype = ci
             lib.msda_bwd_discrete_supported.argtypes = [i64] * 6 + [vp, ci]
+        # the module's fused pair with per-level point counts: additions within ABI 12 too (has_fused_ragged)
+        if hasattr(lib, "msda_bwd_fused_ragged_workspace_bytes"):
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                ffr = getattr(lib, f"msda_fwd_fused_ragged_{suf}")
+                ffr.restype = ci
+                # (value, shapes, proj, ref, out, B, I, H, D, Q, L, points_per_level, ref_dim, padding_mode, align_corners,
+                #  value_row_stride, stream)
+                ffr.argtypes = [vp] * 5 + [i64] * 6 + [vp, ci, ci, ci, i64, vp]
+                gfr = getattr(lib, f"msda_bwd_fused_ragged_{suf}")
+                gfr.restype = ci
+                gfr.argtypes = [vp] * 8 + [i64] * 6 + [vp, ci, ci, ci, i64, i64, vp, i64, vp]
+            lib.msda_bwd_fused_ragged_workspace_bytes.restype = i64
+            lib.msda_bwd_fused_ragged_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -163,6 +178,12 @@ def load_discrete():
         raise MSDALibraryError(f"{LIB_PATH} has no discrete-sampling entry points (msda_fwd_discrete_<dtype> ...): it "
                                "was built from older sources; rebuild the library")
     return lib
+
+
+def has_fused_ragged() -> bool:
+    """Does the loaded library have the fused module pair for per-level point counts (msda_fwd_fused_ragged_<dtype> ...,
+    additions within ABI 12, found by symbol)?  Without them the caller composes the prologue around the ragged operator."""
+    return hasattr(load(), "msda_bwd_fused_ragged_workspace_bytes")
 
 
 def check(rc: int, what: str) -> None:

@@ -78,6 +78,21 @@ extern "C" int64_t msda_bwd_ragged_workspace_bytes(int64_t B, int64_t I, int64_t
                                          ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), S);
 }
 
+// msda_bwd_fused_ragged_<dtype> (grad_value != NULL): the derived sampling points + attention weights (3 elements per
+// sample, rounded up to 256 bytes: msda_launch.hpp, fused_mat_bytes), then the ragged operator's sorted-pipeline workspace
+extern "C" int64_t msda_bwd_fused_ragged_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                                         const int32_t *points_per_level, int elem_size, int value_elem_size,
+                                                         int64_t max_level_cells, int flags)
+{
+    int64_t pmax, S;
+    if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || elem_size <= 0 || msda::ragged_counts(points_per_level, L, pmax, S) != 0)
+        return 0;
+    (void)value_elem_size;
+    const int64_t mat = (B * Q * H * S * 3 * (int64_t)elem_size + 255) / 256 * 256;
+    return mat + msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, pmax, elem_size, 0, 0, max_level_cells,
+                                               ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), S);
+}
+
 extern "C" int msda_bwd_ragged_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                          const int32_t *points_per_level, int elem_size)
 {

@@ -113,6 +113,29 @@ __device__ __forceinline__ int lvl_of(const RaggedParams &p, int sl, float)
     }
     return l;
 }
+// ... and the level's point count with it, from the same scan (the fused module kernels: a sample's box-size offset is
+// scaled by 1 / (2 P_l) of its OWN level): the level's first sample and its end — the first start beyond sl, pst[L] = S at
+// the latest — are picked up on the way, every pst[k] still one scalar operand at a constant offset.  Bounded by
+// kFusedRaggedMaxLevels: the fused kernels carry more live scalars than the plain ones (reference points, the second
+// storage type, the workspace pointers), and with all 32 possible level starts held in SGPRs next to them the backward
+// kernels at the VGPR cap had nowhere left to spill scalars but scratch memory.  The host refuses L beyond the bound
+// (MSDA_ERR_UNSUPPORTED: the caller composes the prologue around the ragged operator); DETR pyramids have 3 ... 5 levels.
+constexpr int kFusedRaggedMaxLevels = 8;
+__device__ __forceinline__ int lvl_of(const RaggedParams &p, int sl, int &pts)
+{
+    int l = 0, st = 0, en = p.LP;
+#pragma unroll
+    for (int k = 1; k <= kFusedRaggedMaxLevels; ++k) {
+        if (k > p.L) break;
+        const int s = p.pst[k];
+        const bool ge = sl >= s;
+        l += ge ? 1 : 0;
+        st = ge ? s : st;
+        en = ge ? en : min(en, s);
+    }
+    pts = en - st;
+    return l;
+}
 // First sample of level l (l uniform, 0 <= l <= L).
 __device__ __forceinline__ int lvl_start(const RaggedParams &p, int l)
 {
@@ -577,7 +600,10 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                         const int sl = f - imul24(fu, sc);
                         const int fq = wq0 + fu;
                         if (fq < q_end_) {
-                            const int l = div_small(sl, p.P, inv_P);
+                            [[maybe_unused]] int npts = p.P;  // per-level point counts: the count of the sample's own level
+                            int l;
+                            if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
+                            else l = div_small(sl, p.P, inv_P);
                             const int sidx = imul24(fq, HLP) + sl;
                             const A ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
                             const A lg = SR::to_acc(proj3[3 * sidx + 2]);
@@ -588,11 +614,17 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                                 // NB: (x, y) offsets are divided by img_shapes in its stored (h, w) order (frontend.py:275)
                                 w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->h[l];
                                 w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->w[l];
+                            } else if constexpr (kRagged<PP>) {
+                                // multiply, divide, add — each rounded once, nothing for the compiler to fuse: the point
+                                // is bit for bit what the same expression gives in PyTorch, so a sample within an ulp of
+                                // a pixel boundary lands on the same side of it as in the unfused composition
+                                w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) / (A)(2 * npts);
+                                w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) / (A)(2 * npts);
                             } else {
                                 w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) / (A)(2 * p.P);
                                 w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) / (A)(2 * p.P);
                             }
-                            w.v[3] = (A)0;
+                            w.v[3] = kRagged<PP> ? (A)l : (A)0;  // (per-level counts: phase 1 takes the level from here)
                             w_rec[imul24(fu, scp) + sl] = w;
                         }
                     }
@@ -617,11 +649,13 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                     const int sl = s0 + (f - imul24(fu, sc));
                     const int fq = wq0 + fu;
                     if (fq < q_end_) {
-                        const int l = lvl_of(p, sl, inv_P);
+                        int l;
+                        if constexpr (!(FUSED && kRagged<PP>)) l = lvl_of(p, sl, inv_P);
                         const int sidx = imul24(fq, HLP) + sl;
                         A sx, sy, a;
                         if constexpr (FUSED) {  // everything was parked by phase 0
                             const Rec4<A> pk = w_rec[imul24(fu, scp) + (sl - s0)], un = w_rec[imul24(fu, scp) + sc];
+                            if constexpr (kRagged<PP>) l = (int)pk.v[3];
                             sx = pk.v[1];
                             sy = pk.v[2];
                             a = exp_t(pk.v[0] - un.v[0]) * un.v[1];
@@ -1066,9 +1100,12 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     const int sl = f - imul24(fu, sc);
                     const int fq = wq0 + fu;
                     if (fq < q_end_) {
-                        const int l = div_small(sl, p.P, inv_P);
+                        [[maybe_unused]] int npts = p.P;  // per-level point counts: the count of the sample's own level
+                        int l;
+                        if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
+                        else l = div_small(sl, p.P, inv_P);
                         const int sidx = imul24(fq, HLP) + sl;
-                        const A ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
+                        A ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
                         const A lg = SR::to_acc(proj3[3 * sidx + 2]);
                         const T *r = refp + (size_t)fq * p.ref_dim;
                         Rec4<A> w;
@@ -1076,11 +1113,21 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         if (p.ref_dim == 2) {
                             w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->h[l];  // NB: (x, y) / img_shapes in its stored (h, w) order
                             w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->w[l];
+                        } else if constexpr (kRagged<PP>) {
+                            // the point as the fused forward forms it (multiply, divide, add: PyTorch's bits, so the
+                            // location gradient sees the same bilinear cell as the unfused composition); the offsets are
+                            // then parked SCALED by their level's 1 / (2 P_l): the box-size gradient below and the point
+                            // written for the grad_value passes need no level look-up of their own
+                            w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) / (A)(2 * npts);
+                            w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) / (A)(2 * npts);
+                            const A hinv = (A)1 / (A)(2 * npts);
+                            ox *= hinv;
+                            oy *= hinv;
                         } else {
                             w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) * half_inv_P;
                             w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) * half_inv_P;
                         }
-                        w.v[3] = (A)0;
+                        w.v[3] = kRagged<PP> ? (A)l : (A)0;  // (per-level counts: phase 1 takes the level from here)
                         w_rec[imul24(fu, scp) + sl] = w;
                         w_ox[imul24(fu, scp) + sl] = ox;
                         w_oy[imul24(fu, scp) + sl] = oy;
@@ -1107,7 +1154,9 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                 const int sl = s0 + (f - imul24(fu, sc));
                 const int fq = wq0 + fu;
                 if (fq < q_end_) {
-                    const int l = lvl_of(p, sl, inv_P);
+                    int l;
+                    if constexpr (FUSED && kRagged<PP>) l = (int)w_rec[imul24(fu, scp) + (sl - s0)].v[3];  // (parked by phase 0)
+                    else l = lvl_of(p, sl, inv_P);
                     const int sidx = imul24(fq, HLP) + sl;
                     const int lh = tab->h[l], lw = tab->w[l];
                     A px, py, a;
@@ -1458,8 +1507,9 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     gr[0] = TR::from_acc(f_gx);
                     gr[1] = TR::from_acc(f_gy);
                     if (p.ref_dim == 4) {
-                        gr[2] = TR::from_acc(f_gw * half_inv_P);
-                        gr[3] = TR::from_acc(f_gh * half_inv_P);
+                        // (per-level point counts: the parked offsets already carry their level's 1 / (2 P_l))
+                        gr[2] = TR::from_acc(kRagged<PP> ? f_gw : f_gw * half_inv_P);
+                        gr[3] = TR::from_acc(kRagged<PP> ? f_gh : f_gh * half_inv_P);
                     }
                 }
             }
@@ -1477,7 +1527,10 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     const Rec4<A> res = w_rec[imul24(fu, scp) + (sl - s0)];
                     if constexpr (FUSED) {
                         // chain rule through the prologue: softmax (logit), offset scaling (dx, dy)
-                        const int l = div_small(sl, p.P, inv_P);
+                        [[maybe_unused]] int npts = p.P;
+                        int l;
+                        if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
+                        else l = div_small(sl, p.P, inv_P);
                         const int rs_ = imul24(fu, scp) + (sl - s0);
                         const A a = w_a[rs_], dot = w_a[imul24(fu, scp) + sc];
                         const T *r = refp + (size_t)fq * p.ref_dim;
@@ -1485,6 +1538,10 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         if (p.ref_dim == 2) {
                             kx = (A)1 / (A)tab->h[l];
                             ky = (A)1 / (A)tab->w[l];
+                        } else if constexpr (kRagged<PP>) {
+                            const A hinv = (A)1 / (A)(2 * npts);
+                            kx = TR::to_acc(r[2]) * hinv;
+                            ky = TR::to_acc(r[3]) * hinv;
                         } else {
                             kx = TR::to_acc(r[2]) * half_inv_P;
                             ky = TR::to_acc(r[3]) * half_inv_P;
@@ -1502,6 +1559,9 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                             if (p.ref_dim == 2) {
                                 m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox / (A)tab->h[l]);
                                 m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy / (A)tab->w[l]);
+                            } else if constexpr (kRagged<PP>) {  // (ox, oy: scaled when they were parked)
+                                m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]));
+                                m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]));
                             } else {
                                 m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) * half_inv_P);
                                 m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) * half_inv_P);

@@ -375,6 +375,13 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
     // (the sample-gradient kernel has the variant for its reduce-scatter units: float accumulation, 4 or 8 lanes)
     // fp32 operators only: measured at c3 (bf16, 64-byte rows: forward 88 against 86 us) and c5 (fp16, D = 64, L * P = 40 in
     // three trips: 3.17 against 2.93 ms) the 16-bit operators do not gain
+    if constexpr ((MODE == 2 || MODE == 3) && kRagged<PP>) {
+        // (the fused kernels' level scan is bounded, msda_kernels.hpp; before anything is launched)
+        if (p.L > kFusedRaggedMaxLevels) {
+            set_error("the fused prologue with per-level point counts serves at most %d levels, got %d", kFusedRaggedMaxLevels, p.L);
+            return MSDA_ERR_UNSUPPORTED;
+        }
+    }
     // small problems (decoder calls): the forward with one wave per unit (msda_fwd_unit_kernel)
     if constexpr (MODE == 0 && VEC * sizeof(T) == 16 && sizeof(A) == 4) {
         const long long units = (long long)p.B * p.Q * p.H;
@@ -453,7 +460,7 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
     static std::atomic<uint64_t> big_lds_done{0};  // one per template instantiation
     const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
     if constexpr (MODE == 3) {
-        auto kernel = msda_bwd_sample_kernel<T, VEC, G, true, TV, kBlock, false, TS>;
+        auto kernel = msda_bwd_sample_kernel<T, VEC, G, true, TV, kBlock, false, TS, PP>;
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, p);
     } else if constexpr (MODE == 1) {
@@ -461,7 +468,7 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, p);
     } else if constexpr (MODE == 2) {
-        auto kernel = msda_fwd_kernel<T, VEC, G, true, TV, kBlock, false, TS>;
+        auto kernel = msda_fwd_kernel<T, VEC, G, true, TV, kBlock, false, TS, PP>;
         allow_big_lds(kernel, big_lds_done);
         hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, p);
     } else {
@@ -819,12 +826,16 @@ int run_fwd(const void *value, const int64_t *shapes, const void *loc, const voi
 // Module forward with the prologue fused in: `proj` is the raw query projection
 // [B, Q, H, L, P, 3] = (x offset, y offset, attention logit), `ref` the reference points [B, Q, ref_dim].
 // TS: storage type of `proj` and `out` (T unless the module keeps them in 16 bits next to fp32 reference points)
-template <typename T, typename TV = T, typename TS = T>
+// PP = RaggedParams (msda_fwd_fused_ragged_<dtype>): per-level point counts `ppl` (ragged_counts checked them; P is their
+// maximum), `proj` [B, Q, H, S, 3]
+template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, const void *ref, void *out, int64_t B,
                   int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,
-                  int align_corners, int64_t value_row_stride, void *stream_)
+                  int align_corners, int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr)
 {
-    const Dims d{B, I, H, D, Q, L, P};
+    Dims d{B, I, H, D, Q, L, P};
+    if (ppl != nullptr)
+        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const size_t out_bytes = (size_t)(B * Q * H * D) * sizeof(TS);
     if (out_bytes == 0) return 0;
@@ -835,11 +846,11 @@ int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, co
     const void *ptrs[] = {out};
     int rc = check_common<T>(d, padding_mode, ptrs, 1);
     if (rc) return rc;
-    if (L * P == 0 || I == 0) return (int)hipMemsetAsync(out, 0, out_bytes, stream);
+    if (samples(d) == 0 || I == 0) return (int)hipMemsetAsync(out, 0, out_bytes, stream);
     const void *ptrs2[] = {value, shapes, proj, ref};
     rc = check_common<T>(d, padding_mode, ptrs2, 4);
     if (rc) return rc;
-    if (Q * H * L * P * 3 >= ((int64_t)1 << 31)) {
+    if (Q * H * samples(d) * 3 >= ((int64_t)1 << 31)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
@@ -848,13 +859,14 @@ int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, co
         set_error("misaligned buffer");
         return MSDA_ERR_MISALIGNED;
     }
-    Params p{};
+    PP p{};
     p.value = value;
     p.shapes = shapes;
     p.loc = proj;
     p.attn = nullptr;
     p.out = out;
     fill_params(p, d, padding_mode, align_corners);
+    fill_level_starts(p, ppl, L);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.ref = ref;
@@ -1301,18 +1313,24 @@ int run_bwd_discrete(const void *grad_out, const void *value, const int64_t *sha
 // grad_value, grad_proj [B,Q,H,L,P,3] and per-head partial sums of grad_reference_points [B,Q,H,ref_dim].
 // The first `fused_mat_bytes` of the workspace receive the sampling points / attention weights the kernel
 // derives (the grad_value passes read them); the rest is the sorted pipeline's workspace.
-inline size_t fused_mat_bytes(int64_t B, int64_t H, int64_t Q, int64_t L, int64_t P, size_t elem)
+// (S: samples of a (b, q, h) unit — L * P, or the sum of the per-level point counts)
+inline size_t fused_mat_bytes(int64_t B, int64_t H, int64_t Q, int64_t S, size_t elem)
 {
-    return align_up((size_t)(B * Q * H * L * P) * 3 * elem, 256);
+    return align_up((size_t)(B * Q * H * S) * 3 * elem, 256);
 }
 
-template <typename T, typename TV = T, typename TS = T>
+// PP = RaggedParams (msda_bwd_fused_ragged_<dtype>): per-level point counts `ppl`, proj / grad_proj [B, Q, H, S, 3]; the
+// derived points and weights go to the workspace in the ragged operator's layout and its grad_value pipeline reads them
+template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes, const void *proj, const void *ref,
                   void *grad_value, void *grad_proj, void *grad_ref_part, int64_t B, int64_t I, int64_t H, int64_t D,
                   int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode, int align_corners,
-                  int64_t max_level_cells, int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream_)
+                  int64_t max_level_cells, int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream_,
+                  const int32_t *ppl = nullptr)
 {
-    const Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
+    Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
+    if (ppl != nullptr)
+        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     int rc = check_common<T>(d, padding_mode, nullptr, 0);
     if (rc) return rc;
@@ -1325,8 +1343,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         return MSDA_ERR_BAD_ARG;
     }
     const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
-    const size_t ns = (size_t)(B * Q * H * L * P);
-    if (B * Q * H * D == 0 || L * P == 0 || I == 0) {  // no sample touches anything: all gradients are zero
+    const size_t ns = (size_t)(B * Q * H * samples(d));
+    if (B * Q * H * D == 0 || samples(d) == 0 || I == 0) {  // no sample touches anything: all gradients are zero
         hipError_t e = hipSuccess;
         if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
         if (e == hipSuccess && ns) e = hipMemsetAsync(grad_proj, 0, ns * 3 * sizeof(TS), stream);
@@ -1336,7 +1354,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
     const void *ptrs[] = {grad_out, value, shapes, proj, ref};
     rc = check_common<T>(d, padding_mode, ptrs, 5);
     if (rc) return rc;
-    if (Q * H * L * P * 3 >= ((int64_t)1 << 31)) {
+    if (Q * H * samples(d) * 3 >= ((int64_t)1 << 31)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
@@ -1347,12 +1365,12 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         return MSDA_ERR_MISALIGNED;
     }
     const bool want_value = grad_value != nullptr;
-    const size_t mat = fused_mat_bytes(B, H, Q, L, P, sizeof(T));
+    const size_t mat = fused_mat_bytes(B, H, Q, samples(d), sizeof(T));
     if (want_value && (workspace == nullptr || !aligned_to(workspace, 256) || (uint64_t)workspace_bytes < mat)) {
         set_error("the fused backward needs a 256-byte aligned workspace of at least %zu bytes for grad_value", mat);
         return MSDA_ERR_BAD_ARG;
     }
-    Params p{};
+    PP p{};
     p.value = value;
     p.shapes = shapes;
     p.loc = proj;
@@ -1362,6 +1380,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
     p.grad_loc = grad_proj;
     p.grad_attn = grad_ref_part;
     fill_params(p, d, padding_mode, align_corners);
+    fill_level_starts(p, ppl, L);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.ref = ref;
@@ -1474,7 +1493,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         return msda::run_bwd_discrete<T, TV>(grad_out, value, shapes, loc, attn, grad_value, grad_attn, B, I, H, \
                                              D, Q, L, points_per_level, max_level_cells, value_row_stride,       \
                                              workspace, workspace_bytes, stream);                                \
-    }
+    }                                                                                                            \
+    MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
 // fp32 reference points and fp32 arithmetic (msda_fwd_fused_f32_sbf16 / _sf16): fused entry points only
@@ -1498,6 +1518,41 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                           grad_ref_partial, B, I, H, D, Q, L, P, ref_dim, padding_mode,          \
                                           align_corners, max_level_cells, value_row_stride, workspace,           \
                                           workspace_bytes, stream);                                              \
+    }                                                                                                            \
+    MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)
+
+// the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
+// points, TV value rows, TS projection / out / their gradients)
+#define MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, TS)                                                     \
+    extern "C" int msda_fwd_fused_ragged_##SUF(const void *value, const int64_t *shapes, const void *proj,       \
+                                               const void *ref, void *out, int64_t B, int64_t I, int64_t H,       \
+                                               int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level,  \
+                                               int ref_dim, int padding_mode, int align_corners,                  \
+                                               int64_t value_row_stride, void *stream)                            \
+    {                                                                                                            \
+        int64_t pmax, S;                                                                                         \
+        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
+        if (rc) return rc;                                                                                       \
+        return msda::run_fwd_fused<T, TV, TS, msda::RaggedParams>(value, shapes, proj, ref, out, B, I, H, D, Q, L, \
+                                                                  pmax, ref_dim, padding_mode, align_corners,     \
+                                                                  value_row_stride, stream, points_per_level);    \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_ragged_##SUF(const void *grad_out, const void *value, const int64_t *shapes,   \
+                                               const void *proj, const void *ref, void *grad_value,               \
+                                               void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I,     \
+                                               int64_t H, int64_t D, int64_t Q, int64_t L,                        \
+                                               const int32_t *points_per_level, int ref_dim, int padding_mode,    \
+                                               int align_corners, int64_t max_level_cells,                        \
+                                               int64_t value_row_stride, void *workspace,                         \
+                                               int64_t workspace_bytes, void *stream)                             \
+    {                                                                                                            \
+        int64_t pmax, S;                                                                                         \
+        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
+        if (rc) return rc;                                                                                       \
+        return msda::run_bwd_fused<T, TV, TS, msda::RaggedParams>(                                                \
+            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, pmax,  \
+            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
+            stream, points_per_level);                                                                           \
     }
 
 // one storage type for every tensor

@@ -438,6 +438,100 @@ public:
     }
 };
 
+// The fused module core with per-level point counts (msda_fwd_fused_ragged_ / msda_bwd_fused_ragged_<dtype>, additions
+// within ABI 12): proj [B, Q, H, S, 3], `counts` the L point counts (host numbers; the Python caller checked them, that
+// they are not all equal and that the fused kernels take them — S within msda_fused_lp_limit, at most 8 levels — so the
+// library never declines).  A node of its own for the reason MSDARaggedFunction has one.
+using FwdFusedRaggedFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
+                                 int64_t, int64_t, int64_t, const int32_t *, int, int, int, int64_t, void *);
+using BwdFusedRaggedFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *,
+                                 void *, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int, int, int,
+                                 int64_t, int64_t, void *, int64_t, void *);
+std::pair<FwdFusedRaggedFn, BwdFusedRaggedFn> fused_ragged_fns_for(at::ScalarType t, at::ScalarType c)
+{
+    if (t != c) {
+        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
+                          "unsupported dtype combination: value ", t, " with ", c);
+        if (t == at::kBFloat16) return {msda_fwd_fused_ragged_f32_vbf16, msda_bwd_fused_ragged_f32_vbf16};
+        return {msda_fwd_fused_ragged_f32_vf16, msda_bwd_fused_ragged_f32_vf16};
+    }
+    switch (t) {
+    case at::kFloat: return {msda_fwd_fused_ragged_f32, msda_bwd_fused_ragged_f32};
+    case at::kHalf: return {msda_fwd_fused_ragged_f16, msda_bwd_fused_ragged_f16};
+    case at::kBFloat16: return {msda_fwd_fused_ragged_bf16, msda_bwd_fused_ragged_bf16};
+    case at::kDouble: return {msda_fwd_fused_ragged_f64, msda_bwd_fused_ragged_f64};
+    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
+    }
+}
+
+class MSDAFusedRaggedFunction : public torch::autograd::Function<MSDAFusedRaggedFunction> {
+public:
+    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
+                              const at::Tensor &proj_, const at::Tensor &ref_, int64_t padding_mode, bool align_corners,
+                              int64_t level_cells, const std::vector<int64_t> &counts)
+    {
+        const auto [img, vrow] = value_rows(img_);
+        const at::Tensor proj = proj_.contiguous(), ref = ref_.contiguous();
+        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        at::Tensor out = at::empty({B, Q, H, D}, proj.options());
+        const c10::DeviceGuard guard(img.device());
+        check_rc(fused_ragged_fns_for(img.scalar_type(), proj.scalar_type())
+                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(), out.data_ptr(), B,
+                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), (int)ref.size(-1), (int)padding_mode,
+                            align_corners ? 1 : 0, vrow, current_stream(img)),
+                 "msda_fwd_fused_ragged");
+        ctx->save_for_backward({img, shapes, proj, ref});
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["align_corners"] = align_corners;
+        ctx->saved_data["level_cells"] = level_cells;
+        ctx->saved_data["vrow"] = vrow;
+        ctx->saved_data["counts"] = counts;
+        return out;
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
+                                                   torch::autograd::variable_list grads)
+    {
+        const auto saved = ctx->get_saved_variables();
+        const at::Tensor &img = saved[0], &shapes = saved[1], &proj = saved[2], &ref = saved[3];
+        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
+        const bool align_corners = ctx->saved_data["align_corners"].toBool();
+        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
+        const int64_t vrow = ctx->saved_data["vrow"].toInt();
+        const auto counts = ctx->saved_data["counts"].toIntVector();
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        const int64_t L = (int64_t)ppl.size();
+        at::Tensor gout = grads[0].contiguous();
+        if (gout.scalar_type() != proj.scalar_type()) gout = gout.to(proj.scalar_type());
+        const bool want_value = ctx->needs_input_grad(0);
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
+        const int64_t ref_dim = ref.size(-1);
+        at::Tensor g_img, ws;
+        at::Tensor g_proj = at::empty_like(proj), g_ref_part = at::empty({B, Q, H, ref_dim}, proj.options());
+        int64_t ws_bytes = 0;
+        if (want_value) {
+            g_img = at::empty(img.sizes(), img.options());
+            ws_bytes = msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)proj.element_size(),
+                                                             (int)img.element_size(), level_cells, 0);
+            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
+        }
+        {
+            const c10::DeviceGuard guard(img.device());
+            check_rc(fused_ragged_fns_for(img.scalar_type(), proj.scalar_type())
+                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(),
+                                 want_value ? g_img.data_ptr() : nullptr, g_proj.data_ptr(), g_ref_part.data_ptr(), B, I, H,
+                                 D, Q, L, ppl.data(), (int)ref_dim, padding_mode, align_corners ? 1 : 0, level_cells, vrow,
+                                 ws.defined() ? ws.data_ptr() : nullptr, ws_bytes, current_stream(img)),
+                     "msda_bwd_fused_ragged");
+        }
+        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_proj : at::Tensor(),
+                                           ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor(), at::Tensor(),
+                                           at::Tensor(), at::Tensor(), at::Tensor()});
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------------
 // Row ranges of the flattened (b, q) row space — the launches of the row-sharded operator
 // (msda_triton_amd/distributed.py; SURVEY 8e, reference independence argument kernels.py:18-21).  A rank's rows
@@ -667,6 +761,13 @@ at::Tensor msda_fused(const at::Tensor &img, const at::Tensor &shapes, const at:
     return MSDAFusedFunction::apply(img, shapes, proj, ref, padding_mode, align_corners, level_cells);
 }
 
+at::Tensor msda_fused_ragged(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj, const at::Tensor &ref,
+                             int64_t padding_mode, bool align_corners, int64_t level_cells,
+                             const std::vector<int64_t> &counts)
+{
+    return MSDAFusedRaggedFunction::apply(img, shapes, proj, ref, padding_mode, align_corners, level_cells, counts);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -686,6 +787,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("msda_fused", &msda_fused, "module core with the softmax / sampling-point prologue fused in (differentiable)",
           pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
           pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells") = 0);
+    m.def("msda_fused_ragged", &msda_fused_ragged,
+          "module core with the prologue fused in, per-level point counts: proj [B,Q,H,S,3] (differentiable)",
+          pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
+          pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells"),
+          pybind11::arg("points_per_level"));
     m.def("msda_rows", &msda_rows,
           "rows [r0, r1) of the flattened (b, q) row space computed in `chunks` pieces into a full [B,Q,H,D] result "
           "(differentiable; the row-sharded operator without its exchange)",

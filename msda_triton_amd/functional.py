@@ -661,10 +661,17 @@ class _HipFusedModuleCoreFunction(Function):
         return g_img, None, g_proj, g_ref, None, None, None
 
 
-def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None) -> torch.Tensor:
+def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None,
+                      points_per_level=None) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *module_sampling_inputs(proj, ...))`` — on GPU tensors
     with the prologue fused into the forward kernel; on host tensors exactly that composition.  ``level_shapes``: the
-    level sizes as host numbers, optional (:func:`level_cells_of`)."""
+    level sizes as host numbers, optional (:func:`level_cells_of`).  ``points_per_level``: a point count per level; then
+    ``proj`` is ``[B, Q, H, S, 3]`` with ``S = sum(points_per_level)``, level-major
+    (:func:`msda_triton_amd.ragged.ragged_module_sampling_inputs` states the prologue)."""
+    if points_per_level is not None:
+        from .ragged import fused_ragged_module_core
+        return fused_ragged_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners,
+                                        points_per_level, level_shapes)
     level_cells = level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1])
     if img.device.type == "cuda" and img_shapes.device != img.device:
         # the level table is a handful of integers: follow `img` (the reference's module accepts a host-resident

@@ -7,13 +7,15 @@ GEMMs; ``_linear.py`` only re-shapes their weight gradient for tall inputs); the
 """
 from __future__ import annotations
 
-from typing import Literal, Optional
+import numbers
+from typing import Literal, Optional, Sequence, Union
 
 import torch
 from torch import nn
 
 from ._linear import projection
 from .functional import fused_module_core, module_sampling_inputs
+from .ragged import ragged_module_sampling_inputs
 
 
 class MultiscaleDeformableAttention(nn.Module):
@@ -24,7 +26,11 @@ class MultiscaleDeformableAttention(nn.Module):
         hidden_dim: projected feature dimension; must be divisible by ``num_heads``.
         num_levels: number of pyramid levels.
         num_heads: number of attention heads.
-        num_points: sampling points per level.
+        num_points: sampling points per level; or (not in the reference) one count per level, e.g. ``[3, 6, 3]`` — the
+            D-FINE / DEIMv2 / RT-DETRv2 layout: the query projection then holds ``sum(num_points)`` samples per head,
+            level-major, the softmax runs over all of them and a 4-d reference box scales a sample's offset by
+            ``1 / (2 * num_points[l])`` of its own level.  A list of equal counts is the same module as the ``int``
+            (same parameters, same numbers).
         padding_mode: ``"border"`` or ``"zeros"``.
         align_corners: grid alignment.
         value_dtype: (not in the reference; GPU only) ``torch.bfloat16`` / ``torch.float16``: keep the projected value
@@ -39,8 +45,8 @@ class MultiscaleDeformableAttention(nn.Module):
         ValueError: if ``hidden_dim`` is not divisible by ``num_heads`` (frontend.py:211-212).
     """
 
-    def __init__(self, emb_dim: int, hidden_dim: int, num_levels: int, num_heads: int, num_points: int,
-                 padding_mode: Literal["border", "zeros"], align_corners: bool,
+    def __init__(self, emb_dim: int, hidden_dim: int, num_levels: int, num_heads: int,
+                 num_points: Union[int, Sequence[int]], padding_mode: Literal["border", "zeros"], align_corners: bool,
                  value_dtype: Optional[torch.dtype] = None):
         super().__init__()
         if hidden_dim % num_heads != 0:
@@ -48,6 +54,18 @@ class MultiscaleDeformableAttention(nn.Module):
                 f"Hidden dimension ({hidden_dim=}) should be divisible by number of heads ({num_heads=}).")
         if value_dtype not in (None, torch.bfloat16, torch.float16):
             raise ValueError(f"`value_dtype` should be None, torch.bfloat16 or torch.float16, but got {value_dtype}.")
+        # per-level point counts; None with an `int` (one count for every level: the reference's module, unchanged)
+        self.points_per_level = None
+        if not isinstance(num_points, numbers.Integral):
+            counts = tuple(int(p) for p in num_points)
+            if len(counts) != num_levels:
+                raise ValueError(f"`num_points` has {len(counts)} entries, but the module has {num_levels=} levels.")
+            if any(p < 1 for p in counts):
+                raise ValueError(f"every entry of `num_points` should be at least 1, but got {list(counts)}.")
+            if all(p == counts[0] for p in counts):
+                num_points = counts[0]  # equal counts: the uniform module
+            else:
+                self.points_per_level = counts
         self.value_dtype = value_dtype
         self.num_levels = num_levels
         self.num_heads = num_heads
@@ -57,12 +75,18 @@ class MultiscaleDeformableAttention(nn.Module):
         self.align_corners = align_corners
         # one fused query projection: (x offset, y offset, attention logit) per (head, level, point)
         self.img_input_proj = nn.Linear(emb_dim, hidden_dim)
-        self.query_input_proj = nn.Linear(emb_dim, num_heads * num_levels * num_points * 3)
+        # (per-level counts: laid out [H, S, 3] with S = sum(num_points), samples level-major)
+        samples = num_levels * num_points if self.points_per_level is None else sum(self.points_per_level)
+        self.query_input_proj = nn.Linear(emb_dim, num_heads * samples * 3)
         self.query_output_proj = nn.Linear(hidden_dim, emb_dim)
 
     def sampling_inputs(self, img_shapes: torch.Tensor, queries: torch.Tensor, reference_points: torch.Tensor):
-        """Query projection -> (sampling_points [B,N,H,L,P,2], attention_weights [B,N,H,L,P])."""
+        """Query projection -> (sampling_points [B,N,H,L,P,2], attention_weights [B,N,H,L,P]); with per-level point
+        counts ([B,N,H,S,2], [B,N,H,S]), level-major."""
         B, N, _ = queries.shape
+        if self.points_per_level is not None:
+            proj = self.query_input_proj(queries).reshape(B, N, self.num_heads, sum(self.points_per_level), 3)
+            return ragged_module_sampling_inputs(proj, img_shapes, reference_points, self.points_per_level)
         proj = self.query_input_proj(queries).reshape(B, N, self.num_heads, self.num_levels, self.num_points, 3)
         return module_sampling_inputs(proj, img_shapes, reference_points)
 
@@ -89,7 +113,9 @@ class MultiscaleDeformableAttention(nn.Module):
                 f"`reference_points` should have the last dim either 2 or 4, but got {reference_points.shape[-1]}.")
         # one projection holds (x offset, y offset, attention logit) per (head, level, point); on the GPU the softmax
         # and the offset -> sampling-point math run inside the attention kernel's prologue
-        proj = projection(self.query_input_proj, queries).reshape(B, N, H, L, P, 3)
+        counts = self.points_per_level
+        proj = projection(self.query_input_proj, queries)
+        proj = proj.reshape(B, N, H, L, P, 3) if counts is None else proj.reshape(B, N, H, sum(counts), 3)
         # (the value pyramid is this module's own tensor: for large fp32 calls its pixels' rows are written one 128-byte line
         #  apart, which takes them off the vector L1's tag-RAM skew — functional.value_row_pad; the kernels read that layout
         #  in place.  Measured at the c2 module shape, fp32, tools/module_pad_ab.py: step 1.05 -> 1.02 ms at 10 000 queries,
@@ -104,15 +130,15 @@ class MultiscaleDeformableAttention(nn.Module):
             # result and their gradients; rounding happens at the same places (the GEMMs' outputs / inputs)
             with torch.autocast("cuda", enabled=False):
                 attended = fused_module_core(value, img_shapes, proj, reference_points.float(), self.padding_mode,
-                                             self.align_corners, level_shapes)
+                                             self.align_corners, level_shapes, counts)
         elif self.value_dtype is not None and value.device.type == "cuda":
             # 16-bit value pyramid next to fp32 sampling inputs: the mixed-storage kernels read it as it is (no fp32
             # copy, which is what autocast's cast_inputs would make), so the call sits outside autocast
             value = value.to(self.value_dtype)  # nothing to do when autocast already produced this dtype
             with torch.autocast("cuda", enabled=False):
                 attended = fused_module_core(value, img_shapes, proj.float(), reference_points.float(),
-                                             self.padding_mode, self.align_corners, level_shapes).to(proj.dtype)
+                                             self.padding_mode, self.align_corners, level_shapes, counts).to(proj.dtype)
         else:
             attended = fused_module_core(value, img_shapes, proj, reference_points, self.padding_mode,
-                                         self.align_corners, level_shapes)
+                                         self.align_corners, level_shapes, counts)
         return projection(self.query_output_proj, attended.reshape(B, N, self.hidden_dim))

@@ -211,3 +211,236 @@ def ragged_multiscale_deformable_attention(img, img_shapes, sampling_points, att
                                F._padding_code(padding_mode), bool(align_corners), level_cells, list(counts))
     return _HipRaggedFunction.apply(img, img_shapes, sampling_points, attention_weights, padding_mode,
                                     bool(align_corners), counts, level_cells)
+
+
+# ------------------------------------------------------------------------------------------
+# module core with per-level point counts: raw projection [B, Q, H, S, 3] -> attended values
+# ------------------------------------------------------------------------------------------
+def check_proj_points_per_level(img_shapes, proj, reference_points, points_per_level) -> Tuple[int, ...]:
+    """Validate the module core's ragged layout; returns the counts as a tuple of ints.  Raises ``ValueError``."""
+    counts = tuple(int(p) for p in points_per_level)
+    if img_shapes.dim() != 2 or img_shapes.shape[1] != 2:
+        raise ValueError(f"`img_shapes` should be [L, 2], but got {tuple(img_shapes.shape)}.")
+    L = int(img_shapes.shape[0])
+    if len(counts) != L:
+        raise ValueError(f"`points_per_level` has {len(counts)} entries, but `img_shapes` describes {L} levels.")
+    if any(p < 1 for p in counts):
+        raise ValueError(f"every entry of `points_per_level` should be at least 1, but got {list(counts)}.")
+    if proj.dim() != 5 or proj.shape[-1] != 3:
+        raise ValueError("with `points_per_level`, expected proj [B,N,H,S,3] = (x offset, y offset, logit) per sample; "
+                         f"got {tuple(proj.shape)}")
+    if sum(counts) != proj.shape[3]:
+        raise ValueError(f"`points_per_level` sums to {sum(counts)}, but `proj` has S = {proj.shape[3]} samples per head.")
+    if reference_points.dim() != 3 or reference_points.shape[-1] not in (2, 4):
+        raise ValueError("`reference_points` should be [B,N,2] or [B,N,4] (last dim either 2 or 4), but got "
+                         f"{tuple(reference_points.shape)}.")
+    if tuple(reference_points.shape[:2]) != tuple(proj.shape[:2]):
+        raise ValueError(f"inconsistent shapes: proj {tuple(proj.shape)}, reference_points {tuple(reference_points.shape)}")
+    return counts
+
+
+def ragged_module_sampling_inputs(proj: torch.Tensor, img_shapes: torch.Tensor, reference_points: torch.Tensor, counts):
+    """The module's prologue for per-level point counts in plain PyTorch (differentiable): raw projection
+    ``[B, N, H, S, 3]`` = (x offset, y offset, attention logit) per sample, ``S = sum(counts)``, level-major ->
+    ``(sampling_points [B, N, H, S, 2], attention_weights [B, N, H, S])``.
+
+    * weights: softmax of the logits over all ``S`` samples of a ``(b, n, h)`` unit;
+    * 2-d reference points: ``ref + (ox / img_shapes[l][0], oy / img_shapes[l][1])`` — the stored (h, w) order, exactly
+      as :func:`msda_triton_amd.functional.module_sampling_inputs` keeps it;
+    * 4-d: ``ref_xy + (ox, oy) * ref_wh / (2 * P_l)`` with the count of the sample's own level (D-FINE's
+      ``offset * num_points_scale * ref_wh * offset_scale``, ``num_points_scale = 1 / P_l``, ``offset_scale = 0.5``).
+
+    Equal counts are the uniform prologue on a view."""
+    counts = check_proj_points_per_level(img_shapes, proj, reference_points, counts)
+    B, N, H, S, _ = proj.shape
+    L = len(counts)
+    if all(p == counts[0] for p in counts):
+        pts, att = F.module_sampling_inputs(proj.reshape(B, N, H, L, counts[0], 3), img_shapes, reference_points)
+        return pts.reshape(B, N, H, S, 2), att.reshape(B, N, H, S)
+    offsets, logits = proj[..., :2], proj[..., 2]
+    attention_weights = logits.softmax(dim=-1)
+    level = torch.tensor([l for l, p in enumerate(counts) for _ in range(p)], dtype=torch.long, device=img_shapes.device)
+    ref = reference_points[:, :, None, None, :]
+    if reference_points.shape[-1] == 2:
+        sampling_points = ref + offsets / img_shapes[level].to(proj.device)
+    else:
+        two_p = torch.tensor([2 * p for p in counts for _ in range(p)], dtype=proj.dtype, device=proj.device)
+        sampling_points = ref[..., :2] + offsets * ref[..., 2:] / two_p[:, None]
+    return sampling_points, attention_weights
+
+
+def fused_ragged_limits_ok(D: int, elem_size: int, counts) -> bool:
+    """Do the fused kernels take these counts (all S samples of a unit in one LDS pass, at most 8 levels)?"""
+    key = (D, elem_size)
+    limit = F._FUSED_LP_LIMIT.get(key)
+    if limit is None:
+        limit = F._FUSED_LP_LIMIT[key] = int(_lib.load().msda_fused_lp_limit(*key))
+    return sum(counts) <= limit and len(counts) <= 8
+
+
+def ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts) -> Optional[torch.Tensor]:
+    """Forward with the softmax and the sampling-point arithmetic done in the kernel prologue
+    (``msda_fwd_fused_ragged_<suffix>``).  None when the library declines (S too large for one pass, more than 8 levels)
+    or predates these entry points: the caller then takes the unfused route."""
+    if not _lib.has_fused_ragged():
+        return None
+    B, I, H, D = img.shape
+    B2, Q, H2, S, _ = proj.shape
+    if (B2, H2) != (B, H) or reference_points.shape[0] != B:
+        raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
+                         f"reference_points {tuple(reference_points.shape)}")
+    F._check_devices(img, img_shapes, proj, reference_points)
+    pad = F._padding_code(padding_mode)
+    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    shapes = F._shapes_i64(img_shapes)
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    fn = getattr(_lib.load(), f"msda_fwd_fused_ragged_{suf}")
+
+    def call():
+        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+                  B, I, H, D, Q, len(counts), _counts_array(counts), reference_points.shape[-1], pad,
+                  int(bool(align_corners)), vrow, F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_fwd_fused_ragged", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_fwd_fused_ragged_{suf}")
+    return out
+
+
+def ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
+                         need_img: bool = True, level_cells: int = 0, need_ref: bool = True):
+    """Backward of the module core with the prologue's chain rule done in the kernel
+    (``msda_bwd_fused_ragged_<suffix>``): ``(img_grad | None, proj_grad, reference_points_grad | None)``, or None when
+    the library declines (nothing was launched)."""
+    if not _lib.has_fused_ragged():
+        return None
+    B, I, H, D = img.shape
+    _, Q, _, S, _ = proj.shape
+    ref_dim = reference_points.shape[-1]
+    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
+    pad = F._padding_code(padding_mode)
+    cdt = proj.dtype
+    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
+    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and reference points fp32)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    out_grad = out_grad.contiguous()
+    if out_grad.dtype != cdt:
+        out_grad = out_grad.to(cdt)
+    shapes = F._shapes_i64(img_shapes)
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, ref_dim), dtype=reference_points.dtype, device=img.device)
+    lib = _lib.load()
+    fn = getattr(lib, f"msda_bwd_fused_ragged_{suf}")
+    arr = _counts_array(counts)
+    ws, ws_bytes = None, 0
+    level_cells = int(level_cells)
+    if need_img:  # (a frozen value pyramid needs no workspace at all)
+        ws_bytes = int(lib.msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, len(counts), arr,
+                                                                 4 if storage else proj.element_size(),
+                                                                 img.element_size(), level_cells, 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
+
+    def call():
+        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
+                  B, I, H, D, Q, len(counts), arr, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
+                  ws.data_ptr() if ws is not None else None, ws_bytes, F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_bwd_fused_ragged", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_bwd_fused_ragged_{suf}")
+    return g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None)
+
+
+class _HipFusedRaggedModuleCoreFunction(Function):
+    """value, raw projection [B, Q, H, S, 3], reference points -> attended values, the prologue and its chain rule inside
+    the HIP kernels.  When the library declines (or lacks the entry points) the prologue runs in PyTorch around the ragged
+    operator's kernels."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts, level_cells=0):
+        ctx.level_cells, ctx.counts = int(level_cells), counts
+        out = ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts)
+        ctx.fused = out is not None  # the backward has the same limits: do not ask twice
+        if out is None:
+            pts, att = ragged_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points, counts)
+            out = ragged_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners, counts).to(proj.dtype)
+        ctx.save_for_backward(img, img_shapes, proj, reference_points)
+        ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, out_grad):
+        img, img_shapes, proj, reference_points = ctx.saved_tensors
+        need_img, _, need_proj, need_ref = ctx.needs_input_grad[:4]
+        counts = ctx.counts
+        if ctx.fused and (need_proj or need_ref):
+            res = ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, ctx.padding_mode,
+                                       ctx.align_corners, counts, need_img, level_cells=ctx.level_cells, need_ref=need_ref)
+            if res is not None:
+                g_img, g_proj, g_ref = res
+                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None
+        with torch.enable_grad():
+            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
+            ref_ = reference_points.detach().requires_grad_(need_ref)
+            pts, att = ragged_module_sampling_inputs(proj_, img_shapes, ref_, counts)
+        need_sample = need_proj or need_ref
+        g_img, g_pts, g_att = ragged_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(),
+                                             ctx.padding_mode, ctx.align_corners, counts,
+                                             (need_img, need_sample, need_sample), ctx.level_cells)
+        g_proj = g_ref = None
+        if need_sample:
+            wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
+            grads = list(torch.autograd.grad([pts, att], wrt, [g_pts, g_att], allow_unused=True))
+            if need_proj:
+                g_proj = grads.pop(0).to(proj.dtype)
+            if need_ref:
+                g_ref = grads.pop(0)
+        return g_img, None, g_proj, g_ref, None, None, None, None
+
+
+def fused_ragged_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, points_per_level,
+                             level_shapes=None) -> torch.Tensor:
+    """``fused_module_core(..., points_per_level=...)``: ``proj`` is ``[B, Q, H, S, 3]``.  Routing mirrors the uniform
+    function: equal counts -> the uniform call on a view; host tensors -> the composition; GPU -> the fused kernels."""
+    counts = check_proj_points_per_level(img_shapes, proj, reference_points, points_per_level)
+    B, Q, H, S, _ = proj.shape
+    L = len(counts)
+    if all(p == counts[0] for p in counts):
+        return F.fused_module_core(img, img_shapes, proj.reshape(B, Q, H, L, counts[0], 3), reference_points, padding_mode,
+                                   align_corners, level_shapes)
+    level_cells = F.level_cells_of(level_shapes, L, img.shape[1])
+    on_gpu = img.device.type == "cuda"
+    if on_gpu and img_shapes.device != img.device:
+        img_shapes = img_shapes.to(img.device)  # (a handful of integers: follow `img`, as the uniform function does)
+    if on_gpu:
+        F._check_devices(img, proj, reference_points)
+    floating = img.is_floating_point() and proj.is_floating_point() and reference_points.is_floating_point()
+    if on_gpu and floating and not torch.compiler.is_compiling():
+        same = F.dtypes_supported(img.dtype, proj.dtype) and reference_points.dtype == proj.dtype
+        if F._autocast_on() or F.fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype) or same:
+            pad = F._padding_code(padding_mode)
+            ext = _ext.load()
+            if same and ext is not None and hasattr(ext, "msda_fused_ragged") and F.KernelTimer.active is None and \
+                    not F._autocast_on() and _lib.has_fused_ragged() and img.dim() == 4 and \
+                    (img.shape[0], img.shape[2]) == (B, H) and fused_ragged_limits_ok(img.shape[3], proj.element_size(), counts):
+                # the C++ autograd node: decoder-sized calls spend more host time than device time
+                return ext.msda_fused_ragged(img, F._shapes_i64(img_shapes), proj, reference_points, pad,
+                                             bool(align_corners), level_cells, list(counts))
+            return _HipFusedRaggedModuleCoreFunction.apply(img, img_shapes, proj, reference_points, padding_mode,
+                                                           bool(align_corners), counts, level_cells)
+    # host tensors, tracing (the ragged operator's registered custom ops) and everything the checks above did not take
+    pts, att = ragged_module_sampling_inputs(proj, img_shapes, reference_points, counts)
+    return F.multiscale_deformable_attention(img, img_shapes, pts, att, padding_mode, align_corners,
+                                             level_shapes=level_shapes, points_per_level=counts)
