@@ -1,0 +1,361 @@
+"""Inputs on which the operator is EXACT, so DESIGN.md §5 (float coordinates, weights and accumulation for every
+storage type, one rounding on store) can be held with no tolerance.  A helper module, not a conftest.
+
+Every input is a short dyadic number: sampling points are odd multiples of 2^-loc_bits, attention weights multiples of
+2^-attn_bits in [0, 1], `value` and `grad_out` small integers (or multiples of 2^-value_bits / 2^-grad_bits).  Every
+intermediate quantity of a correct evaluation is then a multiple of 2^-f (f: `fractional_bits` below) bounded by the
+condition sum S of absolute values, i.e. it has at most f + ceil(log2 S) significant bits.  While that `budget` stays
+within float32's 24 bits nothing rounds — in any summation order, with or without FMA — and the fp64 oracle IS the
+float32 result.  The only rounding left is the store to a 16-bit type, which `expected` applies once (torch's CPU
+conversion: round to nearest even).
+
+`checked_reference(name, pm, ac)` is what the GPU tests compare against: it asserts the precondition (budget <= 24 for
+every tensor, float32 oracle == float64 oracle bitwise, no sample on an integer pixel coordinate) before it hands out
+the cached fp64 reference.  A case that fails it is a broken fixture: nothing is dropped at run time."""
+import functools
+import math
+import zlib
+
+import numpy as np
+import torch
+
+MODES = [("zeros", False), ("zeros", True), ("border", False), ("border", True)]
+TENSORS = ("out", "grad_value", "grad_loc", "grad_attn")
+F32_BITS = 24
+F32, F64, BF16, F16 = torch.float32, torch.float64, torch.bfloat16, torch.float16
+
+
+# ----------------------------------------------------------------------------------------- the generator
+def _odd_multiples(rng, shape, bits, lo, hi):
+    scale = 2 ** bits
+    kmin, kmax = math.ceil((lo * scale - 1) / 2), math.floor((hi * scale - 1) / 2)
+    return (2 * rng.integers(kmin, kmax + 1, size=shape) + 1) / scale
+
+
+def _grid(rng, shape, vmax, bits):
+    scale = 2 ** bits
+    return rng.integers(-vmax * scale, vmax * scale + 1, size=shape) / scale
+
+
+def exact_case(rng, B, Q, H, D, levels, P, *, loc_bits=7, attn_bits=2, vmax=3, gmax=3, lo=-0.3, hi=1.3, value_bits=0,
+               grad_bits=0, dtype=np.float64):
+    """The usual dict (value, shapes, loc, attn, grad_out) plus the generator's bit counts under "bits".
+
+    `P` an int: loc [B, Q, H, L, P, 2], attn [B, Q, H, L, P].  `P` a list of per-level counts (the ragged
+    `points_per_level` layout, also used by the discrete mode): loc [B, Q, H, S, 2], attn [B, Q, H, S] and "counts"."""
+    I = sum(h * w for h, w in levels)  # noqa: E741
+    L = len(levels)
+    counts = None if isinstance(P, int) else [int(p) for p in P]
+    pts = (L, P) if counts is None else (sum(counts),)
+    attn = rng.integers(0, 2 ** attn_bits + 1, size=(B, Q, H) + pts) / 2 ** attn_bits
+    attn.reshape(-1)[0] = 1.0   # 0 and 1 are always there, however small the tensor
+    attn.reshape(-1)[-1] = 0.0
+    c = dict(
+        value=_grid(rng, (B, I, H, D), vmax, value_bits).astype(dtype),
+        shapes=np.asarray(levels, dtype=np.int64),
+        loc=_odd_multiples(rng, (B, Q, H) + pts + (2,), loc_bits, lo, hi).astype(dtype),
+        attn=attn.astype(dtype),
+        grad_out=_grid(rng, (B, Q, H, D), gmax, grad_bits).astype(dtype),
+        bits=dict(loc=loc_bits, attn=attn_bits, value=value_bits, grad=grad_bits),
+    )
+    if counts is not None:
+        c["counts"] = counts
+    return c
+
+
+def flood_case(rng, B, Q, H, D, levels, P, coords, **kw):
+    """`exact_case` with every sample of level l moved into ONE bilinear cell: x and y drawn from coords[l] = (xs, ys),
+    odd multiples of 2^-loc_bits that land in the same cell under both align modes."""
+    c = exact_case(rng, B, Q, H, D, levels, P, **kw)
+    for lvl, (xs, ys) in enumerate(coords):
+        c["loc"][:, :, :, lvl, :, 0] = rng.choice(np.asarray(xs, dtype=np.float64), size=(B, Q, H, P))
+        c["loc"][:, :, :, lvl, :, 1] = rng.choice(np.asarray(ys, dtype=np.float64), size=(B, Q, H, P))
+    return c
+
+
+# ----------------------------------------------------------------------------------------- the cases the GPU file uses
+PYRAMID = [(16, 16), (8, 8), (4, 4), (2, 2)]
+# name: (kind, (B, Q, H, D, levels, P), generator keywords, 16-bit storage types the GPU file runs the case in)
+CASES = {
+    # the shape matrix (tests/test_gpu_parity.py: SHAPE_MATRIX), L * P <= 16
+    # (points in [0, 1]: pixel coordinates still reach half a pixel beyond the first / last centre at every level, so the
+    #  masked and clamped corners are there; with +-0.3 border padding zeroes so many location gradients of this
+    #  power-of-two pyramid that under 5 % of fp16 grad_loc would round.  lds_q200 keeps +-0.3 on the same pyramid.)
+    "d32_vec_g8": ("bilinear", (2, 70, 8, 32, PYRAMID, 4), dict(attn_bits=3, lo=0.0, hi=1.0), (F16, BF16)),
+    "d64_vec_g16": ("bilinear", (1, 33, 4, 64, [(9, 7), (5, 4)], 3), dict(gmax=1, attn_bits=3), (F16, BF16)),
+    "d8_vec_g4": ("bilinear", (2, 19, 3, 8, [(7, 9), (3, 4)], 5), {}, (F16, BF16)),
+    "d5_scalar": ("bilinear", (2, 13, 3, 5, [(6, 4), (3, 2), (2, 5)], 3), dict(attn_bits=4), (F16, BF16)),
+    "d1": ("bilinear", (1, 23, 2, 1, [(5, 6), (2, 3)], 3), dict(vmax=7, gmax=7, attn_bits=4), (F16, BF16)),
+    "one_query": ("bilinear", (1, 1, 1, 32, [(4, 4), (3, 5)], 3), dict(vmax=5, gmax=5, attn_bits=3), (F16, BF16)),
+    "many_levels": ("bilinear", (1, 6, 2, 8, [(7, 6), (3, 3), (5, 3), (1, 1), (3, 5), (2, 3), (5, 1), (1, 5)], 2),
+                    dict(attn_bits=4),
+                    (F16, BF16)),
+    # forced kernel variants
+    "lds_q200": ("bilinear", (2, 200, 4, 32, PYRAMID, 4), {}, (BF16,)),
+    "b4_passes": ("bilinear", (4, 40, 4, 32, [(9, 7), (5, 4)], 4), {}, (BF16,)),
+    "unaligned": ("bilinear", (1, 9, 2, 32, [(4, 4), (3, 2)], 2), {}, (BF16,)),
+    # thousands of samples in one cell per level (level 0: cell (2, 2) of 6 x 7, level 1: cell (1, 1) of 4 x 4, under
+    # both align modes); sizes chosen so that the weights keep more than 6 fractional bits in every mode
+    # (vmax = gmax = 3, not 1: with +-1 values fewer than 5 % of `out` need rounding in bf16; the budget is 19 bits)
+    "flood": ("flood", (2, 1024, 2, 32, [(6, 7), (4, 4)], 2),
+              dict(loc_bits=4, attn_bits=1, vmax=3, gmax=3,
+                   coords=[((7 / 16,), (7 / 16, 9 / 16)), ((7 / 16, 9 / 16),) * 2]), (BF16,)),
+    # per-level point counts
+    "ragged_363": ("bilinear", (2, 37, 2, 32, [(6, 5), (3, 4), (2, 2)], [3, 6, 3]), {}, (BF16,)),
+    "ragged_125": ("bilinear", (2, 37, 2, 32, [(6, 5), (3, 4), (2, 2)], [1, 2, 5]), {}, (BF16,)),
+    # discrete sampling: no bilinear weights, so value / grad_out carry the fractional bits that make the store round
+    "discrete_363": ("discrete", (2, 37, 2, 32, [(8, 8), (4, 4), (2, 2)], [3, 6, 3]),
+                     dict(attn_bits=5, value_bits=3, grad_bits=3), (BF16,)),
+    "discrete_sorted": ("discrete", (1, 1200, 2, 32, [(32, 32), (16, 16), (8, 8)], [2, 4, 2]),
+                        dict(attn_bits=5, value_bits=3, grad_bits=3, loc_bits=6), (BF16,)),
+}
+BILINEAR = [n for n, c in CASES.items() if c[0] != "discrete"]
+DISCRETE = [n for n, c in CASES.items() if c[0] == "discrete"]
+SHAPE_MATRIX = ["d32_vec_g8", "d64_vec_g16", "d8_vec_g4", "d5_scalar", "d1", "one_query", "many_levels"]
+
+
+@functools.lru_cache(maxsize=None)
+def get_case(name):
+    """The case's fp64 inputs (cached; treat as read-only)."""
+    kind, dims, kw, _ = CASES[name]
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    c = flood_case(rng, *dims, **kw) if kind == "flood" else exact_case(rng, *dims, **kw)
+    for v in c.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return c
+
+
+def storage_types(name):
+    return CASES[name][3]
+
+
+# ----------------------------------------------------------------------------------------- ragged layout <-> dense
+def dense(c):
+    """A ragged case zero-padded to max(P_l) points per level (weight 0, a location off the pixel grid); a uniform case
+    as it is."""
+    if "counts" not in c:
+        return c
+    counts, lb = c["counts"], c["bits"]["loc"]
+    B, Q, H, _, _ = c["loc"].shape
+    L, Pm = len(counts), max(counts)
+    loc = np.full((B, Q, H, L, Pm, 2), (2 ** (lb - 1) + 1) / 2 ** lb, dtype=c["loc"].dtype)
+    attn = np.zeros((B, Q, H, L, Pm), dtype=c["attn"].dtype)
+    s0 = 0
+    for lvl, p in enumerate(counts):
+        loc[:, :, :, lvl, :p] = c["loc"][:, :, :, s0:s0 + p]
+        attn[:, :, :, lvl, :p] = c["attn"][:, :, :, s0:s0 + p]
+        s0 += p
+    return dict(c, loc=loc, attn=attn)
+
+
+def _unpad(t, counts):
+    return np.concatenate([t[:, :, :, lvl, :p] for lvl, p in enumerate(counts)], axis=3)
+
+
+def _oracle_all(oracle, c, pm, ac, dtype):
+    d = dense(c)
+    v, l, a, g = (np.asarray(d[k], dtype=dtype) for k in ("value", "loc", "attn", "grad_out"))
+    out = oracle.forward(v, d["shapes"], l, a, pm, ac)
+    gv, gl, ga = oracle.backward(g, v, d["shapes"], l, a, pm, ac)
+    if "counts" in c:
+        gl, ga = _unpad(gl, c["counts"]), _unpad(ga, c["counts"])
+    return dict(out=out, grad_value=gv, grad_loc=gl, grad_attn=ga)
+
+
+def _oracle():
+    from oracle import msda_oracle
+    msda_oracle.build()
+    return msda_oracle
+
+
+# ----------------------------------------------------------------------------------------- discrete: reference
+def _discrete_all(c, fn, dtype):
+    """out / grad_value / grad_attn of `fn(value, levels, loc, attn, counts)` (differentiable in value and attn)."""
+    v = torch.from_numpy(np.array(c["value"])).to(dtype).requires_grad_(True)
+    a = torch.from_numpy(np.array(c["attn"])).to(dtype).requires_grad_(True)
+    loc = torch.from_numpy(np.array(c["loc"])).to(dtype)
+    out = fn(v, [tuple(s) for s in c["shapes"].tolist()], loc, a, c["counts"])
+    out.backward(torch.from_numpy(np.array(c["grad_out"])).to(out.dtype))
+    return dict(out=out.detach().numpy(), grad_value=v.grad.numpy(), grad_attn=a.grad.numpy())
+
+
+def _ref_discrete(value, levels, loc, attn, counts):
+    from test_discrete_sampling import ref_discrete  # that file's own fp64 index formulation
+    return ref_discrete(value, levels, loc, attn, counts)
+
+
+def _index_discrete(value, levels, loc, attn, counts):
+    """This module's own index formulation, every operation in the inputs' dtype (float32 for the precondition): sample
+    by sample, out += attn * value[pixel]."""
+    B, _, H, D = value.shape
+    bi, hi = torch.arange(B).reshape(B, 1, 1), torch.arange(H).reshape(1, 1, H)
+    out = torch.zeros(B, loc.shape[1], H, D, dtype=value.dtype)
+    start = s0 = 0
+    for (h, w), n in zip(levels, counts):
+        for s in range(s0, s0 + n):
+            ix = torch.clamp(torch.trunc(loc[..., s, 0] * w + 0.5), 0, w - 1).to(torch.int64)
+            iy = torch.clamp(torch.trunc(loc[..., s, 1] * h + 0.5), 0, h - 1).to(torch.int64)
+            out = out + attn[..., s, None] * value[bi, start + iy * w + ix, hi]
+        start += h * w
+        s0 += n
+    return out
+
+
+# ----------------------------------------------------------------------------------------- budget and precondition
+def fractional_bits(bits):
+    lb, ab, vb, gb = bits["loc"], bits["attn"], bits["value"], bits["grad"]
+    return dict(out=ab + 2 * lb + vb, grad_value=ab + 2 * lb + gb, grad_attn=2 * lb + vb + gb, grad_loc=ab + lb + vb + gb)
+
+
+def _magnitude_bits(s):
+    s = float(np.max(s)) if np.size(s) else 0.0
+    return max(0, math.ceil(math.log2(s))) if s > 0 else 0
+
+
+def condition_sums(c, pm, ac):
+    """The largest sum of absolute values behind an element of each result (bilinear cases)."""
+    absd = dict(c, value=np.abs(c["value"]), attn=np.abs(c["attn"]), grad_out=np.abs(c["grad_out"]))
+    r = _oracle_all(_oracle(), absd, pm, ac, np.float64)  # the bilinear weights are >= 0: these ARE the condition sums
+    d = dense(c)
+    size = d["shapes"].max(axis=1).astype(np.float64).reshape(1, 1, 1, -1, 1)
+    g1 = np.abs(d["grad_out"]).sum(-1)[..., None, None]
+    # grad_loc: max(h, w) * |a| * sum_d |g_d| * (4 corners) * max |v|  (an upper bound of the sum the issue names)
+    gl = size * np.abs(d["attn"]) * g1 * 4.0 * float(np.abs(c["value"]).max())
+    return dict(out=float(r["out"].max()), grad_value=float(r["grad_value"].max()), grad_attn=float(r["grad_attn"].max()),
+                grad_loc=float(gl.max()))
+
+
+def budget(c, pm, ac):
+    """Significant bits each result needs, for any evaluation order: fractional bits + ceil(log2(condition sum))."""
+    frac = fractional_bits(c["bits"])
+    return {k: frac[k] + _magnitude_bits(s) for k, s in condition_sums(c, pm, ac).items()}
+
+
+def pixel_coordinates(c, ac):
+    """fp64 pixel-space coordinates of every sample of the (dense) case, [..., L, P, 2]."""
+    d = dense(c)
+    size = np.stack([d["shapes"][:, 1], d["shapes"][:, 0]], -1).astype(np.float64).reshape(1, 1, 1, -1, 1, 2)
+    return d["loc"] * (size - 1) if ac else d["loc"] * size - 0.5
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, pm="border", ac=False):
+    """The fp64 reference of a case (cached): the CPU oracle, or test_discrete_sampling.ref_discrete."""
+    c = get_case(name)
+    if CASES[name][0] == "discrete":
+        return _discrete_all(c, _ref_discrete, F64)
+    return _oracle_all(_oracle(), c, pm, ac, np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def precondition(name, pm="border", ac=False):
+    """Asserts that the case is exact in float32; returns its budget."""
+    c = get_case(name)
+    ref = reference(name, pm, ac)
+    if CASES[name][0] == "discrete":
+        absd = dict(c, value=np.abs(c["value"]), attn=np.abs(c["attn"]), grad_out=np.abs(c["grad_out"]))
+        sums = _discrete_all(absd, _ref_discrete, F64)
+        b = c["bits"]
+        frac = dict(out=b["attn"] + b["value"], grad_value=b["attn"] + b["grad"], grad_attn=b["value"] + b["grad"])
+        bud = {k: frac[k] + _magnitude_bits(sums[k]) for k in frac}
+        f32 = _discrete_all(c, _index_discrete, F32)  # evaluated in float32, independent of the package
+    else:
+        # no sample on an integer pixel coordinate, where grad_loc is discontinuous; an axis of ONE pixel under
+        # align_corners is no exception to the rule but outside it: its coordinate is x * 0, zero in any arithmetic
+        pix = pixel_coordinates(c, ac)
+        wh = np.stack([c["shapes"][:, 1], c["shapes"][:, 0]], -1).reshape(1, 1, 1, -1, 1, 2)
+        on_grid = (pix == np.round(pix)) & ~((wh == 1) & bool(ac))
+        assert not on_grid.any(), f"{name}: a sample sits on an integer pixel coordinate (grad_loc kink)"
+        bud = budget(c, pm, ac)
+        f32 = _oracle_all(_oracle(), c, pm, ac, np.float32)
+    assert max(bud.values()) <= F32_BITS, f"{name} {pm} {ac}: budget {bud} exceeds float32's {F32_BITS} bits"
+    for k, r in ref.items():
+        assert f32[k].dtype == np.float32 and np.array_equal(f32[k].astype(np.float64), r), \
+            f"{name} {pm} {ac}: the float32 and float64 references differ in {k}"
+    return bud
+
+
+def checked_reference(name, pm="border", ac=False):
+    precondition(name, pm, ac)
+    return reference(name, pm, ac)
+
+
+def expected(ref64, torch_dtype):
+    """ref64 -> float32 (exact, by the precondition) -> the storage type, rounded to nearest even ONCE."""
+    t = torch.from_numpy(np.array(ref64))
+    if torch_dtype == F64:
+        return t
+    f32 = t.to(F32)
+    assert torch.equal(f32.double(), t), "the reference is not a float32 number: the precondition was not checked"
+    return f32.to(torch_dtype)
+
+
+# ----------------------------------------------------------------------------------------- emulated wrong kernels (CPU)
+def truncate(t32, dtype):
+    """float32 -> 16-bit storage by TRUNCATION (toward zero) instead of round-to-nearest-even."""
+    t32 = t32.to(F32).contiguous()
+    if dtype == BF16:
+        return (t32.view(torch.int32) & -65536).view(F32).to(BF16)
+    r = t32.to(dtype)
+    over = r.float().abs() > t32.abs()
+    toward_zero = (r.view(torch.int16) - 1).view(dtype)  # sign-magnitude: one step smaller in magnitude
+    return torch.where(over, toward_zero, r)
+
+
+def taps(c, pm, ac):
+    """The oracle's bilinear taps in numpy fp64 for the (dense) case: (index [4][B, Q, H, L, P] into the pyramid, mask
+    [4], weight [4]), corners ordered 00, 01, 10, 11 (y, x)."""
+    d = dense(c)
+    pix = pixel_coordinates(c, ac)
+    h = d["shapes"][:, 0].reshape(1, 1, 1, -1, 1)
+    w = d["shapes"][:, 1].reshape(1, 1, 1, -1, 1)
+    start = (np.cumsum(d["shapes"][:, 0] * d["shapes"][:, 1]) - d["shapes"][:, 0] * d["shapes"][:, 1]).reshape(1, 1, 1, -1, 1)
+    x0, y0 = np.floor(pix[..., 0]), np.floor(pix[..., 1])
+    dx, dy = pix[..., 0] - x0, pix[..., 1] - y0
+    idx, mask, wgt = [], [], []
+    for oy, ox in ((0, 0), (0, 1), (1, 0), (1, 1)):
+        x, y = x0 + ox, y0 + oy
+        ok = (x >= 0) & (x <= w - 1) & (y >= 0) & (y <= h - 1) if pm == "zeros" else np.ones(x.shape, bool)
+        xc, yc = np.clip(x, 0, w - 1).astype(np.int64), np.clip(y, 0, h - 1).astype(np.int64)
+        idx.append(start + yc * w + xc)
+        mask.append(ok)
+        wgt.append((dy if oy else 1 - dy) * (dx if ox else 1 - dx))
+    return idx, mask, wgt
+
+
+def contributions(c, pm, ac, weight_fn=None, drop=None):
+    """attn * bilinear sample per (b, q, h, l, p), fp64 [B, Q, H, L, P, D]; the forward sums them over (l, p).
+    weight_fn: applied to each corner weight (a mutant's quantisation); drop = (corner, flat sample index): that corner
+    of that sample contributes nothing."""
+    d = dense(c)
+    idx, mask, wgt = taps(c, pm, ac)
+    B, _, H, D = d["value"].shape
+    bi, hi = np.arange(B).reshape(B, 1, 1, 1, 1), np.arange(H).reshape(1, 1, H, 1, 1)
+    total = 0.0
+    for k in range(4):
+        wk = wgt[k] if weight_fn is None else weight_fn(wgt[k])
+        wk = np.where(mask[k], wk, 0.0)
+        if drop is not None and drop[0] == k:
+            wk = wk.copy()
+            wk.reshape(-1)[drop[1]] = 0.0
+        total = total + wk[..., None] * d["value"][bi, idx[k], hi]
+    return d["attn"][..., None] * total
+
+
+def smallest_corner_of_one_sample(c, pm, ac):
+    """(corner, flat sample index): among the samples' smallest-weight corners (unmasked, weight > 0), the one that
+    carries most — largest attention weight x corner weight x |value| — so that dropping it is as visible as dropping
+    ONE smallest corner can be; chosen from the inputs alone."""
+    d = dense(c)
+    idx, mask, wgt = taps(c, pm, ac)
+    B, _, H, D = d["value"].shape
+    bi, hi = np.arange(B).reshape(B, 1, 1, 1, 1), np.arange(H).reshape(1, 1, H, 1, 1)
+    w4 = np.stack([np.where(m & (w > 0), w, np.inf) for m, w in zip(mask, wgt)])
+    k = np.argmin(w4, axis=0)
+    wmin = np.take_along_axis(w4, k[None], 0)[0]
+    rows = np.stack([np.abs(d["value"][bi, i, hi]).max(-1) for i in idx])
+    carried = np.where(np.isfinite(wmin), wmin, 0.0) * np.take_along_axis(rows, k[None], 0)[0] * np.abs(d["attn"])
+    flat = int(np.argmax(carried.reshape(-1)))
+    assert carried.reshape(-1)[flat] > 0, "no sample whose smallest corner matters: the fixture has no teeth"
+    return int(k.reshape(-1)[flat]), flat
