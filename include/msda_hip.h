@@ -89,7 +89,7 @@ extern "C" {
 
 #define MSDA_ERR_BAD_ARG (-1)      /* null pointer, negative size, unknown padding mode */
 #define MSDA_ERR_TOO_MANY_LEVELS (-2) /* L > MSDA_MAX_LEVELS */
-#define MSDA_ERR_TOO_LARGE (-3)    /* a per-batch-element extent does not fit the 32-bit plane offsets: I*H*D*sizeof, Q*H*D*sizeof or Q*H*L*P*2 >= 2^31, or I, Q >= 2^24 */
+#define MSDA_ERR_TOO_LARGE (-3)    /* a per-batch-element extent does not fit the 32-bit plane offsets: I*H*D*sizeof, Q*H*D*sizeof or Q*H*L*P*2 >= 2^31, or I, Q >= 2^24 (sizeof: of the sampling / arithmetic type, 4 for every f32_* suffix; the full list: DESIGN.md 2, "Size limits") */
 #define MSDA_ERR_MISALIGNED (-4)   /* a buffer is not aligned to its element size */
 #define MSDA_ERR_UNSUPPORTED (-5)  /* valid arguments this entry point cannot serve (use the unfused call) */
 
@@ -281,6 +281,8 @@ MSDA_DECLARE_FUSED_STORAGE(f32_sf16)
  * planes as fit are kept in those buffers and the workspace shrinks (c2 @ 10k: 180 -> 98 MB).  A call with such a
  * workspace but without grad_loc / grad_attn (or misaligned buffers) is rejected (MSDA_ERR_BAD_ARG); a larger workspace
  * is fine.
+ * Every workspace query answers 0 for sizes the call itself refuses with MSDA_ERR_TOO_LARGE and for sizes without a
+ * grad_value route (msda_bwd_supported == 0): there is nothing to size, and no product of such sizes is formed.
  */
 #define MSDA_WS_RECORDS_IN_GRADS 1
 /*

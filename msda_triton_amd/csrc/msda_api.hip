@@ -217,6 +217,8 @@ extern "C" int64_t msda_bwd_workspace_bytes(int64_t B, int64_t I, int64_t H, int
                                          ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), 0);
 }
 
+extern "C" int msda_fused_dims_refused_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t);
+
 extern "C" int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                                   int64_t P, int elem_size, int value_elem_size, int64_t max_level_cells,
                                                   int flags)
@@ -225,6 +227,7 @@ extern "C" int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t 
     // the derived sampling points + attention weights (3 elements per sample, rounded up to 256 bytes), then
     // the sorted pipeline's own workspace (msda_launch.hpp: fused_mat_bytes)
     (void)value_elem_size;
+    if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, P, elem_size, 0)) return 0;  // (a call of this size is refused)
     const int64_t mat = (B * Q * H * L * P * 3 * (int64_t)elem_size + 255) / 256 * 256;
     return mat + msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, P, elem_size, 0, 0, max_level_cells,
                                                ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), 0);

@@ -12,9 +12,13 @@ extern "C" __attribute__((visibility("hidden"))) int64_t msda_bwd_workspace_byte
     // P their maximum; 0: L * P)
     msda::Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
     d.S = S;
+    // dimensions the call itself refuses (MSDA_ERR_TOO_LARGE) have no workspace to size: 0, never a wrapped product
+    if (elem_size <= 0 || msda::common_limits_exceeded(d, elem_size)) return 0;
     const bool small = elem_size == 8 ? msda::small_path_chosen<double>(d) : msda::small_path_chosen<float>(d);
     const size_t acc = elem_size == 8 ? 8 : 4;
     if (small) return 0;
+    // ... and so have shapes without a grad_value route (MSDA_ERR_UNSUPPORTED; msda_bwd_supported)
+    if (!(elem_size == 8 ? msda::sorted_fits<double>(d) : msda::sorted_fits<float>(d))) return 0;
     // passes over the batch (MSDA_WS_PASSES): the workspace of ceil(B / passes) batch elements, used once per group
     if (passes > 1 && B > 1) B = (B + passes - 1) / passes;
     // records in the gradient buffers need every group's share of them 16-byte aligned (msda_launch.hpp)
@@ -26,6 +30,15 @@ extern "C" __attribute__((visibility("hidden"))) int64_t msda_bwd_workspace_byte
     const size_t vec = msda::sorted_ws_layout(B, I, H, D, Q, L, msda::samples(d), acc, (size_t)elem_size, true, rg, (size_t)value_elem_size).total;
     const size_t sca = msda::sorted_ws_layout(B, I, H, D, Q, L, msda::samples(d), acc, (size_t)elem_size, false, rg, (size_t)value_elem_size).total;
     return (int64_t)(vec > sca ? vec : sca);
+}
+
+// would a fused call with these sizes be refused for its size (the fused workspace queries then answer 0)
+extern "C" __attribute__((visibility("hidden"))) int msda_fused_dims_refused_impl(int64_t B, int64_t I, int64_t H, int64_t D,
+                                                                                int64_t Q, int64_t L, int64_t P, int elem_size, int64_t S)
+{
+    msda::Dims d{B, I, H, D, Q, L, P};
+    d.S = S;
+    return elem_size <= 0 || msda::common_limits_exceeded(d, elem_size) || msda::fused_limit_exceeded(d);
 }
 
 // can grad_value be produced for these sizes at all (include/msda_hip.h: msda_bwd_supported)
@@ -88,6 +101,7 @@ extern "C" int64_t msda_bwd_fused_ragged_workspace_bytes(int64_t B, int64_t I, i
     if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || elem_size <= 0 || msda::ragged_counts(points_per_level, L, pmax, S) != 0)
         return 0;
     (void)value_elem_size;
+    if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, pmax, elem_size, S)) return 0;
     const int64_t mat = (B * Q * H * S * 3 * (int64_t)elem_size + 255) / 256 * 256;
     return mat + msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, pmax, elem_size, 0, 0, max_level_cells,
                                                ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), S);

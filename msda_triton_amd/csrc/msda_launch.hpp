@@ -71,6 +71,19 @@ inline int64_t samples(const Dims &d) { return d.S > 0 ? d.S : d.L * d.P; }
 // ... or the process-wide promise (msda_set_option("level_cells", n)); 0: unknown
 inline int64_t level_cells_bound(const Dims &d) { return d.cells > 0 ? d.cells : (int64_t)option_level_cells(); }
 
+// The size limits behind the 32-bit plane offsets ("Size limits"); `es`: size of the arithmetic / sampling
+// type.  One definition for the entry points (check_common) and the workspace queries, which answer 0 where a call
+// would be refused.
+inline bool common_limits_exceeded(const Dims &d, int64_t es)
+{
+    const int64_t lim = (int64_t)1 << 31;
+    return d.I * d.H * d.D * es >= lim || d.B >= lim || d.Q >= lim || samples(d) >= (1 << 22) || d.B * d.H >= (1 << 28) ||
+           d.Q * d.H * samples(d) * 2 >= lim || d.Q * d.H * d.D * es >= lim || d.I >= (1 << 24) || d.Q >= (1 << 24) ||
+           d.H * samples(d) >= (1 << 24) || d.H * d.D * es >= (1 << 24);
+}
+// ... and of the fused entry points' projection [B, Q, H, S, 3]
+inline bool fused_limit_exceeded(const Dims &d) { return d.Q * d.H * samples(d) * 3 >= ((int64_t)1 << 31); }
+
 template <typename T>
 inline int check_common(const Dims &d, int padding_mode, const void *const *ptrs, int nptrs)
 {
@@ -86,10 +99,7 @@ inline int check_common(const Dims &d, int padding_mode, const void *const *ptrs
         set_error("L=%lld exceeds MSDA_MAX_LEVELS=%d", (long long)d.L, MSDA_MAX_LEVELS);
         return MSDA_ERR_TOO_MANY_LEVELS;
     }
-    const int64_t lim = (int64_t)1 << 31;
-    if (d.I * d.H * d.D * (int64_t)sizeof(T) >= lim || d.B >= lim || d.Q >= lim || samples(d) >= (1 << 22) ||
-        d.B * d.H >= (1 << 28) || d.Q * d.H * samples(d) * 2 >= lim || d.Q * d.H * d.D * (int64_t)sizeof(T) >= lim || d.I >= (1 << 24) ||
-        d.Q >= (1 << 24) || d.H * samples(d) >= (1 << 24) || d.H * d.D * (int64_t)sizeof(T) >= (1 << 24)) {
+    if (common_limits_exceeded(d, (int64_t)sizeof(T))) {
         set_error("tensor too large for 32-bit plane offsets (I*H*D*sizeof = %lld bytes)",
                   (long long)(d.I * d.H * d.D * (int64_t)sizeof(T)));
         return MSDA_ERR_TOO_LARGE;
@@ -850,7 +860,7 @@ int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, co
     const void *ptrs2[] = {value, shapes, proj, ref};
     rc = check_common<T>(d, padding_mode, ptrs2, 4);
     if (rc) return rc;
-    if (Q * H * samples(d) * 3 >= ((int64_t)1 << 31)) {
+    if (fused_limit_exceeded(d)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
@@ -1354,7 +1364,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
     const void *ptrs[] = {grad_out, value, shapes, proj, ref};
     rc = check_common<T>(d, padding_mode, ptrs, 5);
     if (rc) return rc;
-    if (Q * H * samples(d) * 3 >= ((int64_t)1 << 31)) {
+    if (fused_limit_exceeded(d)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
