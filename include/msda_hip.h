@@ -172,7 +172,17 @@ extern "C" {
                        void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
                        int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,\
                        int padding_mode, int align_corners, int64_t max_level_cells,                \
-                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);\
+    MSDA_API int msda_fwd_fused_levelref_##SUF(const void *value, const int64_t *shapes, const void *proj,\
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
+                       int align_corners, int64_t value_row_stride, void *stream);                  \
+    MSDA_API int msda_bwd_fused_levelref_##SUF(const void *grad_out, const void *value,             \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
+                       int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,   \
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * Per-level point counts (ABI 12, additive): msda_fwd_ragged_<dtype> / msda_bwd_ragged_<dtype> take the arguments of
@@ -205,6 +215,24 @@ extern "C" {
  * max_level_cells and MSDA_WS_PASSES(n) mean what they mean in the uniform fused calls; the workspace comes from
  * msda_bwd_fused_ragged_workspace_bytes, and grad_value runs the ragged operator's pipelines (bitwise reproducible while
  * max_l P_l <= 1024).
+ *
+ * The module's fused pair for PER-LEVEL REFERENCE POINTS — ADDITIONS WITHIN ABI 12, probed by symbol:
+ * msda_fwd_fused_levelref_<suffix> / msda_bwd_fused_levelref_<suffix>, the argument lists of msda_fwd_fused_<suffix> /
+ * msda_bwd_fused_<suffix> for the same eight suffixes.  They are the prologue of Hugging Face transformers' attention
+ * modules (Deformable-DETR, Grounding-DINO, the RT-DETR family), which differs from the reference module's in three ways:
+ *
+ *   ref        [B, Q, L, ref_dim]  a reference point per LEVEL (transformers multiplies them by each level's valid ratio)
+ *   ref_dim 2  point = ref_l + (ox / w_l, oy / h_l)                 — (x, y) by (width, height), not the stored (h, w) order
+ *   ref_dim 4  point = ref_l.xy + (ox, oy) / P * ref_l.wh * 0.5     — in this order, every operation rounded once
+ *   grad_ref_partial  [B, Q, H, L, ref_dim]  a partial per head AND level; the caller sums over the heads
+ *
+ * The weights are the softmax over the L * P logits of a (b, q, h) unit, as in the uniform pair.  Uniform point count P
+ * only.  The sampling point is formed by exactly the operations above (no fused multiply-add), so it is bit for bit what
+ * the same expression gives on the host, and the copy parked for grad_value names the cell the forward sampled.  The limits
+ * are the uniform pair's (L * P <= msda_fused_lp_limit(D, elem_size), else MSDA_ERR_UNSUPPORTED and nothing is launched;
+ * every size guard of msda_fwd_fused_ / msda_bwd_fused_<suffix>).  grad_value IS the uniform pipeline on the derived points:
+ * the workspace is the uniform pair's — msda_bwd_fused_workspace_bytes answers for these calls too, there is no query of
+ * their own — and value_row_stride, max_level_cells and MSDA_WS_PASSES(n) mean what they mean there.
  *
  * Discrete (nearest-pixel) sampling — ADDITIONS WITHIN ABI 12: no existing signature changes and MSDA_ABI_VERSION stays
  * 12, so a caller PROBES FOR THESE BY SYMBOL (dlsym / hasattr) instead of by version; a library built before them simply
@@ -266,7 +294,17 @@ MSDA_DECLARE(f32_vf16)
                        void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
                        int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,\
                        int padding_mode, int align_corners, int64_t max_level_cells,                \
-                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);\
+    MSDA_API int msda_fwd_fused_levelref_##SUF(const void *value, const int64_t *shapes, const void *proj,\
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
+                       int align_corners, int64_t value_row_stride, void *stream);                  \
+    MSDA_API int msda_bwd_fused_levelref_##SUF(const void *grad_out, const void *value,             \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
+                       int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,   \
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);
 MSDA_DECLARE_FUSED_STORAGE(f32_sbf16)
 MSDA_DECLARE_FUSED_STORAGE(f32_sf16)
 #undef MSDA_DECLARE_FUSED_STORAGE

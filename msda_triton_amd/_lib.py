@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = tuple(
     + ["msda_bwd_discrete_workspace_bytes", "msda_bwd_discrete_supported"]
     + [f"msda_{d}_fused_ragged_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
     + ["msda_bwd_fused_ragged_workspace_bytes"]
+    + [f"msda_{d}_fused_levelref_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
     + ["msda_abi_version", "msda_last_error", "msda_set_option", "msda_get_option", "msda_bwd_workspace_bytes",
        "msda_bwd_fused_workspace_bytes", "msda_bwd_supported", "msda_fused_lp_limit", "msda_profile_read",
        "msda_last_launch_info"]
@@ -151,6 +152,16 @@ def load():
                 gfr.argtypes = [vp] * 8 + [i64] * 6 + [vp, ci, ci, ci, i64, i64, vp, i64, vp]
             lib.msda_bwd_fused_ragged_workspace_bytes.restype = i64
             lib.msda_bwd_fused_ragged_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
+        # the module's fused pair for per-level reference points (transformers' prologue): additions within ABI 12 as
+        # well (has_fused_levelref); the argument lists of the uniform fused pair
+        if hasattr(lib, "msda_bwd_fused_levelref_f32"):
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                ffl = getattr(lib, f"msda_fwd_fused_levelref_{suf}")
+                ffl.restype = ci
+                ffl.argtypes = [vp] * 5 + [i64] * 7 + [ci, ci, ci, i64, vp]
+                gfl = getattr(lib, f"msda_bwd_fused_levelref_{suf}")
+                gfl.restype = ci
+                gfl.argtypes = [vp] * 8 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -184,6 +195,13 @@ def has_fused_ragged() -> bool:
     """Does the loaded library have the fused module pair for per-level point counts (msda_fwd_fused_ragged_<dtype> ...,
     additions within ABI 12, found by symbol)?  Without them the caller composes the prologue around the ragged operator."""
     return hasattr(load(), "msda_bwd_fused_ragged_workspace_bytes")
+
+
+def has_fused_levelref() -> bool:
+    """Does the loaded library have the fused module pair for per-level reference points
+    (msda_fwd_fused_levelref_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller composes
+    transformers' prologue around the plain operator."""
+    return hasattr(load(), "msda_bwd_fused_levelref_f32")
 
 
 def check(rc: int, what: str) -> None:

@@ -176,6 +176,42 @@ template <typename A> __device__ __forceinline__ int discrete_pixel(A x, int n)
     return (int)fmin_t(fmax_t(t, (A)0), (A)(n - 1));
 }
 
+// ---- per-level reference points (msda_*_fused_levelref_<dtype>): the fused module kernels for Hugging Face's attention
+// modules (Deformable-DETR, Grounding-DINO, the RT-DETR family) ----
+// `ref` is [B, Q, L, ref_dim] — a point per LEVEL, already scaled by the level's valid ratio — and the points follow
+// transformers' rule, not the reference module's:
+//   2-d   x = ref_x + ox / w_l              y = ref_y + oy / h_l        (the reference divides by (h_l, w_l))
+//   4-d   x = ref_x + ox / P * ref_w * 0.5  y = ref_y + oy / P * ref_h * 0.5
+// and the backward leaves a grad_reference_points partial per (b, q, head, LEVEL).  A kernarg type of its own with
+// nothing behind Params: the uniform and the per-level-count instantiations keep their types and their code, and the
+// three rules hang on overloads / `if constexpr (kLevelRef<PP>)`.  Uniform point count only.
+struct LevelRefParams : Params {};
+template <typename PP> constexpr bool kLevelRef = std::is_base_of<LevelRefParams, PP>::value;
+
+// Elements of `ref` per query, and the reference point of (query fq, level l) behind the batch element's base.
+__device__ __forceinline__ int ref_row_elems(const Params &p) { return p.ref_dim; }
+__device__ __forceinline__ int ref_row_elems(const LevelRefParams &p) { return p.L * p.ref_dim; }
+template <typename T> __device__ __forceinline__ const T *ref_of(const Params &p, const T *refp, int fq, int)
+{
+    return refp + (size_t)fq * p.ref_dim;
+}
+template <typename T> __device__ __forceinline__ const T *ref_of(const LevelRefParams &p, const T *refp, int fq, int l)
+{
+    return refp + ((size_t)fq * p.L + l) * p.ref_dim;
+}
+// The 4-d point from the offset already divided by P: two rounded multiplies, then a rounded add — transformers'
+// `ref + offsets / P * size * 0.5`, operation by operation.  The translation units are built with -ffp-contract=fast;
+// the product passes through an empty asm statement (as discrete_pixel's) so that the add cannot take it as an FMA
+// operand: the point is bit for bit the host's, and grad_value's parked copy of it (the backward's phase 3 calls this
+// again on the same operands) names the cell the forward sampled.
+template <typename A> __device__ __forceinline__ A levelref_box_point(A r, A q, A size)
+{
+    A t = q * size;
+    t = t * (A)0.5;
+    asm("" : "+v"(t));
+    return r + t;
+}
+
 template <typename A> struct alignas(16) Rec4 {
     A v[4];
 };
@@ -474,7 +510,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
         proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;
         attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
     };
-    const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * p.ref_dim : nullptr;
+    const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * ref_row_elems(p) : nullptr;
     const int HLP = p.H * p.LP;
     const float inv_P = 1.0f / (float)p.P;
     const int nchan_chunks = (p.D + G * VEC - 1) / (G * VEC);
@@ -607,10 +643,18 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                             const int sidx = imul24(fq, HLP) + sl;
                             const A ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
                             const A lg = SR::to_acc(proj3[3 * sidx + 2]);
-                            const T *r = refp + (size_t)fq * p.ref_dim;
+                            const T *r = ref_of(p, refp, fq, l);
                             Rec4<A> w;
                             w.v[0] = lg;
-                            if (p.ref_dim == 2) {
+                            if constexpr (kLevelRef<PP>) {  // transformers' rule on the level's own reference point
+                                if (p.ref_dim == 2) {
+                                    w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->w[l];
+                                    w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->h[l];
+                                } else {
+                                    w.v[1] = levelref_box_point<A>(TR::to_acc(r[0]), ox / (A)p.P, TR::to_acc(r[2]));
+                                    w.v[2] = levelref_box_point<A>(TR::to_acc(r[1]), oy / (A)p.P, TR::to_acc(r[3]));
+                                }
+                            } else if (p.ref_dim == 2) {
                                 // NB: (x, y) offsets are divided by img_shapes in its stored (h, w) order (frontend.py:275)
                                 w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->h[l];
                                 w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->w[l];
@@ -982,7 +1026,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
         proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;
         attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
     };
-    const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * p.ref_dim : nullptr;
+    const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * ref_row_elems(p) : nullptr;
     A *w_aux = lds.s_aux + wave * UPW * scp * 3;  // FUSED: [slot] = a, [UPW*scp + slot] = ox, [2*UPW*scp + slot] = oy
     A *w_a = w_aux, *w_ox = w_aux + UPW * scp, *w_oy = w_aux + 2 * UPW * scp;
     const A half_inv_P = (A)1 / (A)(2 * p.P);
@@ -1107,10 +1151,26 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         const int sidx = imul24(fq, HLP) + sl;
                         A ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
                         const A lg = SR::to_acc(proj3[3 * sidx + 2]);
-                        const T *r = refp + (size_t)fq * p.ref_dim;
+                        const T *r = ref_of(p, refp, fq, l);
                         Rec4<A> w;
                         w.v[0] = lg;
-                        if (p.ref_dim == 2) {
+                        if constexpr (kLevelRef<PP>) {
+                            // transformers' rule, as the fused forward forms it; the offsets are then parked DIVIDED
+                            // (by the level's width / height, or by P): the point written for the grad_value passes
+                            // is formed from the parked quotient by the same operations, and the box-size gradient
+                            // is the location gradient times it
+                            if (p.ref_dim == 2) {
+                                ox = ox / (A)tab->w[l];
+                                oy = oy / (A)tab->h[l];
+                                w.v[1] = TR::to_acc(r[0]) + ox;
+                                w.v[2] = TR::to_acc(r[1]) + oy;
+                            } else {
+                                ox = ox / (A)p.P;
+                                oy = oy / (A)p.P;
+                                w.v[1] = levelref_box_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]));
+                                w.v[2] = levelref_box_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]));
+                            }
+                        } else if (p.ref_dim == 2) {
                             w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->h[l];  // NB: (x, y) / img_shapes in its stored (h, w) order
                             w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->w[l];
                         } else if constexpr (kRagged<PP>) {
@@ -1482,6 +1542,39 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                 // ---- phase 2b: per-unit sums for the prologue's chain rule, off the gather's critical path: the
                 // unit's lanes stride over its parked results, DPP-reduce ----
                 wave_lds_sync();
+                if constexpr (kLevelRef<PP>) {
+                    // per-level reference points: the softmax's dot product as below; the reference-point gradient is a
+                    // partial per LEVEL — lane j of the unit sums the P parked results of the levels j, j + G, ... in
+                    // sample order (no exchange between lanes: L segment sums of P terms, off the gather's critical
+                    // path) and stores them itself: [B, Q, H, L, ref_dim], the caller sums over the heads
+                    if (unit_ok) {
+                        for (int sl = j; sl < sc; sl += G) {
+                            const int rs_ = imul24(wunit, scp) + sl;
+                            f_dot = fma_t(w_a[rs_], w_rec[rs_].v[0], f_dot);
+                        }
+                        f_dot = group_sum<G>(f_dot);
+                        T *gr = static_cast<T *>(p.grad_attn) + (((size_t)(b * (size_t)p.Q + q) * p.H + h) * p.L) * p.ref_dim;
+                        for (int l = j; l < p.L; l += G) {
+                            A gx = (A)0, gy = (A)0, gw = (A)0, gh = (A)0;
+                            const int rs0 = imul24(wunit, scp) + imul24(l, p.P);
+                            for (int k = 0; k < p.P; ++k) {
+                                const Rec4<A> res = w_rec[rs0 + k];
+                                gx += res.v[1];
+                                gy += res.v[2];
+                                gw = fma_t(res.v[1], w_ox[rs0 + k], gw);
+                                gh = fma_t(res.v[2], w_oy[rs0 + k], gh);
+                            }
+                            T *gl = gr + imul24(l, p.ref_dim);
+                            gl[0] = TR::from_acc(gx);
+                            gl[1] = TR::from_acc(gy);
+                            if (p.ref_dim == 4) {  // (d point / d size = offset / P * 0.5; the parked offsets carry the 1 / P)
+                                gl[2] = TR::from_acc(gw * (A)0.5);
+                                gl[3] = TR::from_acc(gh * (A)0.5);
+                            }
+                        }
+                        if (j == 0) w_a[imul24(wunit, scp) + sc] = f_dot;  // the unit's padding slot
+                    }
+                } else {
                 if (unit_ok) {
                     for (int sl = j; sl < sc; sl += G) {
                         const int rs_ = imul24(wunit, scp) + sl;
@@ -1512,6 +1605,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         gr[3] = TR::from_acc(kRagged<PP> ? f_gh : f_gh * half_inv_P);
                     }
                 }
+                }
             }
             wave_lds_sync();
             if constexpr (kDma) {
@@ -1533,9 +1627,17 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         else l = div_small(sl, p.P, inv_P);
                         const int rs_ = imul24(fu, scp) + (sl - s0);
                         const A a = w_a[rs_], dot = w_a[imul24(fu, scp) + sc];
-                        const T *r = refp + (size_t)fq * p.ref_dim;
+                        const T *r = ref_of(p, refp, fq, l);
                         A kx, ky;
-                        if (p.ref_dim == 2) {
+                        if constexpr (kLevelRef<PP>) {
+                            if (p.ref_dim == 2) {
+                                kx = (A)1 / (A)tab->w[l];
+                                ky = (A)1 / (A)tab->h[l];
+                            } else {
+                                kx = TR::to_acc(r[2]) * half_inv_P;
+                                ky = TR::to_acc(r[3]) * half_inv_P;
+                            }
+                        } else if (p.ref_dim == 2) {
                             kx = (A)1 / (A)tab->h[l];
                             ky = (A)1 / (A)tab->w[l];
                         } else if constexpr (kRagged<PP>) {
@@ -1556,7 +1658,15 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                             // (stored here, at the end of the wave's life, where nothing waits behind the stores)
                             const A ox = w_ox[rs_], oy = w_oy[rs_];
                             Pack<T, 2> m;
-                            if (p.ref_dim == 2) {
+                            if constexpr (kLevelRef<PP>) {  // (ox, oy: the quotients phase 0 parked; the same operations)
+                                if (p.ref_dim == 2) {
+                                    m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox);
+                                    m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy);
+                                } else {
+                                    m.v[0] = TR::from_acc(levelref_box_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2])));
+                                    m.v[1] = TR::from_acc(levelref_box_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3])));
+                                }
+                            } else if (p.ref_dim == 2) {
                                 m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox / (A)tab->h[l]);
                                 m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy / (A)tab->w[l]);
                             } else if constexpr (kRagged<PP>) {  // (ox, oy: scaled when they were parked)

@@ -838,6 +838,8 @@ int run_fwd(const void *value, const int64_t *shapes, const void *loc, const voi
 // TS: storage type of `proj` and `out` (T unless the module keeps them in 16 bits next to fp32 reference points)
 // PP = RaggedParams (msda_fwd_fused_ragged_<dtype>): per-level point counts `ppl` (ragged_counts checked them; P is their
 // maximum), `proj` [B, Q, H, S, 3]
+// PP = LevelRefParams (msda_fwd_fused_levelref_<dtype>): `ref` is [B, Q, L, ref_dim] and the points follow transformers'
+// rule (msda_kernels.hpp)
 template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, const void *ref, void *out, int64_t B,
                   int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,
@@ -1329,8 +1331,14 @@ inline size_t fused_mat_bytes(int64_t B, int64_t H, int64_t Q, int64_t S, size_t
     return align_up((size_t)(B * Q * H * S) * 3 * elem, 256);
 }
 
+// The kernarg the grad_value passes behind a fused backward run on.  Per-level reference points change the prologue
+// only: grad_value is the UNIFORM pipeline on the parked points (no kernels of its own).
+template <typename PP> inline PP &value_pass_params(PP &p) { return p; }
+inline Params &value_pass_params(LevelRefParams &p) { return p; }
+
 // PP = RaggedParams (msda_bwd_fused_ragged_<dtype>): per-level point counts `ppl`, proj / grad_proj [B, Q, H, S, 3]; the
 // derived points and weights go to the workspace in the ragged operator's layout and its grad_value pipeline reads them
+// PP = LevelRefParams (msda_bwd_fused_levelref_<dtype>): `ref` [B, Q, L, ref_dim], partials [B, Q, H, L, ref_dim]
 template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes, const void *proj, const void *ref,
                   void *grad_value, void *grad_proj, void *grad_ref_part, int64_t B, int64_t I, int64_t H, int64_t D,
@@ -1358,7 +1366,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         hipError_t e = hipSuccess;
         if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
         if (e == hipSuccess && ns) e = hipMemsetAsync(grad_proj, 0, ns * 3 * sizeof(TS), stream);
-        if (e == hipSuccess && B * Q * H) e = hipMemsetAsync(grad_ref_part, 0, (size_t)(B * Q * H) * ref_dim * sizeof(T), stream);
+        const size_t nref = (size_t)(B * Q * H) * (kLevelRef<PP> ? (size_t)L : 1) * ref_dim;
+        if (e == hipSuccess && nref) e = hipMemsetAsync(grad_ref_part, 0, nref * sizeof(T), stream);
         return (int)e;
     }
     const void *ptrs[] = {grad_out, value, shapes, proj, ref};
@@ -1411,7 +1420,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         p.attn = p.mat_attn;
         p.ref = nullptr;
         p.ref_dim = 0;
-        rc = run_value<T, TV, TS>(p, d, ws + mat, workspace_bytes - (int64_t)mat, stream);
+        rc = run_value<T, TV, TS>(value_pass_params(p), d, ws + mat, workspace_bytes - (int64_t)mat, stream);
     }
     return rc;
 }
@@ -1504,7 +1513,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                              D, Q, L, points_per_level, max_level_cells, value_row_stride,       \
                                              workspace, workspace_bytes, stream);                                \
     }                                                                                                            \
-    MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)
+    MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)                                                          \
+    MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
 // fp32 reference points and fp32 arithmetic (msda_fwd_fused_f32_sbf16 / _sf16): fused entry points only
@@ -1529,7 +1539,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                           align_corners, max_level_cells, value_row_stride, workspace,           \
                                           workspace_bytes, stream);                                              \
     }                                                                                                            \
-    MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)
+    MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)                                                         \
+    MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)
 
 // the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
 // points, TV value rows, TS projection / out / their gradients)
@@ -1563,6 +1574,34 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
             grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, pmax,  \
             ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
             stream, points_per_level);                                                                           \
+    }
+
+// the module's fused kernels for per-level reference points and transformers' point rule:
+// msda_{fwd,bwd}_fused_levelref_<suffix>, the argument lists of msda_{fwd,bwd}_fused_<suffix> (`ref` [B, Q, L, ref_dim],
+// the grad_reference_points partials [B, Q, H, L, ref_dim])
+#define MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, TS)                                                   \
+    extern "C" int msda_fwd_fused_levelref_##SUF(const void *value, const int64_t *shapes, const void *proj,     \
+                                                 const void *ref, void *out, int64_t B, int64_t I, int64_t H,     \
+                                                 int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim,         \
+                                                 int padding_mode, int align_corners, int64_t value_row_stride,   \
+                                                 void *stream)                                                    \
+    {                                                                                                            \
+        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefParams>(value, shapes, proj, ref, out, B, I, H, D, Q, L, \
+                                                                    P, ref_dim, padding_mode, align_corners,     \
+                                                                    value_row_stride, stream);                   \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_levelref_##SUF(const void *grad_out, const void *value, const int64_t *shapes, \
+                                                 const void *proj, const void *ref, void *grad_value,             \
+                                                 void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I,   \
+                                                 int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P,           \
+                                                 int ref_dim, int padding_mode, int align_corners,                \
+                                                 int64_t max_level_cells, int64_t value_row_stride,               \
+                                                 void *workspace, int64_t workspace_bytes, void *stream)          \
+    {                                                                                                            \
+        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefParams>(                                              \
+            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, P,     \
+            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
+            stream);                                                                                             \
     }
 
 // one storage type for every tensor

@@ -532,6 +532,92 @@ public:
     }
 };
 
+// The fused module core for per-level reference points and transformers' point rule (msda_fwd_fused_levelref_ /
+// msda_bwd_fused_levelref_<dtype>, additions within ABI 12): ref [B, Q, L, ref_dim], the kernel's partials
+// [B, Q, H, L, ref_dim] summed over the heads here.  The Python caller has checked L * P <= msda_fused_lp_limit, so the
+// library never declines; the workspace is the uniform fused pair's.
+std::pair<FwdFusedFn, BwdFusedFn> fused_levelref_fns_for(at::ScalarType t, at::ScalarType c)
+{
+    if (t != c) {
+        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
+                          "unsupported dtype combination: value ", t, " with ", c);
+        if (t == at::kBFloat16) return {msda_fwd_fused_levelref_f32_vbf16, msda_bwd_fused_levelref_f32_vbf16};
+        return {msda_fwd_fused_levelref_f32_vf16, msda_bwd_fused_levelref_f32_vf16};
+    }
+    switch (t) {
+    case at::kFloat: return {msda_fwd_fused_levelref_f32, msda_bwd_fused_levelref_f32};
+    case at::kHalf: return {msda_fwd_fused_levelref_f16, msda_bwd_fused_levelref_f16};
+    case at::kBFloat16: return {msda_fwd_fused_levelref_bf16, msda_bwd_fused_levelref_bf16};
+    case at::kDouble: return {msda_fwd_fused_levelref_f64, msda_bwd_fused_levelref_f64};
+    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
+    }
+}
+
+class MSDAFusedLevelRefFunction : public torch::autograd::Function<MSDAFusedLevelRefFunction> {
+public:
+    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
+                              const at::Tensor &proj_, const at::Tensor &ref_, int64_t padding_mode, bool align_corners,
+                              int64_t level_cells)
+    {
+        const auto [img, vrow] = value_rows(img_);
+        const at::Tensor proj = proj_.contiguous(), ref = ref_.contiguous();
+        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
+        const int64_t Q = proj.size(1), L = proj.size(3), P = proj.size(4);
+        at::Tensor out = at::empty({B, Q, H, D}, proj.options());
+        const c10::DeviceGuard guard(img.device());
+        check_rc(fused_levelref_fns_for(img.scalar_type(), proj.scalar_type())
+                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(), out.data_ptr(), B,
+                            I, H, D, Q, L, P, (int)ref.size(-1), (int)padding_mode, align_corners ? 1 : 0, vrow,
+                            current_stream(img)),
+                 "msda_fwd_fused_levelref");
+        ctx->save_for_backward({img, shapes, proj, ref});
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["align_corners"] = align_corners;
+        ctx->saved_data["level_cells"] = level_cells;
+        ctx->saved_data["vrow"] = vrow;
+        return out;
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
+                                                   torch::autograd::variable_list grads)
+    {
+        const auto saved = ctx->get_saved_variables();
+        const at::Tensor &img = saved[0], &shapes = saved[1], &proj = saved[2], &ref = saved[3];
+        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
+        const bool align_corners = ctx->saved_data["align_corners"].toBool();
+        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
+        const int64_t vrow = ctx->saved_data["vrow"].toInt();
+        at::Tensor gout = grads[0].contiguous();
+        if (gout.scalar_type() != proj.scalar_type()) gout = gout.to(proj.scalar_type());
+        const bool want_value = ctx->needs_input_grad(0);
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
+        const int64_t Q = proj.size(1), L = proj.size(3), P = proj.size(4);
+        const int64_t ref_dim = ref.size(-1);
+        at::Tensor g_img, ws;
+        at::Tensor g_proj = at::empty_like(proj), g_ref_part = at::empty({B, Q, H, L, ref_dim}, proj.options());
+        int64_t ws_bytes = 0;
+        if (want_value) {
+            g_img = at::empty(img.sizes(), img.options());
+            ws_bytes = msda_bwd_fused_workspace_bytes(B, I, H, D, Q, L, P, (int)proj.element_size(),
+                                                      (int)img.element_size(), level_cells, 0);
+            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
+        }
+        {
+            const c10::DeviceGuard guard(img.device());
+            check_rc(fused_levelref_fns_for(img.scalar_type(), proj.scalar_type())
+                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(),
+                                 want_value ? g_img.data_ptr() : nullptr, g_proj.data_ptr(), g_ref_part.data_ptr(), B, I, H,
+                                 D, Q, L, P, (int)ref_dim, padding_mode, align_corners ? 1 : 0, level_cells, vrow,
+                                 ws.defined() ? ws.data_ptr() : nullptr, ws_bytes, current_stream(img)),
+                     "msda_bwd_fused_levelref");
+        }
+        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_proj : at::Tensor(),
+                                           ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor(), at::Tensor(),
+                                           at::Tensor(), at::Tensor()});
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------------
 // Row ranges of the flattened (b, q) row space — the launches of the row-sharded operator
 // (msda_triton_amd/distributed.py; SURVEY 8e, reference independence argument kernels.py:18-21).  A rank's rows
@@ -768,6 +854,12 @@ at::Tensor msda_fused_ragged(const at::Tensor &img, const at::Tensor &shapes, co
     return MSDAFusedRaggedFunction::apply(img, shapes, proj, ref, padding_mode, align_corners, level_cells, counts);
 }
 
+at::Tensor msda_fused_levelref(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj, const at::Tensor &ref,
+                               int64_t padding_mode, bool align_corners, int64_t level_cells)
+{
+    return MSDAFusedLevelRefFunction::apply(img, shapes, proj, ref, padding_mode, align_corners, level_cells);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -792,6 +884,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
           pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells"),
           pybind11::arg("points_per_level"));
+    m.def("msda_fused_levelref", &msda_fused_levelref,
+          "module core with transformers' prologue fused in: reference points [B,Q,L,ref_dim] (differentiable)",
+          pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
+          pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells") = 0);
     m.def("msda_rows", &msda_rows,
           "rows [r0, r1) of the flattened (b, q) row space computed in `chunks` pieces into a full [B,Q,H,D] result "
           "(differentiable; the row-sharded operator without its exchange)",

@@ -526,12 +526,16 @@ def module_sampling_inputs(proj: torch.Tensor, img_shapes: torch.Tensor, referen
     return sampling_points, attention_weights
 
 
-def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners) -> Optional[torch.Tensor]:
+def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners,
+                       levelref: bool = False) -> Optional[torch.Tensor]:
     """Forward with softmax + sampling-point math done in the kernel prologue.  Returns None when the
-    library declines (L*P too large for one pass): the caller then takes the unfused route."""
+    library declines (L*P too large for one pass): the caller then takes the unfused route.  ``levelref``: the
+    reference points are per level, ``[B, Q, L, ref_dim]``, and the points follow transformers' rule
+    (:func:`hf_module_sampling_inputs`; ``msda_fwd_fused_levelref_<dtype>``)."""
     B, I, H, D = img.shape
     B2, Q, H2, L, P, three = proj.shape
-    if (B2, H2, three) != (B, H, 3) or tuple(reference_points.shape[:2]) != (B, Q):
+    if (B2, H2, three) != (B, H, 3) or tuple(reference_points.shape[:2]) != (B, Q) or \
+            reference_points.dim() != (4 if levelref else 3) or (levelref and reference_points.shape[2] != L):
         raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
                          f"reference_points {tuple(reference_points.shape)}")
     ref_dim = reference_points.shape[-1]
@@ -547,7 +551,10 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
     shapes = _shapes_i64(img_shapes)
     out = torch.empty((B, Q, H, D), dtype=cdt, device=img.device)
     lib = _lib.load()
-    fn = getattr(lib, f"msda_fwd_fused_{suf}")
+    name = "msda_fwd_fused_levelref" if levelref else "msda_fwd_fused"
+    fn = getattr(lib, f"{name}_{suf}", None)
+    if fn is None:  # (a library built before the per-level entry points: the caller composes)
+        return None
 
     def call():
         return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
@@ -555,18 +562,19 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
 
     with _OnDevice(img.device):
         timer = KernelTimer.active
-        rc = timer.launch("msda_fwd_fused", img.device, call) if timer else call()
+        rc = timer.launch(name, img.device, call) if timer else call()
     if rc == -5:  # MSDA_ERR_UNSUPPORTED
         return None
-    _lib.check(rc, f"msda_fwd_fused_{suf}")
+    _lib.check(rc, f"{name}_{suf}")
     return out
 
 
 def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners,
-                       need_img: bool = True, level_cells: int = 0, need_ref: bool = True):
+                       need_img: bool = True, level_cells: int = 0, need_ref: bool = True, levelref: bool = False):
     """Backward of the module core with the prologue's chain rule done in the kernel: returns
     ``(img_grad | None, proj_grad, reference_points_grad)``, or None when the library declines (L*P too large
-    for one pass; nothing was launched)."""
+    for one pass; nothing was launched).  ``levelref``: as in :func:`msda_hip_fwd_fused`; the kernel's partials are
+    then ``[B, Q, H, L, ref_dim]`` and the gradient ``[B, Q, L, ref_dim]``."""
     B, I, H, D = img.shape
     _, Q, _, L, P, _ = proj.shape
     ref_dim = reference_points.shape[-1]
@@ -583,9 +591,13 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
     kw = dict(dtype=cdt, device=img.device)
     g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
     g_proj = torch.empty((B, Q, H, L, P, 3), **kw)
-    g_ref_part = torch.empty((B, Q, H, ref_dim), dtype=reference_points.dtype, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, L, ref_dim) if levelref else (B, Q, H, ref_dim), dtype=reference_points.dtype,
+                             device=img.device)
     lib = _lib.load()
-    fn = getattr(lib, f"msda_bwd_fused_{suf}")
+    name = "msda_bwd_fused_levelref" if levelref else "msda_bwd_fused"
+    fn = getattr(lib, f"{name}_{suf}", None)
+    if fn is None:
+        return None
     ws, ws_bytes = None, 0
     level_cells = int(level_cells)  # the level-size bound (level_cells_of), an argument of the size query and the launch
     if need_img:  # (a frozen value pyramid needs no workspace at all — ADVICE r04)
@@ -601,10 +613,10 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
 
     with _OnDevice(img.device):
         timer = KernelTimer.active
-        rc = timer.launch("msda_bwd_fused", img.device, call) if timer else call()
+        rc = timer.launch(name, img.device, call) if timer else call()
     if rc == -5:  # MSDA_ERR_UNSUPPORTED
         return None
-    _lib.check(rc, f"msda_bwd_fused_{suf}")
+    _lib.check(rc, f"{name}_{suf}")
     # (the kernel leaves per-head partials of grad_reference_points; their sum is a launch of its own — 16 us at the c2
     # shape — and reference points rarely require a gradient)
     return g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None)
@@ -721,6 +733,144 @@ def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, ali
                                                          align_corners, level_cells)
     pts, att = module_sampling_inputs(proj, img_shapes, reference_points)
     return multiscale_deformable_attention(img, img_shapes, pts, att, padding_mode, align_corners, level_shapes=level_shapes)
+
+
+# ------------------------------------------------------------------------------------------
+# the same for Hugging Face transformers' attention modules: per-level reference points, transformers' point rule
+# (transformers/models/deformable_detr/modeling_deformable_detr.py, DeformableDetrMultiscaleDeformableAttention.forward;
+#  Grounding-DINO and the RT-DETR family carry the same lines)
+# ------------------------------------------------------------------------------------------
+def hf_module_sampling_inputs(proj: torch.Tensor, img_shapes: torch.Tensor, reference_points: torch.Tensor):
+    """transformers' prologue in plain PyTorch, with transformers' own operations in transformers' own order: raw
+    projection ``[B, N, H, L, P, 3]`` (x offset, y offset, logit) and PER-LEVEL reference points ``[B, N, L, 2 | 4]`` ->
+    (sampling_points ``[B, N, H, L, P, 2]``, attention_weights ``[B, N, H, L, P]``).  It differs from
+    :func:`module_sampling_inputs` (the reference module's prologue) in the reference points' level axis, in dividing the
+    (x, y) offsets by (width, height) — not by ``img_shapes`` in its stored (height, width) order — and in the order of the
+    4-d rule's operations."""
+    B, N, H, L, P, _ = proj.shape
+    sampling_offsets, logits = proj[..., :2], proj[..., 2]
+    attention_weights = torch.nn.functional.softmax(logits.reshape(B, N, H, L * P), -1).view(B, N, H, L, P)
+    num_coordinates = reference_points.shape[-1]
+    if reference_points.dim() != 4 or reference_points.shape[2] != L:
+        raise ValueError(f"`reference_points` should be [B, N, {L}, 2 or 4] (a point per level), but got "
+                         f"{tuple(reference_points.shape)}.")
+    if num_coordinates == 2:
+        offset_normalizer = torch.stack([img_shapes[..., 1], img_shapes[..., 0]], -1)
+        sampling_locations = (
+            reference_points[:, :, None, :, None, :]
+            + sampling_offsets / offset_normalizer[None, None, None, :, None, :]
+        )
+    elif num_coordinates == 4:
+        sampling_locations = (
+            reference_points[:, :, None, :, None, :2]
+            + sampling_offsets / P * reference_points[:, :, None, :, None, 2:] * 0.5
+        )
+    else:
+        raise ValueError(f"`reference_points` should have the last dim either 2 or 4, but got {num_coordinates}.")
+    return sampling_locations, attention_weights
+
+
+def _hf_composition(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes):
+    """transformers' prologue as PyTorch ops around the plain operator (host tensors, traced calls, whatever the fused
+    kernels decline).  16-bit value / projection next to fp32 reference points: the prologue in fp32, the mixed-storage
+    operator, the result back in the projection's dtype."""
+    if img.device.type == "cuda" and fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype):
+        pts, att = hf_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points)
+        return multiscale_deformable_attention(img, img_shapes, pts, att, padding_mode, align_corners,
+                                               level_shapes=level_shapes).to(proj.dtype)
+    pts, att = hf_module_sampling_inputs(proj, img_shapes, reference_points)
+    return multiscale_deformable_attention(img, img_shapes, pts, att, padding_mode, align_corners, level_shapes=level_shapes)
+
+
+class _HipFusedHFModuleCoreFunction(Function):
+    """:class:`_HipFusedModuleCoreFunction` for per-level reference points and transformers' point rule
+    (``msda_*_fused_levelref_<dtype>``).  When the library declines — L*P too large for one LDS pass, or a library built
+    before these entry points — transformers' prologue runs in PyTorch around the plain operator."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, level_cells=0):
+        ctx.level_cells = int(level_cells)
+        out = msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, levelref=True)
+        ctx.fused = out is not None  # the backward has the same limits: do not ask twice
+        if out is None:
+            pts, att = hf_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points)
+            out = msda_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners).to(proj.dtype)
+        ctx.save_for_backward(img, img_shapes, proj, reference_points)
+        ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, out_grad):
+        img, img_shapes, proj, reference_points = ctx.saved_tensors
+        need_img, _, need_proj, need_ref = ctx.needs_input_grad[:4]
+        if ctx.fused and (need_proj or need_ref):
+            res = msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, ctx.padding_mode,
+                                     ctx.align_corners, need_img, level_cells=ctx.level_cells, need_ref=need_ref,
+                                     levelref=True)
+            if res is not None:
+                g_img, g_proj, g_ref = res
+                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None
+        with torch.enable_grad():
+            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
+            ref_ = reference_points.detach().requires_grad_(need_ref)
+            pts, att = hf_module_sampling_inputs(proj_, img_shapes, ref_)
+        out_grad = out_grad.to(pts.dtype)
+        need_sample = need_proj or need_ref
+        g_img, g_pts, g_att = msda_hip_bwd(out_grad, img, img_shapes, pts.detach(), att.detach(), ctx.padding_mode,
+                                           ctx.align_corners, (need_img, need_sample, need_sample),
+                                           level_cells=ctx.level_cells)
+        g_proj = g_ref = None
+        if need_sample:
+            wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
+            grads = list(torch.autograd.grad([pts, att], wrt, [g_pts, g_att], allow_unused=True))
+            if need_proj:
+                g_proj = grads.pop(0).to(proj.dtype)
+            if need_ref:
+                g_ref = grads.pop(0)
+        return g_img, None, g_proj, g_ref, None, None, None
+
+
+def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None) -> torch.Tensor:
+    """``multiscale_deformable_attention(img, img_shapes, *hf_module_sampling_inputs(proj, ...))``: the core of a Hugging
+    Face attention module between its projections — value pyramid ``[B, I, H, D]``, raw projection ``[B, Q, H, L, P, 3]``,
+    per-level reference points ``[B, Q, L, 2 | 4]``.  On GPU tensors the prologue and its chain rule run inside the
+    gather kernels (``msda_*_fused_levelref_<dtype>``); on host tensors, while traced by ``torch.compile`` (over the
+    registered custom ops) and where the library declines it is exactly that composition.  ``level_shapes``: the level
+    sizes as host numbers, optional (:func:`level_cells_of`)."""
+    level_cells = level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1])
+    cuda = img.device.type == "cuda"
+    if cuda and img_shapes.device != img.device:
+        img_shapes = img_shapes.to(img.device)  # a handful of integers: follow `img`, as fused_module_core
+    if cuda and not torch.compiler.is_compiling():
+        _check_devices(img, proj, reference_points)
+        floating = img.is_floating_point() and proj.is_floating_point() and reference_points.is_floating_point()
+        same = dtypes_supported(img.dtype, proj.dtype) and reference_points.dtype == proj.dtype
+        autocast = _autocast_on()
+        if floating and (autocast or same or fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype)):
+            pad = _padding_code(padding_mode)
+            ext = _ext.load()
+            if same and not autocast and KernelTimer.active is None and ext is not None and \
+                    hasattr(ext, "msda_fused_levelref") and _lib.has_fused_levelref():
+                # C++ autograd node; only when the fused kernels take this L*P (it never composes)
+                B, I, H, D = img.shape
+                key = (D, proj.element_size())
+                limit = _FUSED_LP_LIMIT.get(key)
+                if limit is None:
+                    limit = _FUSED_LP_LIMIT[key] = int(ext.fused_lp_limit(*key))
+                if proj.dim() == 6 and proj.shape[3] * proj.shape[4] <= limit and proj.shape[-1] == 3 \
+                        and reference_points.dim() == 4 and reference_points.shape[-1] in (2, 4) \
+                        and tuple(proj.shape[:3]) == (B, reference_points.shape[1], H) \
+                        and reference_points.shape[0] == B and reference_points.shape[2] == proj.shape[3] \
+                        and tuple(img_shapes.shape) == (proj.shape[3], 2):
+                    _shapes_i64(img_shapes)
+                    return ext.msda_fused_levelref(img, img_shapes, proj, reference_points, pad, bool(align_corners),
+                                                   level_cells)
+            return _HipFusedHFModuleCoreFunction.apply(img, img_shapes, proj, reference_points, padding_mode,
+                                                       bool(align_corners), level_cells)
+    return _hf_composition(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes)
 
 
 # ------------------------------------------------------------------------------------------

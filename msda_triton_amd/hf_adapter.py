@@ -23,7 +23,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .functional import _autocast_on, multiscale_deformable_attention
+from .functional import _autocast_on, fused_hf_module_core, multiscale_deformable_attention
 
 
 class MultiScaleDeformableAttention(nn.Module):
@@ -120,12 +120,102 @@ def _core(value, spatial_shapes_list, sampling_locations, attention_weights, num
     return out.flatten(2)
 
 
-def replace_hf_msda(model: nn.Module, discrete: bool = False) -> int:
+class FusedHFDeformableAttention:
+    """Mixed into the class of a Hugging Face attention module (``DeformableDetrMultiscaleDeformableAttention``,
+    ``GroundingDinoMultiscaleDeformableAttention``, the RT-DETR family's ...) by ``replace_hf_msda(model, fused=True)``:
+    the module keeps its submodules, parameters and ``state_dict`` keys; its forward runs the softmax, the offset
+    normalisation and the reference-point broadcast inside the gather kernels (:func:`fused_hf_module_core`).
+
+    The softmaxed attention weights are never materialised, so the second element of the returned pair is ``None``.  A
+    caller that records attentions sets ``module.return_attention_weights = True`` (or passes
+    ``output_attentions=True``): the module then takes the original forward over the adapter's core."""
+
+    return_attention_weights = False
+
+    def _proj_rows(self, device) -> torch.Tensor:
+        # row (h, l, p, k) of the one projection: k < 2 the offset rows of `sampling_offsets`, k == 2 the logit row of
+        # `attention_weights` (behind them in the concatenation)
+        idx = self.__dict__.get("_msda_proj_rows")
+        if idx is None or idx.device != device:
+            n = self.n_heads * self.n_levels * self.n_points
+            s = torch.arange(n, device=device)
+            idx = torch.stack([2 * s, 2 * s + 1, 2 * n + s], -1).reshape(-1)
+            self.__dict__["_msda_proj_rows"] = idx  # (not a buffer: state_dict stays the HF module's)
+        return idx
+
+    def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
+                position_embeddings=None, reference_points=None, spatial_shapes=None, spatial_shapes_list=None,
+                level_start_index=None, **kwargs):
+        if self.return_attention_weights or kwargs.get("output_attentions"):
+            return super().forward(hidden_states, attention_mask=attention_mask, encoder_hidden_states=encoder_hidden_states,
+                                   encoder_attention_mask=encoder_attention_mask, position_embeddings=position_embeddings,
+                                   reference_points=reference_points, spatial_shapes=spatial_shapes,
+                                   spatial_shapes_list=spatial_shapes_list, level_start_index=level_start_index, **kwargs)
+        if position_embeddings is not None:
+            hidden_states = hidden_states + position_embeddings
+        batch_size, num_queries, _ = hidden_states.shape
+        sequence_length = encoder_hidden_states.shape[1]
+        value = self.value_proj(encoder_hidden_states)
+        if attention_mask is not None:
+            value = value.masked_fill(~attention_mask[..., None], float(0))
+        value = value.view(batch_size, sequence_length, self.n_heads, value.shape[-1] // self.n_heads)
+        # ONE GEMM for offsets and logits, laid out [B, Q, H, L, P, 3]; the weight is gathered from the two HF parameters
+        # (autograd routes its gradient back to them)
+        rows = self._proj_rows(hidden_states.device)
+        so, aw = self.sampling_offsets, self.attention_weights
+        weight = torch.cat([so.weight, aw.weight], 0).index_select(0, rows)
+        bias = torch.cat([so.bias, aw.bias], 0).index_select(0, rows) if so.bias is not None and aw.bias is not None else None
+        proj = nn.functional.linear(hidden_states, weight, bias)
+        if bias is None and (so.bias is not None or aw.bias is not None):
+            raise ValueError("`sampling_offsets` and `attention_weights` should both have a bias or neither")
+        proj = proj.view(batch_size, num_queries, self.n_heads, self.n_levels, self.n_points, 3)
+        level_shapes = spatial_shapes_list if isinstance(spatial_shapes_list, (list, tuple)) else None
+        shapes = spatial_shapes
+        if not torch.is_tensor(shapes):
+            shapes = _shapes_tensor(shapes if shapes is not None else spatial_shapes_list, value.device)
+        if value.device.type == "cuda" and value.dtype in (torch.bfloat16, torch.float16) and proj.dtype == value.dtype \
+                and reference_points.dtype == torch.float32:
+            # what autocast hands the core: 16-bit value and projection next to fp32 reference points — the module-storage
+            # kernels (fp32 arithmetic, 16-bit result), called outside autocast so that nothing is cast to fp32
+            with torch.autocast("cuda", enabled=False):
+                out = fused_hf_module_core(value, shapes, proj, reference_points, "zeros", False, level_shapes=level_shapes)
+        else:
+            if proj.dtype != value.dtype:
+                proj = proj.to(value.dtype)
+            if reference_points.dtype != value.dtype:
+                reference_points = reference_points.to(value.dtype)
+            out = fused_hf_module_core(value, shapes, proj, reference_points, "zeros", False, level_shapes=level_shapes)
+        return self.output_proj(out.flatten(2)), None
+
+
+_FUSED_CLASSES: dict = {}  # HF module class -> its fused subclass
+_FUSED_ATTRS = ("sampling_offsets", "attention_weights", "value_proj", "output_proj", "n_heads", "n_levels", "n_points")
+
+
+def _wrap_fused(module: nn.Module) -> bool:
+    if isinstance(module, FusedHFDeformableAttention) or not all(hasattr(module, a) for a in _FUSED_ATTRS):
+        return False
+    attn = getattr(module, "attn", None)
+    if not isinstance(attn, nn.Module) or type(attn).__name__ != "MultiScaleDeformableAttention":
+        return False
+    cls = type(module)
+    fused = _FUSED_CLASSES.get(cls)
+    if fused is None:
+        fused = _FUSED_CLASSES[cls] = type("Fused" + cls.__name__, (FusedHFDeformableAttention, cls), {})
+    module.__class__ = fused
+    return True
+
+
+def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = False) -> int:
     """Swap every HF ``MultiScaleDeformableAttention`` submodule of ``model`` for the adapter, and set
     :func:`ms_deformable_attn_core` on every module that carries an ``ms_deformable_attn_core`` attribute with
     ``decoder_method == "default"`` (D-FINE / DEIMv2; ``"discrete"`` modules are left alone).  With ``discrete=True``
     (opt-in) modules whose ``decoder_method`` is ``"discrete"`` are patched too, with
-    :func:`ms_deformable_attn_core_v2`.  Returns the number of modules replaced or patched."""
+    :func:`ms_deformable_attn_core_v2`.  With ``fused=True`` (opt-in) every attention module that owns such a core as
+    its child ``attn`` next to ``sampling_offsets``, ``attention_weights``, ``value_proj``, ``output_proj``, ``n_heads``,
+    ``n_levels`` and ``n_points`` (Deformable-DETR, Grounding-DINO, the RT-DETR family; matched by these names, not by
+    class) additionally becomes a :class:`FusedHFDeformableAttention`.  Returns the number of modules replaced, patched
+    or wrapped."""
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -142,4 +232,8 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False) -> int:
                 module.ms_deformable_attn_core is not ms_deformable_attn_core_v2:
             module.ms_deformable_attn_core = ms_deformable_attn_core_v2
             count += 1
+    if fused:
+        for module in list(model.modules()):
+            if _wrap_fused(module):
+                count += 1
     return count
