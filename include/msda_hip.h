@@ -182,6 +182,18 @@ extern "C" {
                        void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
                        int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,   \
                        int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);\
+    MSDA_API int msda_fwd_fused_hfbox_##SUF(const void *value, const int64_t *shapes, const void *proj,   \
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, const int32_t *points_per_level,                       \
+                       const float *level_scale, double offset_scale, int ref_dim, int padding_mode,\
+                       int align_corners, int64_t value_row_stride, void *stream);                  \
+    MSDA_API int msda_bwd_fused_hfbox_##SUF(const void *grad_out, const void *value,                \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
+                       int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level,            \
+                       const float *level_scale, double offset_scale, int ref_dim, int padding_mode,\
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
                        void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
@@ -233,6 +245,31 @@ extern "C" {
  * every size guard of msda_fwd_fused_ / msda_bwd_fused_<suffix>).  grad_value IS the uniform pipeline on the derived points:
  * the workspace is the uniform pair's — msda_bwd_fused_workspace_bytes answers for these calls too, there is no query of
  * their own — and value_row_stride, max_level_cells and MSDA_WS_PASSES(n) mean what they mean there.
+ *
+ * The module's fused pair for HUGGING FACE'S BOX RULE WITH PER-LEVEL POINT COUNTS — ADDITIONS WITHIN ABI 12, probed by
+ * symbol: msda_fwd_fused_hfbox_<suffix> / msda_bwd_fused_hfbox_<suffix> for the same eight suffixes, the argument lists
+ * of msda_fwd_fused_ragged_<suffix> / msda_bwd_fused_ragged_<suffix> with two arguments behind `points_per_level`:
+ *
+ *   level_scale   HOST array of L floats: s_l, the scale of level l's offsets.  transformers' modules (D-FINE, DEIMv2,
+ *                 RT-DETRv2) keep float32(1 / P_l) in an fp32 buffer; the caller passes those values
+ *   offset_scale  the modules' offset_scale (a double; 0.5 in the default configurations)
+ *   ref           [B, Q, 4] boxes (cx, cy, w, h); ref_dim must be 4, anything else is MSDA_ERR_BAD_ARG
+ *   grad_ref_partial  [B, Q, H, 4], the caller sums over the heads
+ *
+ * The sampling point of an offset o of level l follows transformers' expression
+ * `ref.xy + o * num_points_scale * ref.wh * offset_scale`, exactly these operations in this order, each rounded once
+ * in the arithmetic type (fp32; fp64 for _f64), s_l and offset_scale first converted to that type:
+ *
+ *   q = o * s_l      t = q * wh      u = t * offset_scale      point = ref.xy + u     (no fused multiply-add)
+ *
+ * so the point is bit for bit the host expression's — in fp64 too, where s_l is float32(1 / P_l) widened and not
+ * 1 / P_l — and the copy parked for grad_value (formed again from the parked q by the same operations) names the cell the
+ * forward sampled.  The weights are the softmax over the unit's S logits.  Gradients: grad_o = gX * s_l * wh * offset_scale,
+ * grad_wh = offset_scale * sum gX * q, grad_xy = sum gX.  Limits, size guards, value_row_stride, max_level_cells and
+ * MSDA_WS_PASSES(n) are the fused per-level-count pair's (S <= msda_fused_lp_limit(D, elem_size) and L <= 8, else
+ * MSDA_ERR_UNSUPPORTED and nothing is launched); grad_value IS that pair's pipeline on the derived points, and the workspace
+ * is its workspace: msda_bwd_fused_ragged_workspace_bytes answers for these calls too.  Equal counts are served as any
+ * others (the uniform pairs implement other rules).
  *
  * Discrete (nearest-pixel) sampling — ADDITIONS WITHIN ABI 12: no existing signature changes and MSDA_ABI_VERSION stays
  * 12, so a caller PROBES FOR THESE BY SYMBOL (dlsym / hasattr) instead of by version; a library built before them simply
@@ -303,6 +340,18 @@ MSDA_DECLARE(f32_vf16)
                        const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
                        void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
                        int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,   \
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);\
+    MSDA_API int msda_fwd_fused_hfbox_##SUF(const void *value, const int64_t *shapes, const void *proj,   \
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, const int32_t *points_per_level,                       \
+                       const float *level_scale, double offset_scale, int ref_dim, int padding_mode,\
+                       int align_corners, int64_t value_row_stride, void *stream);                  \
+    MSDA_API int msda_bwd_fused_hfbox_##SUF(const void *grad_out, const void *value,                \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I, int64_t H,    \
+                       int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level,            \
+                       const float *level_scale, double offset_scale, int ref_dim, int padding_mode,\
                        int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
                        void *workspace, int64_t workspace_bytes, void *stream);
 MSDA_DECLARE_FUSED_STORAGE(f32_sbf16)

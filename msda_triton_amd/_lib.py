@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = tuple(
     + [f"msda_{d}_fused_ragged_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
     + ["msda_bwd_fused_ragged_workspace_bytes"]
     + [f"msda_{d}_fused_levelref_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+    + [f"msda_{d}_fused_hfbox_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
     + ["msda_abi_version", "msda_last_error", "msda_set_option", "msda_get_option", "msda_bwd_workspace_bytes",
        "msda_bwd_fused_workspace_bytes", "msda_bwd_supported", "msda_fused_lp_limit", "msda_profile_read",
        "msda_last_launch_info"]
@@ -162,6 +163,17 @@ def load():
                 gfl = getattr(lib, f"msda_bwd_fused_levelref_{suf}")
                 gfl.restype = ci
                 gfl.argtypes = [vp] * 8 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
+        # the module's fused pair for Hugging Face's box rule with per-level counts (D-FINE, DEIMv2, RT-DETRv2): additions
+        # within ABI 12 (has_fused_hfbox); the fused ragged pair's lists with (level_scale, offset_scale) behind the counts
+        if hasattr(lib, "msda_bwd_fused_hfbox_f32"):
+            cd = ctypes.c_double
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                ffh = getattr(lib, f"msda_fwd_fused_hfbox_{suf}")
+                ffh.restype = ci
+                ffh.argtypes = [vp] * 5 + [i64] * 6 + [vp, vp, cd, ci, ci, ci, i64, vp]
+                gfh = getattr(lib, f"msda_bwd_fused_hfbox_{suf}")
+                gfh.restype = ci
+                gfh.argtypes = [vp] * 8 + [i64] * 6 + [vp, vp, cd, ci, ci, ci, i64, i64, vp, i64, vp]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -202,6 +214,13 @@ def has_fused_levelref() -> bool:
     (msda_fwd_fused_levelref_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller composes
     transformers' prologue around the plain operator."""
     return hasattr(load(), "msda_bwd_fused_levelref_f32")
+
+
+def has_fused_hfbox() -> bool:
+    """Does the loaded library have the fused module pair for Hugging Face's box rule with per-level point counts
+    (msda_fwd_fused_hfbox_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller composes
+    transformers' prologue around the ragged operator."""
+    return hasattr(load(), "msda_bwd_fused_hfbox_f32")
 
 
 def check(rc: int, what: str) -> None:

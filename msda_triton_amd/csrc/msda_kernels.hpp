@@ -212,6 +212,50 @@ template <typename A> __device__ __forceinline__ A levelref_box_point(A r, A q, 
     return r + t;
 }
 
+// ---- Hugging Face's box rule with per-level point counts (msda_*_fused_hfbox_<dtype>): the fused module kernels for
+// D-FINE, DEIMv2 and RT-DETRv2 ----
+// The layout is the per-level-count pair's (`proj` [B, Q, H, S, 3] level-major, `ref` [B, Q, 4], the partials
+// [B, Q, H, 4]); the point follows transformers' expression `ref.xy + offsets * num_points_scale * ref.wh * offset_scale`:
+//   q = o * s_l      t = q * wh      u = t * offset_scale      point = ref.xy + u
+// four operations, each rounded once in the arithmetic type.  s_l is the HOST's float32(1 / P_l) — transformers keeps
+// the scale as an fp32 buffer and converts it, so in fp64 it is float32(1/3) widened, not 1/3 — and offset_scale the
+// config's Python float.  Both ride behind the level starts at the end of the kernarg (the preloaded front is unchanged):
+// a kernarg type of its own, derived from RaggedParams so that the level scan, the parked level and the ragged
+// grad_value pipeline (value_pass_params, msda_launch.hpp) serve it as they are, and the rule hangs on
+// `if constexpr (kHfBox<PP>)` in front of the other rules' branches.
+struct HfBoxParams : RaggedParams {
+    float lscale[kFusedRaggedMaxLevels];  // s_l; entries beyond L are 0
+    double off_scale;
+};
+template <typename PP> constexpr bool kHfBox = std::is_base_of<HfBoxParams, PP>::value;
+
+// s_l of the sample's level, converted to the arithmetic type: a select per level on scalars at constant kernarg offsets
+// (as lvl_of's scan; the level itself comes from that scan, the host bounds L by kFusedRaggedMaxLevels).
+template <typename A, typename PP> __device__ __forceinline__ A hfbox_scale(const PP &p, int l)
+{
+    if constexpr (kHfBox<PP>) {
+        float s = p.lscale[0];
+#pragma unroll
+        for (int k = 1; k < kFusedRaggedMaxLevels; ++k) {
+            if (k >= p.L) break;
+            s = l >= k ? p.lscale[k] : s;
+        }
+        return (A)s;
+    } else {
+        return (A)0;
+    }
+}
+// The point from q = o * s_l (the backward parks q: phase 3 calls this again on the same operands, so the copy written
+// for grad_value names the cell the forward sampled).  The translation units are built with -ffp-contract=fast; the last
+// product passes through an empty asm statement (as levelref_box_point's) so that the add cannot take it as an FMA operand.
+template <typename A> __device__ __forceinline__ A hfbox_point(A r, A q, A size, A off_scale)
+{
+    A t = q * size;
+    t = t * off_scale;
+    asm("" : "+v"(t));
+    return r + t;
+}
+
 template <typename A> struct alignas(16) Rec4 {
     A v[4];
 };
@@ -646,7 +690,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                             const T *r = ref_of(p, refp, fq, l);
                             Rec4<A> w;
                             w.v[0] = lg;
-                            if constexpr (kLevelRef<PP>) {  // transformers' rule on the level's own reference point
+                            if constexpr (kHfBox<PP>) {  // transformers' box rule with the level's own 1 / P_l
+                                const A s = hfbox_scale<A>(p, l), os = (A)p.off_scale;
+                                w.v[1] = hfbox_point<A>(TR::to_acc(r[0]), ox * s, TR::to_acc(r[2]), os);
+                                w.v[2] = hfbox_point<A>(TR::to_acc(r[1]), oy * s, TR::to_acc(r[3]), os);
+                            } else if constexpr (kLevelRef<PP>) {  // transformers' rule on the level's own reference point
                                 if (p.ref_dim == 2) {
                                     w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->w[l];
                                     w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->h[l];
@@ -1154,7 +1202,17 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         const T *r = ref_of(p, refp, fq, l);
                         Rec4<A> w;
                         w.v[0] = lg;
-                        if constexpr (kLevelRef<PP>) {
+                        if constexpr (kHfBox<PP>) {
+                            // transformers' box rule, as the fused forward forms it; the offsets are then parked
+                            // SCALED by their level's s_l: phase 3 forms the point written for the grad_value passes
+                            // from the parked product by the same operations, and the box-size gradient is the
+                            // location gradient times it (times offset_scale)
+                            const A s = hfbox_scale<A>(p, l), os = (A)p.off_scale;
+                            ox = ox * s;
+                            oy = oy * s;
+                            w.v[1] = hfbox_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]), os);
+                            w.v[2] = hfbox_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]), os);
+                        } else if constexpr (kLevelRef<PP>) {
                             // transformers' rule, as the fused forward forms it; the offsets are then parked DIVIDED
                             // (by the level's width / height, or by P): the point written for the grad_value passes
                             // is formed from the parked quotient by the same operations, and the box-size gradient
@@ -1599,7 +1657,10 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     T *gr = static_cast<T *>(p.grad_attn) + ((size_t)(b * (size_t)p.Q + q) * p.H + h) * p.ref_dim;
                     gr[0] = TR::from_acc(f_gx);
                     gr[1] = TR::from_acc(f_gy);
-                    if (p.ref_dim == 4) {
+                    if constexpr (kHfBox<PP>) {  // (the parked offsets carry their level's s_l: d point / d size = q * offset_scale)
+                        gr[2] = TR::from_acc(f_gw * (A)p.off_scale);
+                        gr[3] = TR::from_acc(f_gh * (A)p.off_scale);
+                    } else if (p.ref_dim == 4) {
                         // (per-level point counts: the parked offsets already carry their level's 1 / (2 P_l))
                         gr[2] = TR::from_acc(kRagged<PP> ? f_gw : f_gw * half_inv_P);
                         gr[3] = TR::from_acc(kRagged<PP> ? f_gh : f_gh * half_inv_P);
@@ -1629,7 +1690,11 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         const A a = w_a[rs_], dot = w_a[imul24(fu, scp) + sc];
                         const T *r = ref_of(p, refp, fq, l);
                         A kx, ky;
-                        if constexpr (kLevelRef<PP>) {
+                        if constexpr (kHfBox<PP>) {  // d point / d offset = s_l * size * offset_scale
+                            const A s = hfbox_scale<A>(p, l), os = (A)p.off_scale;
+                            kx = s * TR::to_acc(r[2]) * os;
+                            ky = s * TR::to_acc(r[3]) * os;
+                        } else if constexpr (kLevelRef<PP>) {
                             if (p.ref_dim == 2) {
                                 kx = (A)1 / (A)tab->w[l];
                                 ky = (A)1 / (A)tab->h[l];
@@ -1658,7 +1723,10 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                             // (stored here, at the end of the wave's life, where nothing waits behind the stores)
                             const A ox = w_ox[rs_], oy = w_oy[rs_];
                             Pack<T, 2> m;
-                            if constexpr (kLevelRef<PP>) {  // (ox, oy: the quotients phase 0 parked; the same operations)
+                            if constexpr (kHfBox<PP>) {  // (ox, oy: the products phase 0 parked; the same operations)
+                                m.v[0] = TR::from_acc(hfbox_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]), (A)p.off_scale));
+                                m.v[1] = TR::from_acc(hfbox_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]), (A)p.off_scale));
+                            } else if constexpr (kLevelRef<PP>) {  // (ox, oy: the quotients phase 0 parked; the same operations)
                                 if (p.ref_dim == 2) {
                                     m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox);
                                     m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy);

@@ -782,6 +782,19 @@ inline int ragged_counts(const int32_t *ppl, int64_t L, int64_t &pmax, int64_t &
     }
     return 0;
 }
+// the arguments msda_*_fused_hfbox_<dtype> have beyond the per-level-count pair's
+inline int box_rule_args(const float *level_scale, int64_t L, int ref_dim)
+{
+    if (ref_dim != 4) {
+        set_error("the Hugging Face box rule takes boxes: ref_dim must be 4, got %d", ref_dim);
+        return MSDA_ERR_BAD_ARG;
+    }
+    if (level_scale == nullptr && L > 0) {
+        set_error("level_scale: null pointer");
+        return MSDA_ERR_BAD_ARG;
+    }
+    return 0;
+}
 inline void fill_level_starts(RaggedParams &p, const int32_t *ppl, int64_t L)
 {
     p.pst[0] = 0;
@@ -789,6 +802,14 @@ inline void fill_level_starts(RaggedParams &p, const int32_t *ppl, int64_t L)
     for (int64_t l = L + 1; l <= kMaxLevels; ++l) p.pst[l] = p.pst[L];
 }
 inline void fill_level_starts(Params &, const int32_t *, int64_t) {}
+// Hugging Face's box rule (msda_*_fused_hfbox_<dtype>): the caller's fp32 scale per level and offset_scale, behind the
+// level starts.  (L beyond the fused kernels' bound is refused before anything is launched; only the table is filled here.)
+inline void fill_box_scales(HfBoxParams &p, const float *lscale, double off_scale, int64_t L)
+{
+    for (int64_t l = 0; l < kFusedRaggedMaxLevels; ++l) p.lscale[l] = l < L ? lscale[l] : 0.0f;
+    p.off_scale = off_scale;
+}
+inline void fill_box_scales(Params &, const float *, double, int64_t) {}
 
 // PP = RaggedParams: per-level point counts `ppl` (ragged_counts checked them; P is their maximum)
 template <typename T, typename TV = T, typename PP = Params>
@@ -840,10 +861,13 @@ int run_fwd(const void *value, const int64_t *shapes, const void *loc, const voi
 // maximum), `proj` [B, Q, H, S, 3]
 // PP = LevelRefParams (msda_fwd_fused_levelref_<dtype>): `ref` is [B, Q, L, ref_dim] and the points follow transformers'
 // rule (msda_kernels.hpp)
+// PP = HfBoxParams (msda_fwd_fused_hfbox_<dtype>): the per-level-count layout with transformers' box rule — `lscale` holds
+// L fp32 scales on the host, `off_scale` the config's offset_scale (the entry point checked ref_dim == 4)
 template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, const void *ref, void *out, int64_t B,
                   int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,
-                  int align_corners, int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr)
+                  int align_corners, int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr,
+                  const float *lscale = nullptr, double off_scale = 0.0)
 {
     Dims d{B, I, H, D, Q, L, P};
     if (ppl != nullptr)
@@ -879,6 +903,7 @@ int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, co
     p.out = out;
     fill_params(p, d, padding_mode, align_corners);
     fill_level_starts(p, ppl, L);
+    fill_box_scales(p, lscale, off_scale, L);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.ref = ref;
@@ -1335,16 +1360,20 @@ inline size_t fused_mat_bytes(int64_t B, int64_t H, int64_t Q, int64_t S, size_t
 // only: grad_value is the UNIFORM pipeline on the parked points (no kernels of its own).
 template <typename PP> inline PP &value_pass_params(PP &p) { return p; }
 inline Params &value_pass_params(LevelRefParams &p) { return p; }
+// ... and so does Hugging Face's box rule: grad_value is the PER-LEVEL-COUNT pipeline on the parked points.
+inline RaggedParams &value_pass_params(HfBoxParams &p) { return p; }
 
 // PP = RaggedParams (msda_bwd_fused_ragged_<dtype>): per-level point counts `ppl`, proj / grad_proj [B, Q, H, S, 3]; the
 // derived points and weights go to the workspace in the ragged operator's layout and its grad_value pipeline reads them
 // PP = LevelRefParams (msda_bwd_fused_levelref_<dtype>): `ref` [B, Q, L, ref_dim], partials [B, Q, H, L, ref_dim]
+// PP = HfBoxParams (msda_bwd_fused_hfbox_<dtype>): the per-level-count layout and workspace, transformers' box rule with
+// the host's `lscale` [L] and `off_scale`
 template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes, const void *proj, const void *ref,
                   void *grad_value, void *grad_proj, void *grad_ref_part, int64_t B, int64_t I, int64_t H, int64_t D,
                   int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode, int align_corners,
                   int64_t max_level_cells, int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream_,
-                  const int32_t *ppl = nullptr)
+                  const int32_t *ppl = nullptr, const float *lscale = nullptr, double off_scale = 0.0)
 {
     Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
     if (ppl != nullptr)
@@ -1400,6 +1429,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
     p.grad_attn = grad_ref_part;
     fill_params(p, d, padding_mode, align_corners);
     fill_level_starts(p, ppl, L);
+    fill_box_scales(p, lscale, off_scale, L);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.ref = ref;
@@ -1514,7 +1544,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                              workspace, workspace_bytes, stream);                                \
     }                                                                                                            \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)                                                          \
-    MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, T)
+    MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, T)                                                        \
+    MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
 // fp32 reference points and fp32 arithmetic (msda_fwd_fused_f32_sbf16 / _sf16): fused entry points only
@@ -1540,7 +1571,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                           workspace_bytes, stream);                                              \
     }                                                                                                            \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)                                                         \
-    MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)
+    MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)                                                       \
+    MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)
 
 // the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
 // points, TV value rows, TS projection / out / their gradients)
@@ -1602,6 +1634,46 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
             grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, P,     \
             ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
             stream);                                                                                             \
+    }
+
+// the module's fused kernels for Hugging Face's box rule with per-level point counts (D-FINE, DEIMv2, RT-DETRv2):
+// msda_{fwd,bwd}_fused_hfbox_<suffix>, the argument lists of msda_{fwd,bwd}_fused_ragged_<suffix> with the host array
+// `level_scale` [L] (fp32) and `offset_scale` behind `points_per_level`; boxes only (`ref` [B, Q, 4])
+#define MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, TS)                                                      \
+    extern "C" int msda_fwd_fused_hfbox_##SUF(const void *value, const int64_t *shapes, const void *proj,        \
+                                              const void *ref, void *out, int64_t B, int64_t I, int64_t H,        \
+                                              int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level,   \
+                                              const float *level_scale, double offset_scale, int ref_dim,         \
+                                              int padding_mode, int align_corners, int64_t value_row_stride,      \
+                                              void *stream)                                                       \
+    {                                                                                                            \
+        int64_t pmax, S;                                                                                         \
+        int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                              \
+        if (rc) return rc;                                                                                       \
+        if ((rc = msda::box_rule_args(level_scale, L, ref_dim)) != 0) return rc;                                 \
+        return msda::run_fwd_fused<T, TV, TS, msda::HfBoxParams>(value, shapes, proj, ref, out, B, I, H, D, Q, L, \
+                                                                 pmax, ref_dim, padding_mode, align_corners,      \
+                                                                 value_row_stride, stream, points_per_level,      \
+                                                                 level_scale, offset_scale);                      \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_hfbox_##SUF(const void *grad_out, const void *value, const int64_t *shapes,    \
+                                              const void *proj, const void *ref, void *grad_value,                \
+                                              void *grad_proj, void *grad_ref_partial, int64_t B, int64_t I,      \
+                                              int64_t H, int64_t D, int64_t Q, int64_t L,                         \
+                                              const int32_t *points_per_level, const float *level_scale,          \
+                                              double offset_scale, int ref_dim, int padding_mode,                 \
+                                              int align_corners, int64_t max_level_cells,                         \
+                                              int64_t value_row_stride, void *workspace,                          \
+                                              int64_t workspace_bytes, void *stream)                              \
+    {                                                                                                            \
+        int64_t pmax, S;                                                                                         \
+        int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                              \
+        if (rc) return rc;                                                                                       \
+        if ((rc = msda::box_rule_args(level_scale, L, ref_dim)) != 0) return rc;                                 \
+        return msda::run_bwd_fused<T, TV, TS, msda::HfBoxParams>(                                                 \
+            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, pmax,  \
+            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
+            stream, points_per_level, level_scale, offset_scale);                                                \
     }
 
 // one storage type for every tensor

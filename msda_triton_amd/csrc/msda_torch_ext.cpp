@@ -532,6 +532,111 @@ public:
     }
 };
 
+// The fused module core for Hugging Face's box rule with per-level point counts (msda_fwd_fused_hfbox_ /
+// msda_bwd_fused_hfbox_<dtype>, additions within ABI 12): proj [B, Q, H, S, 3], ref [B, Q, 4], `counts` the L point counts
+// and `level_scale` the L fp32 scales as host numbers (float32(1 / P_l): the Python caller computed them on the host and
+// checked that the fused kernels take the counts, so the library never declines), `offset_scale` the module's.  The
+// workspace is the fused per-level-count pair's.
+using FwdFusedHfBoxFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
+                                int64_t, int64_t, int64_t, const int32_t *, const float *, double, int, int, int, int64_t,
+                                void *);
+using BwdFusedHfBoxFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *,
+                                void *, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, const float *,
+                                double, int, int, int, int64_t, int64_t, void *, int64_t, void *);
+std::pair<FwdFusedHfBoxFn, BwdFusedHfBoxFn> fused_hfbox_fns_for(at::ScalarType t, at::ScalarType c)
+{
+    if (t != c) {
+        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
+                          "unsupported dtype combination: value ", t, " with ", c);
+        if (t == at::kBFloat16) return {msda_fwd_fused_hfbox_f32_vbf16, msda_bwd_fused_hfbox_f32_vbf16};
+        return {msda_fwd_fused_hfbox_f32_vf16, msda_bwd_fused_hfbox_f32_vf16};
+    }
+    switch (t) {
+    case at::kFloat: return {msda_fwd_fused_hfbox_f32, msda_bwd_fused_hfbox_f32};
+    case at::kHalf: return {msda_fwd_fused_hfbox_f16, msda_bwd_fused_hfbox_f16};
+    case at::kBFloat16: return {msda_fwd_fused_hfbox_bf16, msda_bwd_fused_hfbox_bf16};
+    case at::kDouble: return {msda_fwd_fused_hfbox_f64, msda_bwd_fused_hfbox_f64};
+    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
+    }
+}
+
+class MSDAFusedHfBoxFunction : public torch::autograd::Function<MSDAFusedHfBoxFunction> {
+public:
+    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
+                              const at::Tensor &proj_, const at::Tensor &ref_, int64_t padding_mode, bool align_corners,
+                              int64_t level_cells, const std::vector<int64_t> &counts, const std::vector<double> &level_scale,
+                              double offset_scale)
+    {
+        TORCH_CHECK_VALUE(level_scale.size() == counts.size(), "level_scale and points_per_level differ in length");
+        const auto [img, vrow] = value_rows(img_);
+        const at::Tensor proj = proj_.contiguous(), ref = ref_.contiguous();
+        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        const std::vector<float> scale(level_scale.begin(), level_scale.end());  // (fp32 values: the conversion is exact)
+        at::Tensor out = at::empty({B, Q, H, D}, proj.options());
+        const c10::DeviceGuard guard(img.device());
+        check_rc(fused_hfbox_fns_for(img.scalar_type(), proj.scalar_type())
+                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(), out.data_ptr(), B,
+                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), scale.data(), offset_scale, (int)ref.size(-1),
+                            (int)padding_mode, align_corners ? 1 : 0, vrow, current_stream(img)),
+                 "msda_fwd_fused_hfbox");
+        ctx->save_for_backward({img, shapes, proj, ref});
+        ctx->saved_data["padding_mode"] = padding_mode;
+        ctx->saved_data["align_corners"] = align_corners;
+        ctx->saved_data["level_cells"] = level_cells;
+        ctx->saved_data["vrow"] = vrow;
+        ctx->saved_data["counts"] = counts;
+        ctx->saved_data["level_scale"] = level_scale;
+        ctx->saved_data["offset_scale"] = offset_scale;
+        return out;
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
+                                                   torch::autograd::variable_list grads)
+    {
+        const auto saved = ctx->get_saved_variables();
+        const at::Tensor &img = saved[0], &shapes = saved[1], &proj = saved[2], &ref = saved[3];
+        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
+        const bool align_corners = ctx->saved_data["align_corners"].toBool();
+        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
+        const int64_t vrow = ctx->saved_data["vrow"].toInt();
+        const auto counts = ctx->saved_data["counts"].toIntVector();
+        const auto level_scale = ctx->saved_data["level_scale"].toDoubleVector();
+        const double offset_scale = ctx->saved_data["offset_scale"].toDouble();
+        const std::vector<int32_t> ppl(counts.begin(), counts.end());
+        const std::vector<float> scale(level_scale.begin(), level_scale.end());
+        const int64_t L = (int64_t)ppl.size();
+        at::Tensor gout = grads[0].contiguous();
+        if (gout.scalar_type() != proj.scalar_type()) gout = gout.to(proj.scalar_type());
+        const bool want_value = ctx->needs_input_grad(0);
+        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
+        const int64_t ref_dim = ref.size(-1);
+        at::Tensor g_img, ws;
+        at::Tensor g_proj = at::empty_like(proj), g_ref_part = at::empty({B, Q, H, ref_dim}, proj.options());
+        int64_t ws_bytes = 0;
+        if (want_value) {
+            g_img = at::empty(img.sizes(), img.options());
+            ws_bytes = msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)proj.element_size(),
+                                                             (int)img.element_size(), level_cells, 0);
+            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
+        }
+        {
+            const c10::DeviceGuard guard(img.device());
+            check_rc(fused_hfbox_fns_for(img.scalar_type(), proj.scalar_type())
+                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(),
+                                 want_value ? g_img.data_ptr() : nullptr, g_proj.data_ptr(), g_ref_part.data_ptr(), B, I, H,
+                                 D, Q, L, ppl.data(), scale.data(), offset_scale, (int)ref_dim, padding_mode,
+                                 align_corners ? 1 : 0, level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr, ws_bytes,
+                                 current_stream(img)),
+                     "msda_bwd_fused_hfbox");
+        }
+        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_proj : at::Tensor(),
+                                           ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor(), at::Tensor(),
+                                           at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()});
+    }
+};
+
 // The fused module core for per-level reference points and transformers' point rule (msda_fwd_fused_levelref_ /
 // msda_bwd_fused_levelref_<dtype>, additions within ABI 12): ref [B, Q, L, ref_dim], the kernel's partials
 // [B, Q, H, L, ref_dim] summed over the heads here.  The Python caller has checked L * P <= msda_fused_lp_limit, so the
@@ -860,6 +965,14 @@ at::Tensor msda_fused_levelref(const at::Tensor &img, const at::Tensor &shapes, 
     return MSDAFusedLevelRefFunction::apply(img, shapes, proj, ref, padding_mode, align_corners, level_cells);
 }
 
+at::Tensor msda_fused_hfbox(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj, const at::Tensor &ref,
+                            int64_t padding_mode, bool align_corners, int64_t level_cells, const std::vector<int64_t> &counts,
+                            const std::vector<double> &level_scale, double offset_scale)
+{
+    return MSDAFusedHfBoxFunction::apply(img, shapes, proj, ref, padding_mode, align_corners, level_cells, counts,
+                                         level_scale, offset_scale);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -888,6 +1001,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "module core with transformers' prologue fused in: reference points [B,Q,L,ref_dim] (differentiable)",
           pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
           pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells") = 0);
+    m.def("msda_fused_hfbox", &msda_fused_hfbox,
+          "module core with Hugging Face's box prologue fused in: per-level point counts, boxes [B,Q,4] (differentiable)",
+          pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
+          pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells"),
+          pybind11::arg("points_per_level"), pybind11::arg("level_scale"), pybind11::arg("offset_scale"));
     m.def("msda_rows", &msda_rows,
           "rows [r0, r1) of the flattened (b, q) row space computed in `chunks` pieces into a full [B,Q,H,D] result "
           "(differentiable; the row-sharded operator without its exchange)",

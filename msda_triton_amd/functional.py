@@ -20,6 +20,7 @@ from __future__ import annotations
 import os
 from typing import Literal, Optional, Tuple
 
+import numpy as np
 import torch
 from torch.amp import custom_bwd, custom_fwd
 from torch.autograd.function import Function, once_differentiable
@@ -871,6 +872,54 @@ def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, 
             return _HipFusedHFModuleCoreFunction.apply(img, img_shapes, proj, reference_points, padding_mode,
                                                        bool(align_corners), level_cells)
     return _hf_composition(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes)
+
+
+# ------------------------------------------------------------------------------------------
+# ... and for the Hugging Face modules with per-level point counts and the box rule (D-FINE, DEIMv2, RT-DETRv2:
+# transformers/models/d_fine/modeling_d_fine.py, DFineMultiscaleDeformableAttention.forward)
+# ------------------------------------------------------------------------------------------
+def hf_box_level_scale(points_per_level) -> Tuple[float, ...]:
+    """transformers' ``num_points_scale`` per level, as host numbers: the modules build an fp32 buffer from ``1 / P_l``,
+    so the scale is ``float32(1 / P_l)`` — in fp64 that value widened, not ``1 / P_l``."""
+    return tuple(float(np.float32(1 / int(p))) for p in points_per_level)
+
+
+def hf_box_sampling_inputs(proj: torch.Tensor, reference_points: torch.Tensor, points_per_level, offset_scale: float = 0.5):
+    """The box prologue of transformers' D-FINE / DEIMv2 / RT-DETRv2 attention modules in plain PyTorch, with transformers'
+    own operations in transformers' own order: raw projection ``[B, N, H, S, 3]`` (x offset, y offset, logit per sample,
+    ``S = sum(points_per_level)``, level-major) and ONE box per query ``[B, N, 4]`` or ``[B, N, 1, 4]`` ->
+    (sampling_points ``[B, N, H, S, 2]``, attention_weights ``[B, N, H, S]``).  It differs from
+    :func:`msda_triton_amd.ragged.ragged_module_sampling_inputs` (``ref_xy + o * ref_wh / (2 P_l)``) in the order of the
+    operations and in the scale, which is the fp32 value :func:`hf_box_level_scale` converted to the working dtype."""
+    counts = tuple(int(p) for p in points_per_level)
+    if proj.dim() != 5 or proj.shape[-1] != 3 or proj.shape[3] != sum(counts) or any(p < 1 for p in counts):
+        raise ValueError(f"expected proj [B,N,H,S,3] with S = sum(points_per_level) = {sum(counts)} and every count at "
+                         f"least 1; got {tuple(proj.shape)}, {list(counts)}")
+    if reference_points.dim() == 3:
+        reference_points = reference_points[:, :, None, :]
+    if reference_points.dim() != 4 or reference_points.shape[2] != 1 or reference_points.shape[-1] != 4 or \
+            tuple(reference_points.shape[:2]) != tuple(proj.shape[:2]):
+        raise ValueError(f"`reference_points` should be [B, N, 4] or [B, N, 1, 4] (one box per query) next to proj "
+                         f"{tuple(proj.shape)}, but got {tuple(reference_points.shape)}.")
+    sampling_offsets, logits = proj[..., :2], proj[..., 2]
+    attention_weights = torch.nn.functional.softmax(logits, dim=-1)
+    scale = [s for s, n in zip(hf_box_level_scale(counts), counts) for _ in range(n)]
+    num_points_scale = torch.tensor(scale, dtype=torch.float32, device=proj.device).to(dtype=proj.dtype).unsqueeze(-1)
+    offset = sampling_offsets * num_points_scale * reference_points[:, :, None, :, 2:] * offset_scale
+    sampling_locations = reference_points[:, :, None, :, :2] + offset
+    return sampling_locations, attention_weights
+
+
+def fused_hf_box_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale: float = 0.5,
+                      padding_mode: str = "zeros", align_corners: bool = False, level_shapes=None) -> torch.Tensor:
+    """``multiscale_deformable_attention(img, img_shapes, *hf_box_sampling_inputs(proj, ...), points_per_level=...)``: the
+    core of a D-FINE / DEIMv2 / RT-DETRv2 attention module between its projections — value pyramid ``[B, I, H, D]``, raw
+    projection ``[B, Q, H, S, 3]`` (level-major), boxes ``[B, Q, 4]`` or ``[B, Q, 1, 4]``.  On GPU tensors the prologue and
+    its chain rule run inside the gather kernels (``msda_*_fused_hfbox_<dtype>``, equal counts included); on host tensors,
+    while traced and where the library declines it is exactly that composition (:mod:`msda_triton_amd.ragged`)."""
+    from .ragged import fused_hf_box_module_core
+    return fused_hf_box_module_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale, padding_mode,
+                                    align_corners, level_shapes)
 
 
 # ------------------------------------------------------------------------------------------

@@ -20,10 +20,14 @@ rounded pixel per sample, :mod:`msda_triton_amd.discrete`) — and is what ``rep
 """
 from __future__ import annotations
 
+import inspect
+
+import numpy as np
 import torch
 from torch import nn
 
-from .functional import _autocast_on, fused_hf_module_core, multiscale_deformable_attention
+from .functional import (_autocast_on, fused_hf_box_core, fused_hf_module_core, hf_box_level_scale,
+                         multiscale_deformable_attention)
 
 
 class MultiScaleDeformableAttention(nn.Module):
@@ -206,6 +210,129 @@ def _wrap_fused(module: nn.Module) -> bool:
     return True
 
 
+def _first_attr(module, *names):
+    for n in names:
+        if hasattr(module, n):
+            return getattr(module, n)
+    return None
+
+
+class FusedHFBoxDeformableAttention(FusedHFDeformableAttention):
+    """The same mixin for the Hugging Face attention modules with a point count per level and the box rule
+    (``DFineMultiscaleDeformableAttention``, ``Deimv2MultiscaleDeformableAttention``,
+    ``RTDetrV2MultiscaleDeformableAttention``): softmax, ``offset * num_points_scale * ref_wh * offset_scale`` and the
+    reference-point broadcast run inside the gather kernels (:func:`fused_hf_box_core`).  ``position_embeddings``,
+    ``value_proj`` and ``output_proj`` are applied where the module has them (RT-DETRv2); D-FINE's and DEIMv2's value is
+    ``encoder_hidden_states`` reshaped.
+
+    The second element of the returned pair is ``None``.  The original forward (over the adapter's core, where the module
+    carries one) runs when attention weights are asked for (``return_attention_weights`` / ``output_attentions=True``),
+    for 2-d reference points, for a reference-point axis of length other than 1 and for ``method="discrete"``."""
+
+    def _proj_rows(self, device) -> torch.Tensor:
+        # row (h, s, k) of the one projection: k < 2 the offset rows of `sampling_offsets`, k == 2 the logit row of
+        # `attention_weights` (behind them in the concatenation)
+        idx = self.__dict__.get("_msda_proj_rows")
+        if idx is None or idx.device != device:
+            n = self.n_heads * sum(int(p) for p in _first_attr(self, "num_points_list", "n_points_list"))
+            s = torch.arange(n, device=device)
+            idx = torch.stack([2 * s, 2 * s + 1, 2 * n + s], -1).reshape(-1)
+            self.__dict__["_msda_proj_rows"] = idx  # (not a buffer: state_dict stays the HF module's)
+        return idx
+
+    def forward(self, hidden_states, attention_mask=None, *args, **kwargs):
+        if args:  # positional arguments follow the wrapped class's own order (D-FINE's and RT-DETRv2's differ)
+            names = type(self).__dict__.get("_msda_arg_names")
+            if names is None:
+                names = tuple(inspect.signature(super(FusedHFDeformableAttention, self).forward).parameters)[2:]
+                type(self)._msda_arg_names = names
+            kwargs.update(zip(names, args))
+        reference_points = kwargs.get("reference_points")
+        if self.return_attention_weights or kwargs.get("output_attentions") or \
+                _first_attr(self, "decoder_method", "method") != "default" or \
+                not torch.is_tensor(reference_points) or reference_points.dim() != 4 or \
+                reference_points.shape[2] != 1 or reference_points.shape[-1] != 4:
+            return super(FusedHFDeformableAttention, self).forward(hidden_states, attention_mask, **kwargs)
+        encoder_hidden_states = kwargs["encoder_hidden_states"]
+        spatial_shapes, spatial_shapes_list = kwargs.get("spatial_shapes"), kwargs.get("spatial_shapes_list")
+        position_embeddings = kwargs.get("position_embeddings")
+        if position_embeddings is not None:
+            hidden_states = hidden_states + position_embeddings
+        batch_size, num_queries, _ = hidden_states.shape
+        sequence_length = encoder_hidden_states.shape[1]
+        value_proj, output_proj = getattr(self, "value_proj", None), getattr(self, "output_proj", None)
+        value = value_proj(encoder_hidden_states) if value_proj is not None else encoder_hidden_states
+        if attention_mask is not None and value_proj is not None:  # (RT-DETRv2 masks the rows, D-FINE the reshaped value)
+            value = value.masked_fill(~attention_mask[..., None], float(0))
+        value = value.reshape(batch_size, sequence_length, self.n_heads, value.shape[-1] // self.n_heads)
+        if attention_mask is not None and value_proj is None:
+            value = value.masked_fill(~attention_mask[..., None], float(0))
+        # ONE GEMM for offsets and logits, laid out [B, Q, H, S, 3]; the weight is gathered from the two HF parameters
+        # (autograd routes its gradient back to them)
+        rows = self._proj_rows(hidden_states.device)
+        so, aw = self.sampling_offsets, self.attention_weights
+        if (so.bias is None) != (aw.bias is None):
+            raise ValueError("`sampling_offsets` and `attention_weights` should both have a bias or neither")
+        weight = torch.cat([so.weight, aw.weight], 0).index_select(0, rows)
+        bias = torch.cat([so.bias, aw.bias], 0).index_select(0, rows) if so.bias is not None else None
+        counts = [int(p) for p in _first_attr(self, "num_points_list", "n_points_list")]
+        proj = nn.functional.linear(hidden_states, weight, bias).view(batch_size, num_queries, self.n_heads, sum(counts), 3)
+        level_shapes = spatial_shapes_list if isinstance(spatial_shapes_list, (list, tuple)) else None
+        shapes = spatial_shapes
+        if not torch.is_tensor(shapes):
+            shapes = _shapes_tensor(shapes if shapes is not None else spatial_shapes_list, value.device)
+        offset_scale = float(self.offset_scale)
+        if value.device.type == "cuda" and value.dtype in (torch.bfloat16, torch.float16) and proj.dtype == value.dtype \
+                and reference_points.dtype == torch.float32:
+            # what autocast hands the core: 16-bit value and projection next to fp32 boxes — the module-storage kernels
+            # (fp32 arithmetic, 16-bit result), called outside autocast so that nothing is cast to fp32
+            with torch.autocast("cuda", enabled=False):
+                out = fused_hf_box_core(value, shapes, proj, reference_points, counts, offset_scale, "zeros", False,
+                                        level_shapes=level_shapes)
+        else:
+            if proj.dtype != value.dtype:
+                proj = proj.to(value.dtype)
+            if reference_points.dtype != value.dtype:
+                reference_points = reference_points.to(value.dtype)
+            out = fused_hf_box_core(value, shapes, proj, reference_points, counts, offset_scale, "zeros", False,
+                                    level_shapes=level_shapes)
+        out = out.flatten(2)
+        return (output_proj(out) if output_proj is not None else out), None
+
+
+_FUSED_BOX_ATTRS = ("sampling_offsets", "attention_weights", "n_heads", "offset_scale")
+
+
+def _wrap_fused_box(module: nn.Module) -> bool:
+    """Wrap a module with per-level point counts and the box rule, matched by attribute names.  The scale buffer is
+    compared ONCE, here, with float32(1 / P_l) repeated P_l times — a loaded checkpoint could carry other values, and the
+    kernels take the scale from the counts."""
+    if isinstance(module, FusedHFDeformableAttention) or not all(hasattr(module, a) for a in _FUSED_BOX_ATTRS):
+        return False
+    counts, scale = _first_attr(module, "num_points_list", "n_points_list"), _first_attr(module, "num_points_scale", "n_points_scale")
+    if not isinstance(counts, (list, tuple)) or not torch.is_tensor(scale) or not isinstance(module.offset_scale, (int, float)) \
+            or _first_attr(module, "decoder_method", "method") != "default":
+        return False
+    counts = [int(p) for p in counts]
+    if not counts or any(p < 1 for p in counts):
+        return False
+    expect = np.asarray([s for s, n in zip(hf_box_level_scale(counts), counts) for _ in range(n)], dtype=np.float32)
+    have = scale.detach().to("cpu")  # (`.double()` widens the buffer, the values stay; a 16-bit model's rounded copy differs)
+    if not have.is_floating_point() or tuple(have.shape) != expect.shape or \
+            not np.array_equal(have.double().numpy(), expect.astype(np.float64)):
+        return False
+    so, aw = module.sampling_offsets, module.attention_weights
+    n = int(module.n_heads) * sum(counts)
+    if not isinstance(so, nn.Linear) or not isinstance(aw, nn.Linear) or so.out_features != 2 * n or aw.out_features != n:
+        return False
+    cls = type(module)
+    fused = _FUSED_CLASSES.get(cls)
+    if fused is None:
+        fused = _FUSED_CLASSES[cls] = type("Fused" + cls.__name__, (FusedHFBoxDeformableAttention, cls), {})
+    module.__class__ = fused
+    return True
+
+
 def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = False) -> int:
     """Swap every HF ``MultiScaleDeformableAttention`` submodule of ``model`` for the adapter, and set
     :func:`ms_deformable_attn_core` on every module that carries an ``ms_deformable_attn_core`` attribute with
@@ -214,8 +341,13 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
     :func:`ms_deformable_attn_core_v2`.  With ``fused=True`` (opt-in) every attention module that owns such a core as
     its child ``attn`` next to ``sampling_offsets``, ``attention_weights``, ``value_proj``, ``output_proj``, ``n_heads``,
     ``n_levels`` and ``n_points`` (Deformable-DETR, Grounding-DINO, the RT-DETR family; matched by these names, not by
-    class) additionally becomes a :class:`FusedHFDeformableAttention`.  Returns the number of modules replaced, patched
-    or wrapped."""
+    class) additionally becomes a :class:`FusedHFDeformableAttention`, and every module that has ``sampling_offsets``,
+    ``attention_weights``, ``n_heads``, ``offset_scale``, a point list (``num_points_list`` / ``n_points_list``), a scale
+    buffer (``num_points_scale`` / ``n_points_scale``) equal to ``float32(1 / P_l)`` repeated ``P_l`` times and method
+    ``"default"`` (D-FINE, DEIMv2, RT-DETRv2; by these names as well) a :class:`FusedHFBoxDeformableAttention`.  Returns
+    the number of modules replaced, patched or wrapped: without ``fused`` exactly what it always returned, with it that
+    number plus the modules wrapped (a D-FINE decoder layer then counts twice, once for its core and once for the
+    wrapper)."""
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -234,6 +366,6 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
             count += 1
     if fused:
         for module in list(model.modules()):
-            if _wrap_fused(module):
+            if _wrap_fused(module) or _wrap_fused_box(module):
                 count += 1
     return count

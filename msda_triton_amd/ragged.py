@@ -444,3 +444,212 @@ def fused_ragged_module_core(img, img_shapes, proj, reference_points, padding_mo
     pts, att = ragged_module_sampling_inputs(proj, img_shapes, reference_points, counts)
     return F.multiscale_deformable_attention(img, img_shapes, pts, att, padding_mode, align_corners,
                                              level_shapes=level_shapes, points_per_level=counts)
+
+
+# ------------------------------------------------------------------------------------------
+# the same core for Hugging Face's box rule (D-FINE, DEIMv2, RT-DETRv2): functional.hf_box_sampling_inputs states it
+# ------------------------------------------------------------------------------------------
+def _scale_array(counts) -> ctypes.Array:
+    return (ctypes.c_float * len(counts))(*F.hf_box_level_scale(counts))
+
+
+def _box_ref(reference_points):
+    """``[B, Q, 1, 4]`` -> ``[B, Q, 4]`` (a view; the kernels take one box per query)."""
+    return reference_points[:, :, 0, :] if reference_points.dim() == 4 and reference_points.shape[2] == 1 else reference_points
+
+
+def check_hf_box_args(img_shapes, proj, reference_points, points_per_level) -> Tuple[int, ...]:
+    """Validate the box core's layout; returns the counts as a tuple of ints.  Raises ``ValueError``."""
+    ref = _box_ref(reference_points)
+    if ref.dim() != 3 or ref.shape[-1] != 4:
+        raise ValueError("`reference_points` should be [B,N,4] or [B,N,1,4] (one box per query), but got "
+                         f"{tuple(reference_points.shape)}.")
+    return check_proj_points_per_level(img_shapes, proj, ref, points_per_level)
+
+
+def hf_box_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
+                         offset_scale: float = 0.5) -> Optional[torch.Tensor]:
+    """Forward with the softmax and transformers' box rule done in the kernel prologue
+    (``msda_fwd_fused_hfbox_<suffix>``; ``reference_points`` ``[B, Q, 4]``).  None when the library declines (S too large
+    for one pass, more than 8 levels) or predates these entry points: the caller then takes the unfused route."""
+    if not _lib.has_fused_hfbox():
+        return None
+    B, I, H, D = img.shape
+    B2, Q, H2, S, _ = proj.shape
+    if (B2, H2) != (B, H) or tuple(reference_points.shape) != (B, Q, 4):
+        raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
+                         f"reference_points {tuple(reference_points.shape)}")
+    F._check_devices(img, img_shapes, proj, reference_points)
+    pad = F._padding_code(padding_mode)
+    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    shapes = F._shapes_i64(img_shapes)
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    fn = getattr(_lib.load(), f"msda_fwd_fused_hfbox_{suf}")
+
+    def call():
+        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+                  B, I, H, D, Q, len(counts), _counts_array(counts), _scale_array(counts), float(offset_scale), 4, pad,
+                  int(bool(align_corners)), vrow, F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_fwd_fused_hfbox", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_fwd_fused_hfbox_{suf}")
+    return out
+
+
+def hf_box_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
+                         offset_scale: float = 0.5, need_img: bool = True, level_cells: int = 0, need_ref: bool = True,
+                         parked_points: bool = False):
+    """Backward of the box core with the prologue's chain rule done in the kernel (``msda_bwd_fused_hfbox_<suffix>``):
+    ``(img_grad | None, proj_grad, reference_points_grad | None)``, or None when the library declines (nothing was
+    launched).  ``parked_points`` (with ``need_img``): a fourth element, the sampling points ``[B, Q, H, S, 2]`` the kernel
+    left at the head of its workspace for the grad_value passes — the points the forward sampled, in the arithmetic
+    dtype."""
+    if not _lib.has_fused_hfbox():
+        return None
+    B, I, H, D = img.shape
+    _, Q, _, S, _ = proj.shape
+    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
+    pad = F._padding_code(padding_mode)
+    cdt = proj.dtype
+    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
+    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and reference points fp32)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    out_grad = out_grad.contiguous()
+    if out_grad.dtype != cdt:
+        out_grad = out_grad.to(cdt)
+    shapes = F._shapes_i64(img_shapes)
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, 4), dtype=reference_points.dtype, device=img.device)
+    lib = _lib.load()
+    fn = getattr(lib, f"msda_bwd_fused_hfbox_{suf}")
+    arr, scale = _counts_array(counts), _scale_array(counts)
+    ws, ws_bytes = None, 0
+    level_cells = int(level_cells)
+    if need_img:  # (a frozen value pyramid needs no workspace at all); the fused per-level-count pair's query answers
+        ws_bytes = int(lib.msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, len(counts), arr,
+                                                                 4 if storage else proj.element_size(),
+                                                                 img.element_size(), level_cells, 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
+
+    def call():
+        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
+                  B, I, H, D, Q, len(counts), arr, scale, float(offset_scale), 4, pad, int(bool(align_corners)),
+                  level_cells, vrow, ws.data_ptr() if ws is not None else None, ws_bytes, F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_bwd_fused_hfbox", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_bwd_fused_hfbox_{suf}")
+    res = (g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None))
+    if parked_points and ws is not None:
+        n = B * Q * H * S * 2 * reference_points.element_size()
+        res += (ws[:n].view(reference_points.dtype).view(B, Q, H, S, 2).clone(),)
+    return res
+
+
+def _hf_box_composition(img, img_shapes, proj, reference_points, counts, offset_scale, padding_mode, align_corners,
+                        level_shapes):
+    """transformers' box prologue as PyTorch ops around the ragged operator (host tensors, traced calls, whatever the fused
+    kernels do not take).  16-bit value / projection next to fp32 boxes: the prologue in fp32, the mixed-storage operator,
+    the result back in the projection's dtype."""
+    if img.device.type == "cuda" and F.fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype):
+        pts, att = F.hf_box_sampling_inputs(proj.to(reference_points.dtype), reference_points, counts, offset_scale)
+        return F.multiscale_deformable_attention(img, img_shapes, pts, att, padding_mode, align_corners,
+                                                 level_shapes=level_shapes, points_per_level=counts).to(proj.dtype)
+    pts, att = F.hf_box_sampling_inputs(proj, reference_points, counts, offset_scale)
+    return F.multiscale_deformable_attention(img, img_shapes, pts, att, padding_mode, align_corners,
+                                             level_shapes=level_shapes, points_per_level=counts)
+
+
+class _HipFusedHfBoxCoreFunction(Function):
+    """:class:`_HipFusedRaggedModuleCoreFunction` for transformers' box rule (``msda_*_fused_hfbox_<dtype>``).  When the
+    library declines (or lacks the entry points) the prologue runs in PyTorch around the ragged operator's kernels."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts, offset_scale,
+                level_cells=0):
+        ctx.level_cells, ctx.counts, ctx.offset_scale = int(level_cells), counts, float(offset_scale)
+        out = hf_box_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts, offset_scale)
+        ctx.fused = out is not None  # the backward has the same limits: do not ask twice
+        if out is None:
+            pts, att = F.hf_box_sampling_inputs(proj.to(reference_points.dtype), reference_points, counts, offset_scale)
+            out = ragged_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners, counts).to(proj.dtype)
+        ctx.save_for_backward(img, img_shapes, proj, reference_points)
+        ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, out_grad):
+        img, img_shapes, proj, reference_points = ctx.saved_tensors
+        need_img, _, need_proj, need_ref = ctx.needs_input_grad[:4]
+        counts = ctx.counts
+        if ctx.fused and (need_proj or need_ref):
+            res = hf_box_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, ctx.padding_mode,
+                                       ctx.align_corners, counts, ctx.offset_scale, need_img, level_cells=ctx.level_cells,
+                                       need_ref=need_ref)
+            if res is not None:
+                g_img, g_proj, g_ref = res
+                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None, None
+        with torch.enable_grad():
+            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
+            ref_ = reference_points.detach().requires_grad_(need_ref)
+            pts, att = F.hf_box_sampling_inputs(proj_, ref_, counts, ctx.offset_scale)
+        need_sample = need_proj or need_ref
+        g_img, g_pts, g_att = ragged_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(),
+                                             ctx.padding_mode, ctx.align_corners, counts,
+                                             (need_img, need_sample, need_sample), ctx.level_cells)
+        g_proj = g_ref = None
+        if need_sample:
+            wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
+            grads = list(torch.autograd.grad([pts, att], wrt, [g_pts, g_att], allow_unused=True))
+            if need_proj:
+                g_proj = grads.pop(0).to(proj.dtype)
+            if need_ref:
+                g_ref = grads.pop(0)
+        return g_img, None, g_proj, g_ref, None, None, None, None, None
+
+
+def fused_hf_box_module_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale=0.5,
+                             padding_mode="zeros", align_corners=False, level_shapes=None) -> torch.Tensor:
+    """:func:`msda_triton_amd.functional.fused_hf_box_core`.  Routing mirrors ``fused_hf_module_core``: host tensors -> the
+    composition; GPU -> the fused kernels (the C++ node, else the Python ``Function``); traced -> the composition over the
+    registered ragged custom ops.  Equal counts stay on these kernels: the uniform fused kernels implement other rules."""
+    counts = check_hf_box_args(img_shapes, proj, reference_points, points_per_level)
+    offset_scale = float(offset_scale)
+    B, Q, H, S, _ = proj.shape
+    L = len(counts)
+    on_gpu = img.device.type == "cuda"
+    if on_gpu and img_shapes.device != img.device:
+        img_shapes = img_shapes.to(img.device)  # (a handful of integers: follow `img`, as the other cores do)
+    floating = img.is_floating_point() and proj.is_floating_point() and reference_points.is_floating_point()
+    if on_gpu and floating and not torch.compiler.is_compiling():
+        F._check_devices(img, proj, reference_points)
+        same = F.dtypes_supported(img.dtype, proj.dtype) and reference_points.dtype == proj.dtype
+        if F._autocast_on() or F.fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype) or same:
+            pad = F._padding_code(padding_mode)
+            level_cells = F.level_cells_of(level_shapes, L, img.shape[1])
+            ref = _box_ref(reference_points)
+            ext = _ext.load()
+            if same and ext is not None and hasattr(ext, "msda_fused_hfbox") and F.KernelTimer.active is None and \
+                    not F._autocast_on() and _lib.has_fused_hfbox() and img.dim() == 4 and \
+                    (img.shape[0], img.shape[2]) == (B, H) and fused_ragged_limits_ok(img.shape[3], proj.element_size(), counts):
+                # the C++ autograd node: decoder-sized calls spend more host time than device time
+                return ext.msda_fused_hfbox(img, F._shapes_i64(img_shapes), proj, ref, pad, bool(align_corners),
+                                            level_cells, list(counts), list(F.hf_box_level_scale(counts)), offset_scale)
+            return _HipFusedHfBoxCoreFunction.apply(img, img_shapes, proj, ref, padding_mode, bool(align_corners), counts,
+                                                    offset_scale, level_cells)
+    # host tensors, tracing (the ragged operator's registered custom ops) and everything the checks above did not take
+    return _hf_box_composition(img, img_shapes, proj, reference_points, counts, offset_scale, padding_mode, align_corners,
+                               level_shapes)
