@@ -183,6 +183,27 @@ extern "C" {
                        int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,   \
                        int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
                        void *workspace, int64_t workspace_bytes, void *stream);\
+    MSDA_API int msda_fwd_masked_##SUF(const void *value, const uint8_t *value_mask,                \
+                       const int64_t *shapes, const void *loc, const void *attn, void *out,         \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                       int padding_mode, int align_corners, int64_t value_row_stride, void *stream);\
+    MSDA_API int msda_bwd_masked_##SUF(const void *grad_out, const void *value,                     \
+                       const uint8_t *value_mask, const int64_t *shapes, const void *loc,           \
+                       const void *attn, void *grad_value, void *grad_loc, void *grad_attn,         \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                       int padding_mode, int align_corners, int64_t max_level_cells,                \
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);\
+    MSDA_API int msda_fwd_fused_levelref_masked_##SUF(const void *value, const uint8_t *value_mask, \
+                       const int64_t *shapes, const void *proj, const void *ref, void *out,         \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                       int ref_dim, int padding_mode, int align_corners, int64_t value_row_stride,  \
+                       void *stream);                                                               \
+    MSDA_API int msda_bwd_fused_levelref_masked_##SUF(const void *grad_out, const void *value,      \
+                       const uint8_t *value_mask, const int64_t *shapes, const void *proj,          \
+                       const void *ref, void *grad_value, void *grad_proj, void *grad_ref_partial,  \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                       int ref_dim, int padding_mode, int align_corners, int64_t max_level_cells,   \
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);\
     MSDA_API int msda_fwd_fused_hfbox_##SUF(const void *value, const int64_t *shapes, const void *proj,   \
                        const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
                        int64_t Q, int64_t L, const int32_t *points_per_level,                       \
@@ -271,6 +292,28 @@ extern "C" {
  * is its workspace: msda_bwd_fused_ragged_workspace_bytes answers for these calls too.  Equal counts are served as any
  * others (the uniform pairs implement other rules).
  *
+ * The VALUE PADDING MASK twins — ADDITIONS WITHIN ABI 12, probed by symbol: msda_fwd_masked_<dtype> / msda_bwd_masked_<dtype>
+ * (the six suffixes of msda_fwd_<dtype>) and msda_fwd_fused_levelref_masked_<suffix> / msda_bwd_fused_levelref_masked_<suffix>
+ * (the eight suffixes of the per-level-reference pair) take their twins' argument lists with one argument behind `value`:
+ *
+ *   value_mask   [B, I] bytes on the device, one per pixel of the pyramid: non-zero = the pixel is real, 0 = padding
+ *                (transformers' attention_mask polarity; mmcv's key_padding_mask is the inverse)
+ *
+ * A padding pixel counts as a row of zeros WHATEVER BITS IT HOLDS — NaN and Inf there reach no output:
+ *
+ *   out, grad_loc, grad_attn (grad_proj, grad_ref_partial)   those of the twin on where(mask, value, 0), bit for bit
+ *   grad_value                                                where(mask, the twin's grad_value, +0)
+ *
+ * The mask acts on the corner's address, never as a factor: in phase 1 of the forward and of the sample gradients a corner
+ * whose pixel is padding takes the offset of a corner dropped by "zeros" padding and reads 0 without touching memory; the
+ * grad_value finish pass (or the single-launch kernel's final store) stores a padding pixel's row as zeros, so neither
+ * direction has a pass of its own over the pyramid.  The mask is read through a range-checked descriptor of I bytes per
+ * batch element and takes no gradient.  A NULL value_mask is MSDA_ERR_BAD_ARG, refused before any other argument is looked
+ * at: a caller without a mask calls the twin.  Size guards, limits, value_row_stride (the mask indexes PIXELS, not bytes),
+ * max_level_cells, MSDA_WS_RECORDS_IN_GRADS and MSDA_WS_PASSES(n) are the twins', and so are the workspaces:
+ * msda_bwd_workspace_bytes / msda_bwd_fused_workspace_bytes answer for these calls too.  The one-wave-per-unit forward is
+ * never chosen for a masked call (msda_last_launch_info("fwd_variant") says 0 or 1).
+ *
  * Discrete (nearest-pixel) sampling — ADDITIONS WITHIN ABI 12: no existing signature changes and MSDA_ABI_VERSION stays
  * 12, so a caller PROBES FOR THESE BY SYMBOL (dlsym / hasattr) instead of by version; a library built before them simply
  * lacks them.  msda_fwd_discrete_<dtype> / msda_bwd_discrete_<dtype> take the ragged layout above (`points_per_level`,
@@ -342,6 +385,17 @@ MSDA_DECLARE(f32_vf16)
                        int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,   \
                        int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
                        void *workspace, int64_t workspace_bytes, void *stream);\
+    MSDA_API int msda_fwd_fused_levelref_masked_##SUF(const void *value, const uint8_t *value_mask, \
+                       const int64_t *shapes, const void *proj, const void *ref, void *out,         \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                       int ref_dim, int padding_mode, int align_corners, int64_t value_row_stride,  \
+                       void *stream);                                                               \
+    MSDA_API int msda_bwd_fused_levelref_masked_##SUF(const void *grad_out, const void *value,      \
+                       const uint8_t *value_mask, const int64_t *shapes, const void *proj,          \
+                       const void *ref, void *grad_value, void *grad_proj, void *grad_ref_partial,  \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                       int ref_dim, int padding_mode, int align_corners, int64_t max_level_cells,   \
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);\
     MSDA_API int msda_fwd_fused_hfbox_##SUF(const void *value, const int64_t *shapes, const void *proj,   \
                        const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
                        int64_t Q, int64_t L, const int32_t *points_per_level,                       \

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = tuple(
     + ["msda_bwd_fused_ragged_workspace_bytes"]
     + [f"msda_{d}_fused_levelref_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
     + [f"msda_{d}_fused_hfbox_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+    + [f"msda_{d}_masked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES]
+    + [f"msda_{d}_fused_levelref_masked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
     + ["msda_abi_version", "msda_last_error", "msda_set_option", "msda_get_option", "msda_bwd_workspace_bytes",
        "msda_bwd_fused_workspace_bytes", "msda_bwd_supported", "msda_fused_lp_limit", "msda_profile_read",
        "msda_last_launch_info"]
@@ -174,6 +176,22 @@ def load():
                 gfh = getattr(lib, f"msda_bwd_fused_hfbox_{suf}")
                 gfh.restype = ci
                 gfh.argtypes = [vp] * 8 + [i64] * 6 + [vp, vp, cd, ci, ci, ci, i64, i64, vp, i64, vp]
+        # the value-mask twins: additions within ABI 12 (has_value_mask); the twins' lists with `value_mask` behind `value`
+        if hasattr(lib, "msda_bwd_masked_f32"):
+            for suf in DTYPE_SUFFIXES:
+                fm = getattr(lib, f"msda_fwd_masked_{suf}")
+                fm.restype = ci
+                fm.argtypes = [vp] * 6 + [i64] * 7 + [ci, ci, i64, vp]
+                gm = getattr(lib, f"msda_bwd_masked_{suf}")
+                gm.restype = ci
+                gm.argtypes = [vp] * 9 + [i64] * 7 + [ci, ci, i64, i64, vp, i64, vp]
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                flm = getattr(lib, f"msda_fwd_fused_levelref_masked_{suf}")
+                flm.restype = ci
+                flm.argtypes = [vp] * 6 + [i64] * 7 + [ci, ci, ci, i64, vp]
+                glm = getattr(lib, f"msda_bwd_fused_levelref_masked_{suf}")
+                glm.restype = ci
+                glm.argtypes = [vp] * 9 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -221,6 +239,13 @@ def has_fused_hfbox() -> bool:
     (msda_fwd_fused_hfbox_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller composes
     transformers' prologue around the ragged operator."""
     return hasattr(load(), "msda_bwd_fused_hfbox_f32")
+
+
+def has_value_mask() -> bool:
+    """Does the loaded library have the value-mask twins (msda_fwd_masked_<dtype> ..., msda_fwd_fused_levelref_masked_<dtype>
+    ..., additions within ABI 12, found by symbol)?  Without them a masked call composes ``masked_fill`` with the unmasked
+    route."""
+    return hasattr(load(), "msda_bwd_masked_f32")
 
 
 def check(rc: int, what: str) -> None:

@@ -282,9 +282,12 @@ __device__ __forceinline__ uint32_t mad24(uint32_t a, uint32_t b, uint32_t c)
 
 // base / masked: added to every corner's offset / what a corner masked by "zeros" padding gets instead (defaults: the
 // plane itself; the LDSL kernels pass the LDS position of their copy and of its row of zeros)
-template <typename A>
+// kPix (the value-mask kernels, mask_taps below): the four corners' pixel indices `start + y * w + x` are handed out too —
+// the clamped ones, so every index names a pixel of the level whatever the coordinate
+template <typename A, bool kPix = false>
 __device__ __forceinline__ void make_taps(A x, A y, int h, int w, int start, bool zeros, bool align,
-                                          uint32_t row_bytes, Taps<A> &t, uint32_t base = 0, uint32_t masked = kMaskedOffset)
+                                          uint32_t row_bytes, Taps<A> &t, uint32_t base = 0, uint32_t masked = kMaskedOffset,
+                                          uint32_t *pix = nullptr)
 {
     const A W = (A)w, Hh = (A)h;
     A px, py;
@@ -309,6 +312,12 @@ __device__ __forceinline__ void make_taps(A x, A y, int h, int w, int start, boo
     t.off[1] = mad24(r0 + (uint32_t)x1c, row_bytes, base);
     t.off[2] = mad24(r1 + (uint32_t)x0c, row_bytes, base);
     t.off[3] = mad24(r1 + (uint32_t)x1c, row_bytes, base);
+    if constexpr (kPix) {
+        pix[0] = r0 + (uint32_t)x0c;
+        pix[1] = r0 + (uint32_t)x1c;
+        pix[2] = r1 + (uint32_t)x0c;
+        pix[3] = r1 + (uint32_t)x1c;
+    }
     if (zeros) {
         const bool mx0 = (x0 >= (A)0) && (x0 <= xm), mx1 = (x1 >= (A)0) && (x1 <= xm);
         const bool my0 = (y0 >= (A)0) && (y0 <= ym), my1 = (y1 >= (A)0) && (y1 <= ym);
@@ -324,6 +333,22 @@ __device__ __forceinline__ void make_taps(A x, A y, int h, int w, int start, boo
     }
     t.dx = px - x0;
     t.dy = py - y0;
+}
+
+// Value padding mask (msda_*_masked_<dtype>): a corner whose pixel's mask byte is 0 reads zeros whatever bits the pixel
+// holds — it takes the offset a corner dropped by "zeros" padding gets, so NaN / Inf in padding never reach a register.
+// `rm` covers the batch element's I mask bytes (range-checked: an index beyond them reads 0, a padding pixel); `first`
+// is added to every index (the LDSL kernels: indices relative to the first LDS-resident level).  Four byte loads per
+// sample in phase 1, in flight together; phase 2 is the unmasked kernels'.
+template <typename A>
+__device__ __forceinline__ void mask_taps(Taps<A> &t, const uint32_t (&pix)[4], uint32_t first, rsrc_t rm, uint32_t masked)
+{
+    uint8_t m[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[k] = __builtin_amdgcn_raw_buffer_load_b8(rm, pix[k] + first, 0, 0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (m[k] == 0) t.off[k] = masked;
 }
 
 // ------------------------------------------------------------------------------------------

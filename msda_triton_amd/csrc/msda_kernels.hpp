@@ -186,16 +186,47 @@ template <typename A> __device__ __forceinline__ int discrete_pixel(A x, int n)
 // nothing behind Params: the uniform and the per-level-count instantiations keep their types and their code, and the
 // three rules hang on overloads / `if constexpr (kLevelRef<PP>)`.  Uniform point count only.
 struct LevelRefParams : Params {};
-template <typename PP> constexpr bool kLevelRef = std::is_base_of<LevelRefParams, PP>::value;
+
+// ---- value padding mask (msda_*_masked_<dtype>, msda_*_fused_levelref_masked_<dtype>) ----
+// `vmask` is [B, I] bytes, non-zero = the pixel is real; a pixel whose byte is 0 counts as a row of zeros whatever bits it
+// holds.  A kernarg type of its own with the pointer BEHIND Params (the preloaded front is unchanged): the unmasked
+// instantiations keep their types and their code, and the hooks hang on `if constexpr (kValueMask<PP>)`:
+//   forward / sample gradients   phase 1, behind make_taps: a masked corner takes the offset a corner dropped by "zeros"
+//                                padding gets — kMaskedOffset, or the LDS row of zeros (mask_taps, msda_common.hpp)
+//   grad_value                   the finish pass gives a masked pixel empty ranges (its row is stored as zeros, its slots are
+//                                never loaded); the single-launch kernel stores zeros for it
+// The fused pair for per-level reference points has its masked kernarg below the plain one, so that the grad_value passes
+// behind the fused backward run on the plain masked pipeline (value_pass_params, msda_launch.hpp).
+struct MaskedParams : Params {
+    const uint8_t *vmask;
+};
+struct LevelRefMaskedParams : MaskedParams {};
+template <typename PP> constexpr bool kValueMask = std::is_base_of<MaskedParams, PP>::value;
+// the batch element's mask bytes as a range-checked descriptor (nothing at all in the unmasked kernels)
+template <typename PP, bool = kValueMask<PP>> struct MaskSrc {
+    __device__ __forceinline__ MaskSrc(const PP &, int) {}
+};
+template <typename PP> struct MaskSrc<PP, true> {
+    rsrc_t r;
+    __device__ __forceinline__ MaskSrc(const PP &p, int b) : r(make_rsrc(p.vmask + (size_t)b * p.I, (uint32_t)p.I)) {}
+};
+
+template <typename PP>
+constexpr bool kLevelRef = std::is_base_of<LevelRefParams, PP>::value || std::is_base_of<LevelRefMaskedParams, PP>::value;
 
 // Elements of `ref` per query, and the reference point of (query fq, level l) behind the batch element's base.
 __device__ __forceinline__ int ref_row_elems(const Params &p) { return p.ref_dim; }
 __device__ __forceinline__ int ref_row_elems(const LevelRefParams &p) { return p.L * p.ref_dim; }
+__device__ __forceinline__ int ref_row_elems(const LevelRefMaskedParams &p) { return p.L * p.ref_dim; }
 template <typename T> __device__ __forceinline__ const T *ref_of(const Params &p, const T *refp, int fq, int)
 {
     return refp + (size_t)fq * p.ref_dim;
 }
 template <typename T> __device__ __forceinline__ const T *ref_of(const LevelRefParams &p, const T *refp, int fq, int l)
+{
+    return refp + ((size_t)fq * p.L + l) * p.ref_dim;
+}
+template <typename T> __device__ __forceinline__ const T *ref_of(const LevelRefMaskedParams &p, const T *refp, int fq, int l)
 {
     return refp + ((size_t)fq * p.L + l) * p.ref_dim;
 }
@@ -526,6 +557,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
     pair = pair0 + half;
     const int b = (int)fast_div((uint32_t)pair, p.div_h);
     int h = pair - b * p.H;
+    [[maybe_unused]] const MaskSrc<PP> vmask(p, b);  // (value-mask twins only; two planes per workgroup share the batch element)
 
     const int scp = p.sc + 1;  // +1 record of padding: units land on different LDS banks
     const GatherLds<A> lds(NU, scp);
@@ -762,7 +794,14 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                             a = TR::to_acc(attn[sidx]);
                         }
                         Taps<A> t;
-                        if constexpr (LDSL) {  // an LDS-served level: offsets into the workgroup's copy (selects, not two code paths)
+                        if constexpr (kValueMask<PP>) {  // the masked twins: the same taps, then the padding pixels' corners dropped
+                            uint32_t pix[4];
+                            const bool inl = LDSL && l >= fl;
+                            const int first = inl ? tab->start[cs.first] : 0;
+                            make_taps<A, true>(sx, sy, tab->h[l], tab->w[l], tab->start[l] - first, p.zeros, p.align, inl ? cs.row_bytes : row_bytes,
+                                               t, inl ? cs.base : 0u, inl ? cs.zero : kMaskedOffset, pix);
+                            mask_taps<A>(t, pix, (uint32_t)first, vmask.r, inl ? cs.zero : kMaskedOffset);
+                        } else if constexpr (LDSL) {  // an LDS-served level: offsets into the workgroup's copy (selects, not two code paths)
                             const bool inl = l >= fl;
                             make_taps<A>(sx, sy, tab->h[l], tab->w[l], tab->start[l] - (inl ? tab->start[cs.first] : 0), p.zeros, p.align,
                                          inl ? cs.row_bytes : row_bytes, t, inl ? cs.base : 0u, inl ? cs.zero : kMaskedOffset);
@@ -1047,6 +1086,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
     pair = pair0 + half;
     const int b = (int)fast_div((uint32_t)pair, p.div_h);
     int h = pair - b * p.H;
+    [[maybe_unused]] const MaskSrc<PP> vmask(p, b);  // (value-mask twins only; two planes per workgroup share the batch element)
 
     const int scp = p.sc + 1;
     // record in : {dx, dy, a*sx*gx_on, a*sy*gy_on};  record out (same slot): {gA, gX, gY, -}
@@ -1297,7 +1337,14 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         a = TR::to_acc(attn[sidx]);
                     }
                     Taps<A> t;
-                    if constexpr (LDSL) {  // an LDS-served level: offsets into the workgroup's copy (selects, not two code paths)
+                    if constexpr (kValueMask<PP>) {  // the masked twins: the same taps, then the padding pixels' corners dropped
+                        uint32_t pix[4];
+                        const bool inl = LDSL && l >= fl;
+                        const int first = inl ? tab->start[cs.first] : 0;
+                        make_taps<A, true>(px, py, lh, lw, tab->start[l] - first, p.zeros, p.align, inl ? cs.row_bytes : row_bytes, t,
+                                           inl ? cs.base : 0u, inl ? cs.zero : kMaskedOffset, pix);
+                        mask_taps<A>(t, pix, (uint32_t)first, vmask.r, inl ? cs.zero : kMaskedOffset);
+                    } else if constexpr (LDSL) {  // an LDS-served level: offsets into the workgroup's copy (selects, not two code paths)
                         const bool inl = l >= fl;
                         make_taps<A>(px, py, lh, lw, tab->start[l] - (inl ? tab->start[cs.first] : 0), p.zeros, p.align,
                                      inl ? cs.row_bytes : row_bytes, t, inl ? cs.base : 0u, inl ? cs.zero : kMaskedOffset);

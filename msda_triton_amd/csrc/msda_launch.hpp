@@ -393,7 +393,8 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         }
     }
     // small problems (decoder calls): the forward with one wave per unit (msda_fwd_unit_kernel)
-    if constexpr (MODE == 0 && VEC * sizeof(T) == 16 && sizeof(A) == 4) {
+    // (never for a value-mask call: the one-wave-per-unit kernel has no mask hook — fwd_variant says 0 or 1 there)
+    if constexpr (MODE == 0 && VEC * sizeof(T) == 16 && sizeof(A) == 4 && !kValueMask<PP>) {
         const long long units = (long long)p.B * p.Q * p.H;
         const int gl = p.D / VEC;
         const int uopt = option_unit_fwd();
@@ -523,7 +524,8 @@ template <typename T, int MODE, typename TV = T, typename TS = T, typename PP = 
 }
 
 // ---- sorted (gather-formulated) grad_value: K1..K5 of msda_value_sorted.hpp ----
-template <typename T, int VEC, int G, int GB, typename TV = T, typename TS = T> inline int launch_value_gather_block(Params &p, hipStream_t stream)
+// PP = MaskedParams: the finish pass is the value-mask twin (the gather itself knows no mask)
+template <typename T, int VEC, int G, int GB, typename TV = T, typename TS = T, typename PP = Params> inline int launch_value_gather_block(PP &p, hipStream_t stream)
 {
     constexpr int NUG = GB / G;
     const int npairs = p.B * p.H;
@@ -540,7 +542,7 @@ template <typename T, int VEC, int G, int GB, typename TV = T, typename TS = T> 
         // head nothing balances.  The rotated mapping mixes the heads (c2 @ 10k: 60.7 -> 56.7 us).
         const int keep = p.xcd_map;
         if (p.xcd_map == 1) p.xcd_map = 2;
-        hipLaunchKernelGGL((msda_value_gather_kernel<T, VEC, G, GB, TS>), g4, dim3(GB), 0, stream, p);
+        hipLaunchKernelGGL((msda_value_gather_kernel<T, VEC, G, GB, TS>), g4, dim3(GB), 0, stream, static_cast<const Params &>(p));
         p.xcd_map = keep;
     }
     // (4-lane groups: 64 of them per workgroup, so 64 pixels keep them all busy)
@@ -550,20 +552,27 @@ template <typename T, int VEC, int G, int GB, typename TV = T, typename TS = T> 
         return MSDA_ERR_TOO_LARGE;
     }
     const ProfileScope prof("msda_value_finish_kernel", stream);
-    if (fp == 64)
-        hipLaunchKernelGGL((msda_value_finish_kernel<T, VEC, G, GB, TV, 64>), g5, dim3(kBlock), 0, stream, p);
-    else
-        hipLaunchKernelGGL((msda_value_finish_kernel<T, VEC, G, GB, TV, 32>), g5, dim3(kBlock), 0, stream, p);
+    if constexpr (kValueMask<PP>) {
+        if (fp == 64)
+            hipLaunchKernelGGL((msda_value_finish_masked_kernel<T, VEC, G, GB, TV, 64>), g5, dim3(kBlock), 0, stream, static_cast<const MaskedParams &>(p));
+        else
+            hipLaunchKernelGGL((msda_value_finish_masked_kernel<T, VEC, G, GB, TV, 32>), g5, dim3(kBlock), 0, stream, static_cast<const MaskedParams &>(p));
+    } else {
+        if (fp == 64)
+            hipLaunchKernelGGL((msda_value_finish_kernel<T, VEC, G, GB, TV, 64>), g5, dim3(kBlock), 0, stream, static_cast<const Params &>(p));
+        else
+            hipLaunchKernelGGL((msda_value_finish_kernel<T, VEC, G, GB, TV, 32>), g5, dim3(kBlock), 0, stream, static_cast<const Params &>(p));
+    }
     return (int)hipGetLastError();
 }
 
-template <typename T, int VEC, int G, typename TV = T, typename TS = T> inline int launch_value_gather(Params &p, hipStream_t stream)
+template <typename T, int VEC, int G, typename TV = T, typename TS = T, typename PP = Params> inline int launch_value_gather(PP &p, hipStream_t stream)
 {
     // (64- and 128-thread gather workgroups were measured too: 71-74 us against 73.6 at c2-10k — no effect, removed)
     return launch_value_gather_block<T, VEC, G, 256, TV, TS>(p, stream);
 }
 
-template <typename T, int VEC, typename TV = T, typename TS = T> inline int dispatch_value_gather_group(Params &p, hipStream_t stream)
+template <typename T, int VEC, typename TV = T, typename TS = T, typename PP = Params> inline int dispatch_value_gather_group(PP &p, hipStream_t stream)
 {
     const int lanes = (p.D + VEC - 1) / VEC;
     switch (pick_group(lanes)) {
@@ -585,6 +594,8 @@ template <typename T> inline bool value_vec_ok(const Params &p)
 template <typename T, typename TV = T, typename TS = T, typename PP = Params> inline int run_value_sorted(PP &p, const Dims &d, void *workspace, hipStream_t stream)
 {
     using A = typename Traits<T>::acc;
+    // the count / scan / place / gather passes know no mask: a value-mask call runs the unmasked kernels on its Params part
+    using KP = std::conditional_t<kValueMask<PP>, Params, PP>;
     const bool vec_ok = value_vec_ok<T>(p);
     const SortedWsLayout w = sorted_ws_layout(d.B, d.I, d.H, d.D, d.Q, d.L, samples(d), sizeof(A), sizeof(T), vec_ok, p.ent_alt0 != nullptr, sizeof(TV));
     unsigned char *ws = static_cast<unsigned char *>(workspace);
@@ -629,8 +640,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     // (the count pass keeps its per-block totals behind the cell table)
     const size_t cell_lds = sizeof(LevelTab) + ((size_t)p.cell_cap + (size_t)p.nblk_cap) * sizeof(int);
     static std::atomic<uint64_t> big_lds_count{0}, big_lds_place{0};
-    allow_big_lds(msda_cell_pass_kernel<T, false, PP>, big_lds_count);  // (the instantiation that is launched)
-    allow_big_lds(msda_cell_pass_kernel<T, true, PP>, big_lds_place);
+    allow_big_lds(msda_cell_pass_kernel<T, false, KP>, big_lds_count);  // (the instantiation that is launched)
+    allow_big_lds(msda_cell_pass_kernel<T, true, KP>, big_lds_place);
     const int64_t scan_blocks = (int64_t)p.nblk_cap * npairs;
     if (scan_blocks >= ((int64_t)1 << 31)) {
         set_error("grid too large");
@@ -679,8 +690,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         g3_place = p.grid3d;
         map_place = p.xcd_map;
         static std::atomic<uint64_t> big_lds_lm{0}, big_lds_lm_small{0};
-        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlock, PP>, big_lds_lm);
-        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlockSmall, PP>, big_lds_lm_small);
+        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlock, KP>, big_lds_lm);
+        allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlockSmall, KP>, big_lds_lm_small);
     }
     for (int r = 0; r < w.rounds; ++r) {  // one round unless Q is so large that a plane's grad_out rows leave L2
         p.q_begin = r * w.q_round;
@@ -691,7 +702,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         p.cell_cap = cell_cap_pm;
         {
             const ProfileScope prof("msda_cell_pass_kernel<count>", stream);
-            hipLaunchKernelGGL((msda_cell_pass_kernel<T, false, PP>), gcell, dim3(kCellBlock), cell_lds, stream, p);
+            hipLaunchKernelGGL((msda_cell_pass_kernel<T, false, KP>), gcell, dim3(kCellBlock), cell_lds, stream, static_cast<const KP &>(p));
         }
         {
             const ProfileScope prof("msda_cell_scan_kernel", stream);
@@ -704,11 +715,11 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
             p.xcd_map = map_place;
             p.cell_cap = place_cells;
             if (place_small)
-                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlockSmall, PP>), gplace, dim3(kPlaceBlockSmall), (size_t)place_cells * 4, stream, p);
+                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlockSmall, KP>), gplace, dim3(kPlaceBlockSmall), (size_t)place_cells * 4, stream, static_cast<const KP &>(p));
             else
-                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlock, PP>), gplace, dim3(kPlaceBlock), (size_t)place_cells * 4, stream, p);
+                hipLaunchKernelGGL((msda_cell_place_lm_kernel<T, kPlaceBlock, KP>), gplace, dim3(kPlaceBlock), (size_t)place_cells * 4, stream, static_cast<const KP &>(p));
         } else {
-            hipLaunchKernelGGL((msda_cell_pass_kernel<T, true, PP>), gcell, dim3(kCellBlock), cell_lds, stream, p);
+            hipLaunchKernelGGL((msda_cell_pass_kernel<T, true, KP>), gcell, dim3(kCellBlock), cell_lds, stream, static_cast<const KP &>(p));
         }
         }
         int rc = (int)hipGetLastError();
@@ -810,12 +821,18 @@ inline void fill_box_scales(HfBoxParams &p, const float *lscale, double off_scal
     p.off_scale = off_scale;
 }
 inline void fill_box_scales(Params &, const float *, double, int64_t) {}
+// the value padding mask (msda_*_masked_<dtype>): [B, I] bytes behind the kernarg; advanced with every other batch-indexed
+// pointer when the grad_value pipeline runs once per group of batch elements
+inline void set_value_mask(MaskedParams &p, const uint8_t *vmask) { p.vmask = vmask; }
+inline void set_value_mask(Params &, const uint8_t *) {}
+inline void advance_value_mask(MaskedParams &pg, const MaskedParams &p, size_t pixels) { pg.vmask = p.vmask + pixels; }
+inline void advance_value_mask(Params &, const Params &, size_t) {}
 
 // PP = RaggedParams: per-level point counts `ppl` (ragged_counts checked them; P is their maximum)
 template <typename T, typename TV = T, typename PP = Params>
 int run_fwd(const void *value, const int64_t *shapes, const void *loc, const void *attn, void *out, int64_t B,
             int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int padding_mode, int align_corners,
-            int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr)
+            int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr, const uint8_t *vmask = nullptr)
 {
     Dims d{B, I, H, D, Q, L, P};
     if (ppl != nullptr)
@@ -845,6 +862,7 @@ int run_fwd(const void *value, const int64_t *shapes, const void *loc, const voi
     p.out = out;
     fill_params(p, d, padding_mode, align_corners);
     fill_level_starts(p, ppl, L);
+    set_value_mask(p, vmask);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.touch = touch_plan(d);
@@ -867,7 +885,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, const void *ref, void *out, int64_t B,
                   int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,
                   int align_corners, int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr,
-                  const float *lscale = nullptr, double off_scale = 0.0)
+                  const float *lscale = nullptr, double off_scale = 0.0, const uint8_t *vmask = nullptr)
 {
     Dims d{B, I, H, D, Q, L, P};
     if (ppl != nullptr)
@@ -904,6 +922,7 @@ int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, co
     fill_params(p, d, padding_mode, align_corners);
     fill_level_starts(p, ppl, L);
     fill_box_scales(p, lscale, off_scale, L);
+    set_value_mask(p, vmask);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.ref = ref;
@@ -1064,6 +1083,7 @@ inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_by
             pg.attn = static_cast<const unsigned char *>(p.attn) + ns0 * sizeof(T);
             pg.grad_out = static_cast<const unsigned char *>(p.grad_out) + (size_t)(b0 * Q * H * D) * sizeof(TS);
             pg.grad_value = static_cast<unsigned char *>(p.grad_value) + (size_t)(b0 * I * H * D) * sizeof(TV);
+            advance_value_mask(pg, p, (size_t)(b0 * I));
             if (p.ent_alt0 != nullptr) {  // this group's own share of the caller's gradient buffers (run_bwd)
                 pg.ent_alt0 = static_cast<unsigned char *>(p.ent_alt0) + ns0 * 2 * sizeof(T);
                 pg.ent_alt1 = static_cast<unsigned char *>(p.ent_alt1) + ns0 * sizeof(T);
@@ -1094,7 +1114,8 @@ template <typename T, typename TV = T, typename PP = Params>
 int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, const void *loc, const void *attn,
             void *grad_value, void *grad_loc, void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,
             int64_t L, int64_t P, int padding_mode, int align_corners, int64_t max_level_cells, int64_t value_row_stride,
-            void *workspace, int64_t workspace_bytes, void *stream_, const int32_t *ppl = nullptr)
+            void *workspace, int64_t workspace_bytes, void *stream_, const int32_t *ppl = nullptr,
+            const uint8_t *vmask = nullptr)
 {
     Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
     if (ppl != nullptr)
@@ -1137,6 +1158,7 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
     p.grad_attn = grad_attn;
     fill_params(p, d, padding_mode, align_corners);
     fill_level_starts(p, ppl, L);
+    set_value_mask(p, vmask);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     // Both halves wanted, one after the other: the sorted records are dead once the gather has run and grad_loc /
@@ -1360,6 +1382,7 @@ inline size_t fused_mat_bytes(int64_t B, int64_t H, int64_t Q, int64_t S, size_t
 // only: grad_value is the UNIFORM pipeline on the parked points (no kernels of its own).
 template <typename PP> inline PP &value_pass_params(PP &p) { return p; }
 inline Params &value_pass_params(LevelRefParams &p) { return p; }
+inline MaskedParams &value_pass_params(LevelRefMaskedParams &p) { return p; }  // (... the plain value-mask pipeline)
 // ... and so does Hugging Face's box rule: grad_value is the PER-LEVEL-COUNT pipeline on the parked points.
 inline RaggedParams &value_pass_params(HfBoxParams &p) { return p; }
 
@@ -1373,7 +1396,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                   void *grad_value, void *grad_proj, void *grad_ref_part, int64_t B, int64_t I, int64_t H, int64_t D,
                   int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode, int align_corners,
                   int64_t max_level_cells, int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream_,
-                  const int32_t *ppl = nullptr, const float *lscale = nullptr, double off_scale = 0.0)
+                  const int32_t *ppl = nullptr, const float *lscale = nullptr, double off_scale = 0.0,
+                  const uint8_t *vmask = nullptr)
 {
     Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
     if (ppl != nullptr)
@@ -1430,6 +1454,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
     fill_params(p, d, padding_mode, align_corners);
     fill_level_starts(p, ppl, L);
     fill_box_scales(p, lscale, off_scale, L);
+    set_value_mask(p, vmask);
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
     if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
     p.ref = ref;
@@ -1543,8 +1568,10 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                              D, Q, L, points_per_level, max_level_cells, value_row_stride,       \
                                              workspace, workspace_bytes, stream);                                \
     }                                                                                                            \
+    MSDA_DEFINE_MASKED_ENTRY_POINTS(SUF, T, TV)                                                                   \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)                                                          \
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, T)                                                        \
+    MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TV, T)                                                 \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
@@ -1572,6 +1599,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
     }                                                                                                            \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)                                                         \
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)                                                       \
+    MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TS, TS)                                                \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)
 
 // the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
@@ -1674,6 +1702,65 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
             grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, pmax,  \
             ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
             stream, points_per_level, level_scale, offset_scale);                                                \
+    }
+
+// the value-mask twins: msda_{fwd,bwd}_masked_<suffix> and msda_{fwd,bwd}_fused_levelref_masked_<suffix> — the twins'
+// argument lists with `value_mask` ([B, I] bytes, non-zero = real pixel) behind `value`; a null mask is an argument error
+// (the caller without a mask calls the twin), refused before any other argument is looked at
+#define MSDA_MASK_REQUIRED(NAME)                                                                                 \
+    if (value_mask == nullptr) {                                                                                 \
+        msda::set_error(NAME ": value_mask is null (call the unmasked entry point instead)");                    \
+        return MSDA_ERR_BAD_ARG;                                                                                 \
+    }
+#define MSDA_DEFINE_MASKED_ENTRY_POINTS(SUF, T, TV)                                                              \
+    extern "C" int msda_fwd_masked_##SUF(const void *value, const uint8_t *value_mask, const int64_t *shapes,   \
+                                         const void *loc, const void *attn, void *out, int64_t B, int64_t I,    \
+                                         int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int padding_mode, \
+                                         int align_corners, int64_t value_row_stride, void *stream)             \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_fwd_masked")                                                                    \
+        return msda::run_fwd<T, TV, msda::MaskedParams>(value, shapes, loc, attn, out, B, I, H, D, Q, L, P,      \
+                                                        padding_mode, align_corners, value_row_stride, stream,   \
+                                                        nullptr, value_mask);                                    \
+    }                                                                                                            \
+    extern "C" int msda_bwd_masked_##SUF(const void *grad_out, const void *value, const uint8_t *value_mask,    \
+                                         const int64_t *shapes, const void *loc, const void *attn,              \
+                                         void *grad_value, void *grad_loc, void *grad_attn, int64_t B, int64_t I, \
+                                         int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int padding_mode, \
+                                         int align_corners, int64_t max_level_cells, int64_t value_row_stride,   \
+                                         void *workspace, int64_t workspace_bytes, void *stream)                 \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_bwd_masked")                                                                    \
+        return msda::run_bwd<T, TV, msda::MaskedParams>(grad_out, value, shapes, loc, attn, grad_value, grad_loc, \
+                                                        grad_attn, B, I, H, D, Q, L, P, padding_mode,            \
+                                                        align_corners, max_level_cells, value_row_stride,        \
+                                                        workspace, workspace_bytes, stream, nullptr, value_mask); \
+    }
+#define MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TV, TS)                                            \
+    extern "C" int msda_fwd_fused_levelref_masked_##SUF(const void *value, const uint8_t *value_mask,           \
+                                                        const int64_t *shapes, const void *proj, const void *ref, \
+                                                        void *out, int64_t B, int64_t I, int64_t H, int64_t D,   \
+                                                        int64_t Q, int64_t L, int64_t P, int ref_dim,            \
+                                                        int padding_mode, int align_corners,                     \
+                                                        int64_t value_row_stride, void *stream)                  \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_fwd_fused_levelref_masked")                                                     \
+        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(                                        \
+            value, shapes, proj, ref, out, B, I, H, D, Q, L, P, ref_dim, padding_mode, align_corners,            \
+            value_row_stride, stream, nullptr, nullptr, 0.0, value_mask);                                        \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_levelref_masked_##SUF(                                                         \
+        const void *grad_out, const void *value, const uint8_t *value_mask, const int64_t *shapes,              \
+        const void *proj, const void *ref, void *grad_value, void *grad_proj, void *grad_ref_partial, int64_t B, \
+        int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,         \
+        int align_corners, int64_t max_level_cells, int64_t value_row_stride, void *workspace,                   \
+        int64_t workspace_bytes, void *stream)                                                                   \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_bwd_fused_levelref_masked")                                                     \
+        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(                                        \
+            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, P,     \
+            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
+            stream, nullptr, nullptr, 0.0, value_mask);                                                          \
     }
 
 // one storage type for every tensor

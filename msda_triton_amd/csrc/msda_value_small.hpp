@@ -53,7 +53,9 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
     constexpr int NG = kSmallBlock / G;  // lane groups per workgroup
     // row loads in flight per lane: 8 — 4 for rows of eight 16-bit channels per lane, whose widened copies (8 floats each) next
     // to the four accumulator rows do not fit the 128 VGPRs of a 1024-thread workgroup (6-26 spilled registers otherwise)
-    constexpr int UB = G < 8 ? G : (VEC >= 8 ? 4 : 8);
+    // (the value-mask twin with eight channels per lane: 2 — the mask look-up at the final store costs the registers that
+    //  the third and fourth row in flight held; the sums and their order are the same)
+    constexpr int UB = G < 8 ? G : (VEC >= 8 ? (kValueMask<PP> ? 2 : 4) : 8);
     // p.small_ns workgroups per (plane, level): each builds the level's sorted records for itself (cheap) and takes
     // every small_ns-th 2 x 2-pixel block of the gather, so few planes still fill the chip
     int pair, slot;
@@ -386,6 +388,9 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
                 store_stream(static_cast<TV *>(p.grad_value) + (((size_t)b * p.I + pstart + py * lw + px) * p.H + h) * p.D + c0, zero);
         }
     }
+    // (the value-mask twin: the mask bytes of this level's pixels, a uniform base)
+    [[maybe_unused]] const uint8_t *mrow = nullptr;
+    if constexpr (kValueMask<PP>) mrow = p.vmask + (size_t)b * p.I + pstart;
     const int items = nbusy * S;
     const int rounds = (items + NG - 1) / NG;
     for (int r = 0; r < rounds; ++r) {
@@ -481,6 +486,12 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) ov.v[i] = TVR::from_acc(acc[k][i]);
                         TV *dst = static_cast<TV *>(p.grad_value) + (((size_t)b * p.I + pstart + pix) * p.H + h) * p.D + c0;
+                        if constexpr (kValueMask<PP>) {  // the value-mask twin: a padding pixel's row is stored as zeros
+                            if (pstart + pix < p.I && mrow[pix] == 0) {
+#pragma unroll
+                                for (int i = 0; i < VEC; ++i) ov.v[i] = TVR::from_acc((A)0);
+                            }
+                        }
                         if (pstart + pix < p.I) store_stream(dst, ov);  // (shapes that disagree with I: stay inside the plane)
                     }
                 }

@@ -183,6 +183,36 @@ def _value_rows(img: torch.Tensor):
     return img.contiguous(), 0
 
 
+def _validate_value_mask(value_mask: torch.Tensor, img: torch.Tensor) -> None:
+    if not torch.is_tensor(value_mask) or value_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"`value_mask` should be a bool or uint8 tensor, but got "
+                         f"{value_mask.dtype if torch.is_tensor(value_mask) else type(value_mask).__name__}.")
+    if value_mask.dim() != 2 or img.dim() != 4 or tuple(value_mask.shape) != tuple(img.shape[:2]):
+        raise ValueError(f"`value_mask` should be [{img.shape[0] if img.dim() else '?'}, {img.shape[1] if img.dim() > 1 else '?'}] "
+                         f"(a flag per pixel of `img`), but got {tuple(value_mask.shape)}.")
+    if value_mask.device != img.device:
+        raise ValueError(f"`value_mask` should be on `img`'s device {img.device}, but got {value_mask.device}.")
+
+
+def check_value_mask(value_mask: torch.Tensor, img: torch.Tensor) -> torch.Tensor:
+    """``value_mask``: ``[B, I]``, bool or uint8, on ``img``'s device — non-zero = the pixel is real (transformers'
+    ``attention_mask`` polarity; mmcv's ``key_padding_mask`` is the inverse).  Returns it as the kernels take it:
+    contiguous uint8 (a bool mask as its uint8 view, without a copy)."""
+    _validate_value_mask(value_mask, img)
+    value_mask = value_mask.contiguous()
+    return value_mask.view(torch.uint8) if value_mask.dtype == torch.bool else value_mask
+
+
+def apply_value_mask(img: torch.Tensor, value_mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """``where(value_mask, img, 0)`` over heads and channels — the composition every route without masked kernels uses
+    (autograd gives ``grad_img`` its zeros); ``img`` itself without a mask."""
+    if value_mask is None:
+        return img
+    _validate_value_mask(value_mask, img)
+    padding = ~value_mask if value_mask.dtype == torch.bool else value_mask == 0
+    return img.masked_fill(padding[:, :, None, None], 0)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _FUSED_LP_LIMIT: dict = {}  # (D, element size) -> msda_fused_lp_limit
 _WS_BYTES: dict = {}  # (B, I, H, D, Q, L, P, elem, option epoch) -> msda_bwd_workspace_bytes
@@ -266,11 +296,14 @@ class KernelTimer:
 # launcher pair — the native seam (reference: kernels.py:351-379, 556-592)
 # ------------------------------------------------------------------------------------------
 def msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, value_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Allocate ``out`` (or write into the caller's contiguous ``[B, Q, H, D]`` buffer, e.g. a slice of a gather
-    buffer) and enqueue the forward kernel on the current stream (no host sync)."""
+    buffer) and enqueue the forward kernel on the current stream (no host sync).  ``value_mask``: the value-mask twin
+    (``msda_fwd_masked_<dtype>``; :func:`check_value_mask`)."""
     B, I, H, D, Q, L, P = _dims(img, sampling_points, attention_weights, img_shapes)
     _check_devices(img, img_shapes, sampling_points, attention_weights)
+    if value_mask is not None:
+        value_mask = check_value_mask(value_mask, img)
     pad = _padding_code(padding_mode)
     cdt = sampling_points.dtype  # dtype of everything but `img` (the same, or fp32 next to a 16-bit `img`)
     if attention_weights.dtype != cdt:
@@ -285,16 +318,18 @@ def msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mo
         raise ValueError(f"`out` should be a contiguous {(B, Q, H, D)} {cdt} tensor on {img.device}, but got "
                          f"{tuple(out.shape)} {out.dtype} on {out.device} (contiguous: {out.is_contiguous()}).")
     lib = _lib.load()
-    fn = getattr(lib, f"msda_fwd_{suf}")
+    name = "msda_fwd" if value_mask is None else "msda_fwd_masked"
+    fn = getattr(lib, f"{name}_{suf}")
+    mask_arg = () if value_mask is None else (value_mask.data_ptr(),)
 
     def call():
-        return fn(img.data_ptr(), shapes.data_ptr(), sampling_points.data_ptr(), attention_weights.data_ptr(),
+        return fn(img.data_ptr(), *mask_arg, shapes.data_ptr(), sampling_points.data_ptr(), attention_weights.data_ptr(),
                   out.data_ptr(), B, I, H, D, Q, L, P, pad, int(bool(align_corners)), vrow, _stream_ptr(img.device))
 
     with _OnDevice(img.device):
         timer = KernelTimer.active
-        rc = timer.launch("msda_fwd", img.device, call) if timer else call()
-    _lib.check(rc, f"msda_fwd_{suf}")
+        rc = timer.launch(name, img.device, call) if timer else call()
+    _lib.check(rc, f"{name}_{suf}")
     return out
 
 
@@ -330,10 +365,11 @@ def level_cells_of(level_shapes, num_levels: Optional[int] = None, num_pixels: O
 def msda_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners,
                  needs: Tuple[bool, bool, bool] = (True, True, True),
                  out: Optional[Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]] = None,
-                 level_cells: int = 0,
+                 level_cells: int = 0, value_mask: Optional[torch.Tensor] = None,
                  ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
     """Returns ``(img_grad, sampling_points_grad, attention_weights_grad)``; entries not in ``needs`` are None.
-    ``level_cells``: see :func:`level_cells_of` (0: unknown).
+    ``level_cells``: see :func:`level_cells_of` (0: unknown).  ``value_mask``: the value-mask twin
+    (``msda_bwd_masked_<dtype>``): padding pixels count as zeros and their ``img_grad`` rows are zeros.
 
     Gradients are allocated contiguous (the reference's ``zeros_like(...).contiguous()`` would write
     into a temporary for permuted inputs, kernels.py:570-578) and are fully written by the kernels,
@@ -342,6 +378,10 @@ def msda_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, 
     """
     B, I, H, D, Q, L, P = _dims(img, sampling_points, attention_weights, img_shapes)
     _check_devices(img, img_shapes, sampling_points, attention_weights, out_grad)
+    if value_mask is not None:
+        value_mask = check_value_mask(value_mask, img)
+    bwd_name = "msda_bwd" if value_mask is None else "msda_bwd_masked"
+    mask_arg = () if value_mask is None else (value_mask.data_ptr(),)
     pad = _padding_code(padding_mode)
     cdt = sampling_points.dtype
     if attention_weights.dtype != cdt:
@@ -371,7 +411,7 @@ def msda_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, 
     g_att = buf(2, (B, Q, H, L, P), want_sample, cdt)
     if want_value or want_sample:
         lib = _lib.load()
-        fn = getattr(lib, f"msda_bwd_{suf}")  # (the level-size bound travels as an argument: include/msda_hip.h)
+        fn = getattr(lib, f"{bwd_name}_{suf}")  # (the level-size bound travels as an argument: include/msda_hip.h)
         ws, ws_bytes = None, 0
         level_cells = int(level_cells)
         if want_value:  # scratch: the inverted index of grad_value (grad_loc / grad_attn never need any)
@@ -390,7 +430,7 @@ def msda_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, 
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
 
         def call(value_part: bool, sample_part: bool):
-            return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), sampling_points.data_ptr(),
+            return fn(out_grad.data_ptr(), img.data_ptr(), *mask_arg, shapes.data_ptr(), sampling_points.data_ptr(),
                       attention_weights.data_ptr(),
                       g_img.data_ptr() if value_part else None,
                       g_pts.data_ptr() if sample_part else None,
@@ -406,10 +446,10 @@ def msda_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, 
             else:  # one C-ABI call per kernel so each gets its own event pair
                 rc = 0
                 if want_sample:
-                    rc = timer.launch("msda_bwd_sample", img.device, lambda: call(False, True))
+                    rc = timer.launch(f"{bwd_name}_sample", img.device, lambda: call(False, True))
                 if rc == 0 and want_value:
-                    rc = timer.launch("msda_bwd_value", img.device, lambda: call(True, False))
-        _lib.check(rc, f"msda_bwd_{suf}")
+                    rc = timer.launch(f"{bwd_name}_value", img.device, lambda: call(True, False))
+        _lib.check(rc, f"{bwd_name}_{suf}")
     return g_img, (g_pts if needs[1] else None), (g_att if needs[2] else None)
 
 
@@ -420,14 +460,17 @@ class _HipMultiscaleDeformableAttentionFunction(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)  # under autocast the op runs in fp32 (frontend.py:111)
-    def forward(ctx, img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners, level_cells=0):
+    def forward(ctx, img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners, level_cells=0,
+                value_mask=None):
         if ctx.needs_input_grad[0]:
             check_backward_supported(img, sampling_points)
         ctx.save_for_backward(img, img_shapes, sampling_points, attention_weights)
         ctx.padding_mode = padding_mode
         ctx.align_corners = align_corners
         ctx.level_cells = int(level_cells)
-        return msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners)
+        ctx.value_mask = value_mask  # (uint8 [B, I] or None; takes no gradient)
+        return msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners,
+                            value_mask=value_mask)
 
     @staticmethod
     @once_differentiable
@@ -437,8 +480,8 @@ class _HipMultiscaleDeformableAttentionFunction(Function):
         needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3])
         g_img, g_pts, g_att = msda_hip_bwd(
             out_grad, img, img_shapes, sampling_points, attention_weights,
-            ctx.padding_mode, ctx.align_corners, needs, level_cells=ctx.level_cells)
-        return g_img, None, g_pts, g_att, None, None, None
+            ctx.padding_mode, ctx.align_corners, needs, level_cells=ctx.level_cells, value_mask=ctx.value_mask)
+        return g_img, None, g_pts, g_att, None, None, None, None
 
 
 def hip_multiscale_deformable_attention(
@@ -450,11 +493,34 @@ def hip_multiscale_deformable_attention(
     align_corners: bool,
     level_shapes=None,
     points_per_level=None,
+    value_mask=None,
 ) -> torch.Tensor:
     """GPU path.  Same contract as the reference's ``triton_multiscale_deformable_attention``
     (frontend.py:71-105): ``ValueError`` on unsupported dtype or non-GPU inputs.  ``level_shapes`` (an addition): the
-    pyramid's (h, w) pairs as host numbers, see :func:`level_cells_of`.  ``points_per_level``: see
+    pyramid's (h, w) pairs as host numbers, see :func:`level_cells_of`.  ``points_per_level``, ``value_mask``: see
     :func:`multiscale_deformable_attention`."""
+    if value_mask is not None:
+        if img.device.type != "cuda":
+            raise ValueError(f"hip_multiscale_deformable_attention needs GPU tensors, but `img` is on {img.device}.")
+        _validate_value_mask(value_mask, img)
+        # the value-mask kernels serve the uniform call outside a trace; everything else composes masked_fill with its route
+        if points_per_level is not None or torch.compiler.is_compiling() or not _lib.has_value_mask():
+            return hip_multiscale_deformable_attention(apply_value_mask(img, value_mask), img_shapes, sampling_points,
+                                                       attention_weights, padding_mode, align_corners, level_shapes,
+                                                       points_per_level)
+        for name, t in (("img", img), ("sampling_points", sampling_points), ("attention_weights", attention_weights)):
+            if t.dtype not in VALID_DTYPES:
+                raise ValueError(f"Dtype of `{name}` should be in {list(VALID_DTYPES)}, but got {t.dtype}.")
+        if sampling_points.dtype != attention_weights.dtype or not dtypes_supported(img.dtype, sampling_points.dtype):
+            raise ValueError(
+                "`img`, `sampling_points` and `attention_weights` should share one dtype (or `img` be float16 / bfloat16 "
+                f"next to float32 sampling inputs), but got {img.dtype}, {sampling_points.dtype}, {attention_weights.dtype}.")
+        _check_devices(img, img_shapes, sampling_points, attention_weights)
+        _padding_code(padding_mode)
+        # (the Python Function: the C++ autograd node takes no mask)
+        return _HipMultiscaleDeformableAttentionFunction.apply(
+            img, img_shapes, sampling_points, attention_weights, padding_mode, bool(align_corners),
+            level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1]), check_value_mask(value_mask, img))
     if points_per_level is not None:
         if img.device.type != "cuda":
             raise ValueError(f"hip_multiscale_deformable_attention needs GPU tensors, but `img` is on {img.device}.")
@@ -528,11 +594,12 @@ def module_sampling_inputs(proj: torch.Tensor, img_shapes: torch.Tensor, referen
 
 
 def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners,
-                       levelref: bool = False) -> Optional[torch.Tensor]:
+                       levelref: bool = False, value_mask: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """Forward with softmax + sampling-point math done in the kernel prologue.  Returns None when the
     library declines (L*P too large for one pass): the caller then takes the unfused route.  ``levelref``: the
     reference points are per level, ``[B, Q, L, ref_dim]``, and the points follow transformers' rule
-    (:func:`hf_module_sampling_inputs`; ``msda_fwd_fused_levelref_<dtype>``)."""
+    (:func:`hf_module_sampling_inputs`; ``msda_fwd_fused_levelref_<dtype>``).  ``value_mask`` (with ``levelref`` only):
+    the value-mask twin ``msda_fwd_fused_levelref_masked_<dtype>``."""
     B, I, H, D = img.shape
     B2, Q, H2, L, P, three = proj.shape
     if (B2, H2, three) != (B, H, 3) or tuple(reference_points.shape[:2]) != (B, Q) or \
@@ -553,12 +620,20 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
     out = torch.empty((B, Q, H, D), dtype=cdt, device=img.device)
     lib = _lib.load()
     name = "msda_fwd_fused_levelref" if levelref else "msda_fwd_fused"
-    fn = getattr(lib, f"{name}_{suf}", None)
+    mask_arg = ()
+    if value_mask is not None:
+        if not levelref:
+            raise ValueError("`value_mask` is served by the per-level-reference fused kernels only (levelref=True)")
+        sym, mask_arg = name + "_masked", (check_value_mask(value_mask, img).data_ptr(),)
+    else:
+        sym = name
+    # (the timer's group stays the pair's — "msda_fwd_fused_levelref" — with or without a mask: it names the launcher)
+    fn = getattr(lib, f"{sym}_{suf}", None)
     if fn is None:  # (a library built before the per-level entry points: the caller composes)
         return None
 
     def call():
-        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+        return fn(img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
                   B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), vrow, _stream_ptr(img.device))
 
     with _OnDevice(img.device):
@@ -566,12 +641,13 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
         rc = timer.launch(name, img.device, call) if timer else call()
     if rc == -5:  # MSDA_ERR_UNSUPPORTED
         return None
-    _lib.check(rc, f"{name}_{suf}")
+    _lib.check(rc, f"{sym}_{suf}")
     return out
 
 
 def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners,
-                       need_img: bool = True, level_cells: int = 0, need_ref: bool = True, levelref: bool = False):
+                       need_img: bool = True, level_cells: int = 0, need_ref: bool = True, levelref: bool = False,
+                       value_mask: Optional[torch.Tensor] = None):
     """Backward of the module core with the prologue's chain rule done in the kernel: returns
     ``(img_grad | None, proj_grad, reference_points_grad)``, or None when the library declines (L*P too large
     for one pass; nothing was launched).  ``levelref``: as in :func:`msda_hip_fwd_fused`; the kernel's partials are
@@ -596,7 +672,14 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
                              device=img.device)
     lib = _lib.load()
     name = "msda_bwd_fused_levelref" if levelref else "msda_bwd_fused"
-    fn = getattr(lib, f"{name}_{suf}", None)
+    mask_arg = ()
+    if value_mask is not None:  # (the value-mask twin; the workspace is the twin's)
+        if not levelref:
+            raise ValueError("`value_mask` is served by the per-level-reference fused kernels only (levelref=True)")
+        sym, mask_arg = name + "_masked", (check_value_mask(value_mask, img).data_ptr(),)
+    else:
+        sym = name
+    fn = getattr(lib, f"{sym}_{suf}", None)  # (the timer's group stays the pair's, as in the forward)
     if fn is None:
         return None
     ws, ws_bytes = None, 0
@@ -607,7 +690,7 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
 
     def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+        return fn(out_grad.data_ptr(), img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
                   g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
                   B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
                   ws.data_ptr() if ws is not None else None, ws_bytes, _stream_ptr(img.device))
@@ -617,7 +700,7 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
         rc = timer.launch(name, img.device, call) if timer else call()
     if rc == -5:  # MSDA_ERR_UNSUPPORTED
         return None
-    _lib.check(rc, f"{name}_{suf}")
+    _lib.check(rc, f"{sym}_{suf}")
     # (the kernel leaves per-head partials of grad_reference_points; their sum is a launch of its own — 16 us at the c2
     # shape — and reference points rarely require a gradient)
     return g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None)
@@ -675,12 +758,14 @@ class _HipFusedModuleCoreFunction(Function):
 
 
 def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None,
-                      points_per_level=None) -> torch.Tensor:
+                      points_per_level=None, value_mask=None) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *module_sampling_inputs(proj, ...))`` — on GPU tensors
     with the prologue fused into the forward kernel; on host tensors exactly that composition.  ``level_shapes``: the
     level sizes as host numbers, optional (:func:`level_cells_of`).  ``points_per_level``: a point count per level; then
     ``proj`` is ``[B, Q, H, S, 3]`` with ``S = sum(points_per_level)``, level-major
-    (:func:`msda_triton_amd.ragged.ragged_module_sampling_inputs` states the prologue)."""
+    (:func:`msda_triton_amd.ragged.ragged_module_sampling_inputs` states the prologue).  ``value_mask``: ``[B, I]``,
+    non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels (these have no masked form)."""
+    img = apply_value_mask(img, value_mask)
     if points_per_level is not None:
         from .ragged import fused_ragged_module_core
         return fused_ragged_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners,
@@ -790,13 +875,15 @@ class _HipFusedHFModuleCoreFunction(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, level_cells=0):
+    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, level_cells=0, value_mask=None):
         ctx.level_cells = int(level_cells)
-        out = msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, levelref=True)
+        ctx.value_mask = value_mask  # (uint8 [B, I] or None: the value-mask twins of both kernel families; no gradient)
+        out = msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, levelref=True,
+                                 value_mask=value_mask)
         ctx.fused = out is not None  # the backward has the same limits: do not ask twice
         if out is None:
             pts, att = hf_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points)
-            out = msda_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners).to(proj.dtype)
+            out = msda_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners, value_mask=value_mask).to(proj.dtype)
         ctx.save_for_backward(img, img_shapes, proj, reference_points)
         ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
         return out
@@ -810,10 +897,10 @@ class _HipFusedHFModuleCoreFunction(Function):
         if ctx.fused and (need_proj or need_ref):
             res = msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, ctx.padding_mode,
                                      ctx.align_corners, need_img, level_cells=ctx.level_cells, need_ref=need_ref,
-                                     levelref=True)
+                                     levelref=True, value_mask=ctx.value_mask)
             if res is not None:
                 g_img, g_proj, g_ref = res
-                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None
+                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None
         with torch.enable_grad():
             proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
             ref_ = reference_points.detach().requires_grad_(need_ref)
@@ -822,7 +909,7 @@ class _HipFusedHFModuleCoreFunction(Function):
         need_sample = need_proj or need_ref
         g_img, g_pts, g_att = msda_hip_bwd(out_grad, img, img_shapes, pts.detach(), att.detach(), ctx.padding_mode,
                                            ctx.align_corners, (need_img, need_sample, need_sample),
-                                           level_cells=ctx.level_cells)
+                                           level_cells=ctx.level_cells, value_mask=ctx.value_mask)
         g_proj = g_ref = None
         if need_sample:
             wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
@@ -831,16 +918,28 @@ class _HipFusedHFModuleCoreFunction(Function):
                 g_proj = grads.pop(0).to(proj.dtype)
             if need_ref:
                 g_ref = grads.pop(0)
-        return g_img, None, g_proj, g_ref, None, None, None
+        return g_img, None, g_proj, g_ref, None, None, None, None
 
 
-def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None) -> torch.Tensor:
+def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None,
+                         value_mask=None, mask_in_kernels: bool = True) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *hf_module_sampling_inputs(proj, ...))``: the core of a Hugging
     Face attention module between its projections — value pyramid ``[B, I, H, D]``, raw projection ``[B, Q, H, L, P, 3]``,
     per-level reference points ``[B, Q, L, 2 | 4]``.  On GPU tensors the prologue and its chain rule run inside the
     gather kernels (``msda_*_fused_levelref_<dtype>``); on host tensors, while traced by ``torch.compile`` (over the
     registered custom ops) and where the library declines it is exactly that composition.  ``level_shapes``: the level
-    sizes as host numbers, optional (:func:`level_cells_of`)."""
+    sizes as host numbers, optional (:func:`level_cells_of`).  ``value_mask``: ``[B, I]`` bool / uint8, non-zero = the pixel
+    is real (transformers' ``attention_mask``; :func:`check_value_mask`) — the result is that of ``where(mask, img, 0)``
+    whatever the padding pixels hold.  On GPU tensors the mask goes into the kernels
+    (``msda_*_fused_levelref_masked_<dtype>``: no pass over the pyramid in either direction); ``mask_in_kernels=False``,
+    host tensors, traced calls and a library without those symbols compose ``masked_fill`` with the unmasked route."""
+    mask = None
+    if value_mask is not None:
+        _validate_value_mask(value_mask, img)
+        if mask_in_kernels and img.device.type == "cuda" and not torch.compiler.is_compiling() and _lib.has_value_mask():
+            mask = check_value_mask(value_mask, img)
+        else:
+            img = apply_value_mask(img, value_mask)
     level_cells = level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1])
     cuda = img.device.type == "cuda"
     if cuda and img_shapes.device != img.device:
@@ -853,7 +952,8 @@ def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, 
         if floating and (autocast or same or fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype)):
             pad = _padding_code(padding_mode)
             ext = _ext.load()
-            if same and not autocast and KernelTimer.active is None and ext is not None and \
+            # (a masked call takes the Python Function: the C++ node has no mask argument)
+            if mask is None and same and not autocast and KernelTimer.active is None and ext is not None and \
                     hasattr(ext, "msda_fused_levelref") and _lib.has_fused_levelref():
                 # C++ autograd node; only when the fused kernels take this L*P (it never composes)
                 B, I, H, D = img.shape
@@ -870,8 +970,9 @@ def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, 
                     return ext.msda_fused_levelref(img, img_shapes, proj, reference_points, pad, bool(align_corners),
                                                    level_cells)
             return _HipFusedHFModuleCoreFunction.apply(img, img_shapes, proj, reference_points, padding_mode,
-                                                       bool(align_corners), level_cells)
-    return _hf_composition(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes)
+                                                       bool(align_corners), level_cells, mask)
+    return _hf_composition(apply_value_mask(img, mask), img_shapes, proj, reference_points, padding_mode, align_corners,
+                           level_shapes)
 
 
 # ------------------------------------------------------------------------------------------
@@ -911,14 +1012,16 @@ def hf_box_sampling_inputs(proj: torch.Tensor, reference_points: torch.Tensor, p
 
 
 def fused_hf_box_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale: float = 0.5,
-                      padding_mode: str = "zeros", align_corners: bool = False, level_shapes=None) -> torch.Tensor:
+                      padding_mode: str = "zeros", align_corners: bool = False, level_shapes=None,
+                      value_mask=None) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *hf_box_sampling_inputs(proj, ...), points_per_level=...)``: the
     core of a D-FINE / DEIMv2 / RT-DETRv2 attention module between its projections — value pyramid ``[B, I, H, D]``, raw
     projection ``[B, Q, H, S, 3]`` (level-major), boxes ``[B, Q, 4]`` or ``[B, Q, 1, 4]``.  On GPU tensors the prologue and
     its chain rule run inside the gather kernels (``msda_*_fused_hfbox_<dtype>``, equal counts included); on host tensors,
-    while traced and where the library declines it is exactly that composition (:mod:`msda_triton_amd.ragged`)."""
+    while traced and where the library declines it is exactly that composition (:mod:`msda_triton_amd.ragged`).
+    ``value_mask``: ``[B, I]``, non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels."""
     from .ragged import fused_hf_box_module_core
-    return fused_hf_box_module_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale, padding_mode,
+    return fused_hf_box_module_core(apply_value_mask(img, value_mask), img_shapes, proj, reference_points, points_per_level, offset_scale, padding_mode,
                                     align_corners, level_shapes)
 
 
@@ -1013,6 +1116,7 @@ def multiscale_deformable_attention(
     level_shapes=None,
     points_per_level=None,
     sampling_mode: Literal["bilinear", "discrete"] = "bilinear",
+    value_mask: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Differentiable multiscale deformable attention.
 
@@ -1038,6 +1142,13 @@ def multiscale_deformable_attention(
             interpolated (transformers' ``method="discrete"``; see :mod:`msda_triton_amd.discrete`).  Accepted only with
             ``padding_mode="border"``, ``align_corners=False`` (neither has a meaning there), with or without
             ``points_per_level``; ``sampling_points`` gets no gradient (``None``).
+        value_mask: optional, not in the reference — ``[batch, num_image]`` bool or uint8 on ``img``'s device, non-zero =
+            the pixel is real (transformers' ``attention_mask`` polarity; mmcv's ``key_padding_mask`` is the inverse).  A
+            padding pixel counts as zeros whatever it holds (NaN included): the results are those of the call on
+            ``where(mask, img, 0)``, and ``img``'s gradient is zero there.  The mask takes no gradient.  GPU tensors with
+            a uniform point count run the value-mask kernels (no extra pass over the pyramid in either direction);
+            host tensors, ``points_per_level``, ``sampling_mode="discrete"`` and traced calls compose ``masked_fill``
+            with their route.
 
     Returns:
         ``[batch, num_queries, num_heads, num_channels]``.
@@ -1045,6 +1156,12 @@ def multiscale_deformable_attention(
     Tensors on an AMD GPU ("cuda" device type on ROCm) run the hand-written gfx950 kernels and
     never fall back; host tensors run the plain-PyTorch formulation.
     """
+    if value_mask is not None:
+        _validate_value_mask(value_mask, img)
+        if sampling_mode == "bilinear" and points_per_level is None and img.device.type == "cuda":
+            return hip_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,
+                                                       align_corners, level_shapes, value_mask=value_mask)
+        img = apply_value_mask(img, value_mask)
     if sampling_mode != "bilinear":
         if sampling_mode != "discrete":
             raise ValueError(f'`sampling_mode` should be "bilinear" or "discrete", but got {sampling_mode!r}.')

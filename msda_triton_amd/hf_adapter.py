@@ -124,6 +124,21 @@ def _core(value, spatial_shapes_list, sampling_locations, attention_weights, num
     return out.flatten(2)
 
 
+# Measured (profiles/r12_hf_mask_bench.json): with the mask in the kernels the core's forward plus backward is
+# ahead of masked_fill + the unmasked kernels by the project's rule — slowest repeat below the other leg's fastest — at
+# the Deformable-DETR encoder shape in fp32 and at the Grounding-DINO decoder shape in fp32 and with bf16 storage.  fp16
+# and fp64 pyramids were not measured and keep masked_fill.  False: every call keeps masked_fill (A/B runs).
+MASK_IN_KERNELS = True
+
+
+def mask_in_kernels(value: torch.Tensor, num_queries: int) -> bool:
+    """Does the fused adapter hand a padding mask to the value-mask kernels (``fused_hf_module_core(value_mask=...)``) for
+    this call, or keep transformers' ``masked_fill`` in front of the unmasked kernels?  The project's rule (DESIGN.md 15,
+    17): the kernels take the mask only where their slowest measured repeat was below ``masked_fill``'s fastest, forward
+    plus backward."""
+    return bool(MASK_IN_KERNELS) and value.device.type == "cuda" and value.dtype in (torch.float32, torch.bfloat16)
+
+
 class FusedHFDeformableAttention:
     """Mixed into the class of a Hugging Face attention module (``DeformableDetrMultiscaleDeformableAttention``,
     ``GroundingDinoMultiscaleDeformableAttention``, the RT-DETR family's ...) by ``replace_hf_msda(model, fused=True)``:
@@ -159,10 +174,13 @@ class FusedHFDeformableAttention:
             hidden_states = hidden_states + position_embeddings
         batch_size, num_queries, _ = hidden_states.shape
         sequence_length = encoder_hidden_states.shape[1]
+        # the padding mask travels to the core with the value pyramid (no masked_fill here): fused_hf_module_core applies it
+        # inside the kernels where mask_in_kernels() says they are ahead, else as the masked_fill transformers runs
         value = self.value_proj(encoder_hidden_states)
-        if attention_mask is not None:
-            value = value.masked_fill(~attention_mask[..., None], float(0))
         value = value.view(batch_size, sequence_length, self.n_heads, value.shape[-1] // self.n_heads)
+        mask_kw = {}
+        if attention_mask is not None:
+            mask_kw = dict(value_mask=attention_mask, mask_in_kernels=mask_in_kernels(value, num_queries))
         # ONE GEMM for offsets and logits, laid out [B, Q, H, L, P, 3]; the weight is gathered from the two HF parameters
         # (autograd routes its gradient back to them)
         rows = self._proj_rows(hidden_states.device)
@@ -182,13 +200,15 @@ class FusedHFDeformableAttention:
             # what autocast hands the core: 16-bit value and projection next to fp32 reference points — the module-storage
             # kernels (fp32 arithmetic, 16-bit result), called outside autocast so that nothing is cast to fp32
             with torch.autocast("cuda", enabled=False):
-                out = fused_hf_module_core(value, shapes, proj, reference_points, "zeros", False, level_shapes=level_shapes)
+                out = fused_hf_module_core(value, shapes, proj, reference_points, "zeros", False, level_shapes=level_shapes,
+                                           **mask_kw)
         else:
             if proj.dtype != value.dtype:
                 proj = proj.to(value.dtype)
             if reference_points.dtype != value.dtype:
                 reference_points = reference_points.to(value.dtype)
-            out = fused_hf_module_core(value, shapes, proj, reference_points, "zeros", False, level_shapes=level_shapes)
+            out = fused_hf_module_core(value, shapes, proj, reference_points, "zeros", False, level_shapes=level_shapes,
+                                       **mask_kw)
         return self.output_proj(out.flatten(2)), None
 
 

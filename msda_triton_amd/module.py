@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from ._linear import projection
-from .functional import fused_module_core, module_sampling_inputs
+from .functional import apply_value_mask, fused_module_core, module_sampling_inputs
 from .ragged import ragged_module_sampling_inputs
 
 
@@ -91,7 +91,7 @@ class MultiscaleDeformableAttention(nn.Module):
         return module_sampling_inputs(proj, img_shapes, reference_points)
 
     def forward(self, img: torch.Tensor, img_shapes: torch.Tensor, queries: torch.Tensor,
-                reference_points: torch.Tensor, level_shapes=None) -> torch.Tensor:
+                reference_points: torch.Tensor, level_shapes=None, value_mask=None) -> torch.Tensor:
         """
         Args:
             img: flattened pyramid ``[batch, num_image, emb_dim]``.
@@ -101,6 +101,9 @@ class MultiscaleDeformableAttention(nn.Module):
                 (cx, cy, w, h), normalised to [0, 1].
             level_shapes: optional (not in the reference): the same (height, width) pairs as host numbers; see
                 ``msda_triton_amd.functional.level_cells_of``.
+            value_mask: optional (not in the reference): ``[batch, num_image]`` bool or uint8, non-zero = the pixel is
+                real (transformers' ``attention_mask`` polarity).  Applied to the projected pyramid as ``masked_fill``
+                (this module's fused kernels have no masked form); see ``multiscale_deformable_attention``.
 
         Returns:
             ``[batch, num_queries, emb_dim]``.
@@ -122,6 +125,7 @@ class MultiscaleDeformableAttention(nn.Module):
         #  no gain at 2 500, and a LOSS at 900 — a host-bound step that the two extra small launches lengthen — so only
         #  from 32 768 (b, q) rows on)
         value = projection(self.img_input_proj, img, pad_rows=B * N >= 32768).reshape(B, I, H, self.hidden_dim // H)
+        value = apply_value_mask(value, value_mask)
         if value.device.type == "cuda" and proj.dtype in (torch.bfloat16, torch.float16) and \
                 self.value_dtype in (None, proj.dtype) and value.dtype == proj.dtype:
             # 16-bit projections (autocast's GEMMs, or 16-bit parameters) with fp32 reference points: the kernels read
