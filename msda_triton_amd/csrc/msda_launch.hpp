@@ -1409,17 +1409,18 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         set_error("ref_dim must be 2 or 4, got %d", ref_dim);
         return MSDA_ERR_BAD_ARG;
     }
-    if (grad_proj == nullptr || grad_ref_part == nullptr) {
+    const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
+    const size_t ns = (size_t)(B * Q * H * samples(d));
+    const size_t nref = (size_t)(B * Q * H) * (kLevelRef<PP> ? (size_t)L : 1) * ref_dim;
+    // (a buffer of no elements may be null: PyTorch's empty tensors are — a call with Q = 0 has nothing to produce there)
+    if ((ns && grad_proj == nullptr) || (nref && grad_ref_part == nullptr)) {
         set_error("the fused backward always produces grad_proj and the grad_reference_points partials");
         return MSDA_ERR_BAD_ARG;
     }
-    const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
-    const size_t ns = (size_t)(B * Q * H * samples(d));
     if (B * Q * H * D == 0 || samples(d) == 0 || I == 0) {  // no sample touches anything: all gradients are zero
         hipError_t e = hipSuccess;
         if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
         if (e == hipSuccess && ns) e = hipMemsetAsync(grad_proj, 0, ns * 3 * sizeof(TS), stream);
-        const size_t nref = (size_t)(B * Q * H) * (kLevelRef<PP> ? (size_t)L : 1) * ref_dim;
         if (e == hipSuccess && nref) e = hipMemsetAsync(grad_ref_part, 0, nref * sizeof(T), stream);
         return (int)e;
     }
