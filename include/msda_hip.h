@@ -560,7 +560,12 @@ MSDA_API int msda_get_option(const char *key);
  * wave per unit, 3 = the discrete-sampling forward (msda_fwd_discrete_<dtype>);  "fwd_lds_level_bytes" LDS bytes per plane set aside for level rows (the kernel keeps the longest suffix
  * of the level list that fits);  "fwd_lds_planes";  "fwd_workgroups";  "sample_variant", "sample_lds_level_bytes" the same
  * for the sample-gradient kernel (2 = the discrete attention-weight gradient);  "value_path" 1 = single-launch kernel, 2 = sorted pipeline;  "value_passes" its passes
- * over the batch.  Unknown key: MSDA_ERR_BAD_ARG. */
+ * over the batch.
+ * "grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches" are COUNTERS, not last values: launches so far in this
+ * process whose (plane, slot) grid took the XCD-aware 3-D form dim3(8, slots, ceil(planes / 8)), the linear 2-D form
+ * dim3(slots, planes), or the flat 1-D form that decodes its block index with a division (more than 65535 slots, plane
+ * groups or — in linear order — planes).  They only rise (reported modulo 2^31); take the difference around a call.
+ * Unknown key: MSDA_ERR_BAD_ARG. */
 MSDA_API int msda_last_launch_info(const char *key);
 
 #ifdef __cplusplus

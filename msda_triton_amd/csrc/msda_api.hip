@@ -191,6 +191,13 @@ void note_launch(int slot, int value)
 {
     if (slot >= 0 && slot < 8) g_info[slot].store(value, std::memory_order_relaxed);
 }
+// ... and launches per grid form (plane_grid): counters, not last values — a route makes several plane_grid launches, and a
+// test wants to know that NONE of them took another form (reported modulo 2^31)
+static std::atomic<unsigned> g_grid[3];
+void note_grid(int form)
+{
+    if (form >= 0 && form < 3) g_grid[form].fetch_add(1u, std::memory_order_relaxed);
+}
 
 void set_error(const char *fmt, ...)
 {
@@ -253,6 +260,9 @@ extern "C" int msda_last_launch_info(const char *key)
                                          "sample_variant", "sample_lds_level_bytes", "value_path", "value_passes"};
     for (int i = 0; key != nullptr && i < 8; ++i)
         if (strcmp(key, kKeys[i]) == 0) return msda::g_info[i].load(std::memory_order_relaxed);
+    static const char *const kGridKeys[3] = {"grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches"};
+    for (int i = 0; key != nullptr && i < 3; ++i)
+        if (strcmp(key, kGridKeys[i]) == 0) return (int)(msda::g_grid[i].load(std::memory_order_relaxed) & 0x7fffffffu);
     msda::set_error("unknown launch-info key '%s'", key ? key : "(null)");
     return MSDA_ERR_BAD_ARG;
 }

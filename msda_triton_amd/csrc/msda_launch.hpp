@@ -33,6 +33,9 @@ void set_error(const char *fmt, ...);
 // bytes, planes per workgroup, workgroups}, 4-5 sample gradients {variant, LDS level bytes}, 6 grad_value path (1 single launch,
 // 2 sorted pipeline), 7 its passes over the batch
 void note_launch(int slot, int value);
+// ... and which grid form plane_grid gave a launch: 0 XCD-aware 3-D, 1 linear 2-D, 2 flat 1-D — one process-wide counter per
+// form that only ever rises ("grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches"; callers take differences)
+void note_grid(int form);
 // measurement only (option "profile"): an event pair around a kernel launch, read back by msda_profile_read
 void *profile_begin(const char *name, hipStream_t stream);
 void profile_end(void *token, hipStream_t stream);
@@ -140,17 +143,20 @@ inline bool plane_grid(Params &p, int npairs, int64_t slots, dim3 &grid)
     if (p.xcd_map && slots <= 65535 && groups <= 65535) {
         p.grid3d = 1;
         grid = dim3(8, (unsigned)slots, (unsigned)groups);
+        note_grid(0);
         return true;
     }
     if (!p.xcd_map && npairs <= 65535 && slots < ((int64_t)1 << 31)) {
         p.grid3d = 1;
         grid = dim3((unsigned)slots, (unsigned)npairs);
+        note_grid(1);
         return true;
     }
     p.grid3d = 0;
     const int64_t blocks = (p.xcd_map ? groups * 8 : (int64_t)npairs) * slots;
     if (blocks >= ((int64_t)1 << 31)) return false;
     grid = dim3((unsigned)blocks);
+    note_grid(2);
     return true;
 }
 
