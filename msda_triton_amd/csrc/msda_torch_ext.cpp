@@ -3,9 +3,15 @@
 // The product boundary is the C ABI; Python reaches it through ctypes (msda_triton_amd/_lib.py).  For
 // Grounding-DINO-sized calls (B*Q ~ 10^3) the kernels take ~60 us while Python's autograd glue, ctypes
 // marshalling and the engine's hop into a Python backward take ~100 us per forward+backward.  This extension is
-// the same glue in C++: one torch::autograd::Function whose forward and backward call msda_fwd_<dtype> /
-// msda_bwd_<dtype> directly.  It contains no kernels and no numerics; the argument validation stays in Python
-// (msda_triton_amd/functional.py) and the same tests cover both routes.
+// the same glue in C++.  It contains no kernels and no numerics; the argument validation stays in Python
+// (msda_triton_amd/functional.py, ragged.py, discrete.py) and the same tests cover both routes.
+//
+// Layout: every family of entry points (msda_fwd<family>_<dtype> / msda_bwd<family>_<dtype>) is one MSDA_FAMILY table
+// line — the dtype rule is written once, in suffix_of — and one thin torch::autograd::Function class, which names its
+// table, its workspace query and the arguments its entry points take between the problem's dimensions and
+// value_row_stride.  The bodies are shared: node_forward for all seven, sampling_backward for the nodes over sampling
+// points and weights (MSDAFunction, MSDARaggedFunction, MSDADiscreteFunction), fused_backward for the module cores with
+// the prologue fused in (MSDAFused*Function).  Behind them, the row-range launches of the row-sharded operator.
 // Reference counterpart: _TritonMultiscaleDeformableAttentionFunction, src/msda_triton/frontend.py:108-142.
 #include <torch/extension.h>
 #include <torch/csrc/autograd/functions/basic_ops.h>
@@ -21,46 +27,56 @@
 
 namespace {
 
-// (ABI 11: value_row_stride in front of the stream / the workspace)
-using FwdFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
-                      int64_t, int64_t, int64_t, int64_t, int, int, int64_t, void *);
-// (the level-size bound travels as an argument: include/msda_hip.h, max_level_cells)
-using BwdFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *, void *,
-                      int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int64_t, int64_t, void *,
-                      int64_t, void *);
+// The entry points' dtype suffixes, in the order MSDA_FAMILY lists them.  `t`: dtype of the value pyramid (and its
+// gradient); `c`: dtype of every other tensor — the same, or float next to a 16-bit pyramid (the mixed-storage entry points)
+enum Suffix { f32, f16, bf16, f64, f32_vbf16, f32_vf16, kSuffixes };
 
-using FwdFusedFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
-                           int64_t, int64_t, int64_t, int64_t, int, int, int, int64_t, void *);
-using BwdFusedFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *, void *,
-                           int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int, int64_t, int64_t,
-                           void *, int64_t, void *);
-
-struct Fns {
-    FwdFn fwd;
-    BwdFn bwd;
-    FwdFusedFn fwd_fused;
-    BwdFusedFn bwd_fused;
-};
-
-// `t`: dtype of the value pyramid (and its gradient); `c`: dtype of every other tensor — the same, or float next to a
-// 16-bit pyramid (the mixed-storage entry points)
-Fns fns_for(at::ScalarType t, at::ScalarType c)
+Suffix suffix_of(at::ScalarType t, at::ScalarType c)
 {
     if (t != c) {
         TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
                           "unsupported dtype combination: value ", t, " with ", c);
-        if (t == at::kBFloat16)
-            return {msda_fwd_f32_vbf16, msda_bwd_f32_vbf16, msda_fwd_fused_f32_vbf16, msda_bwd_fused_f32_vbf16};
-        return {msda_fwd_f32_vf16, msda_bwd_f32_vf16, msda_fwd_fused_f32_vf16, msda_bwd_fused_f32_vf16};
+        return t == at::kBFloat16 ? f32_vbf16 : f32_vf16;
     }
     switch (t) {
-    case at::kFloat: return {msda_fwd_f32, msda_bwd_f32, msda_fwd_fused_f32, msda_bwd_fused_f32};
-    case at::kHalf: return {msda_fwd_f16, msda_bwd_f16, msda_fwd_fused_f16, msda_bwd_fused_f16};
-    case at::kBFloat16: return {msda_fwd_bf16, msda_bwd_bf16, msda_fwd_fused_bf16, msda_bwd_fused_bf16};
-    case at::kDouble: return {msda_fwd_f64, msda_bwd_f64, msda_fwd_fused_f64, msda_bwd_fused_f64};
+    case at::kFloat: return f32;
+    case at::kHalf: return f16;
+    case at::kBFloat16: return bf16;
+    case at::kDouble: return f64;
     default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
     }
 }
+
+// A family's forward / backward pair for every suffix, and the names check_rc reports them under
+template <typename Fwd, typename Bwd> struct Family {
+    struct Pair {
+        Fwd fwd;
+        Bwd bwd;
+    };
+    const char *fwd_name, *bwd_name;
+    Pair pairs[kSuffixes];
+    const Pair &of(at::ScalarType t, at::ScalarType c) const { return pairs[suffix_of(t, c)]; }
+};
+
+#define MSDA_PAIR(F, S) {msda_fwd##F##_##S, msda_bwd##F##_##S}
+#define MSDA_FAMILY(NAME, F)                                                                                           \
+    constexpr Family<decltype(&msda_fwd##F##_f32), decltype(&msda_bwd##F##_f32)> NAME = {                                \
+        "msda_fwd" #F, "msda_bwd" #F,                                                                                    \
+        {MSDA_PAIR(F, f32), MSDA_PAIR(F, f16), MSDA_PAIR(F, bf16), MSDA_PAIR(F, f64), MSDA_PAIR(F, f32_vbf16),           \
+         MSDA_PAIR(F, f32_vf16)}};
+MSDA_FAMILY(kPlain, )
+MSDA_FAMILY(kRagged, _ragged)
+MSDA_FAMILY(kDiscrete, _discrete)
+MSDA_FAMILY(kFused, _fused)
+MSDA_FAMILY(kFusedRagged, _fused_ragged)
+MSDA_FAMILY(kFusedHfBox, _fused_hfbox)
+MSDA_FAMILY(kFusedLevelRef, _fused_levelref)
+#undef MSDA_FAMILY
+#undef MSDA_PAIR
+
+// (the row-range launches below)
+using Fns = decltype(kPlain)::Pair;
+Fns fns_for(at::ScalarType t, at::ScalarType c) { return kPlain.of(t, c); }
 
 void check_rc(int rc, const char *what)
 {
@@ -110,616 +126,347 @@ int64_t value_batch_bytes(const at::Tensor &img, int64_t vrow)
     return vrow > 0 ? img.size(1) * vrow : img.size(1) * img.size(2) * img.size(3) * (int64_t)img.element_size();
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The seven autograd nodes.  Each takes (img, shapes, a, b, ...): `a`, `b` are the sampling points and attention
+// weights, or — the fused module cores — the raw projection and the reference points.
+// ------------------------------------------------------------------------------------------------------------------
+using torch::autograd::AutogradContext;
+using torch::autograd::variable_list;
+
+// What a node's `apply` takes behind the four tensors; a family leaves what its entry points do not take at the default.
+// `counts`: the L per-level point counts, `level_scale`: the L fp32 scales of Hugging Face's box rule — host numbers, which
+// the Python caller checked.
+struct Extra {
+    int64_t padding_mode = 0;
+    bool align_corners = false;
+    int64_t level_cells = 0;  // bound on the largest level's cells (0: unknown)
+    std::vector<int64_t> counts;
+    std::vector<double> level_scale;
+    double offset_scale = 0;
+};
+
+// One call as the launches see it, forward and backward alike: the tensors the kernels read and the pieces of the entry
+// points' argument lists.
+struct Call {
+    at::Tensor img, shapes, a, b;
+    int64_t vrow;                 // value_row_stride of `img` (value_rows)
+    int64_t B, I, H, D, Q, L, P;  // (P: without per-level counts only)
+    int pad, ac;
+    int64_t level_cells;
+    std::vector<int32_t> ppl;
+    std::vector<float> scale;  // (fp32 values: the conversion is exact)
+    double offset_scale;
+
+    Call(at::Tensor img_, int64_t vrow_, at::Tensor shapes_, at::Tensor a_, at::Tensor b_, const Extra &x)
+        : img(std::move(img_)), shapes(std::move(shapes_)), a(std::move(a_)), b(std::move(b_)), vrow(vrow_), B(img.size(0)),
+          I(img.size(1)), H(img.size(2)), D(img.size(3)), Q(a.size(1)),
+          L(x.counts.empty() ? a.size(3) : (int64_t)x.counts.size()), P(x.counts.empty() ? a.size(4) : 0),
+          pad((int)x.padding_mode), ac(x.align_corners ? 1 : 0), level_cells(x.level_cells),
+          ppl(x.counts.begin(), x.counts.end()), scale(x.level_scale.begin(), x.level_scale.end()),
+          offset_scale(x.offset_scale)
+    {
+    }
+    auto inputs() const { return std::make_tuple(img.data_ptr(), shapes.data_ptr<int64_t>(), a.data_ptr(), b.data_ptr()); }
+    auto dims() const { return std::make_tuple(B, I, H, D, Q); }
+    // the samples of a query: L x P, or the per-level counts
+    auto uniform() const { return std::make_tuple(L, P); }
+    auto per_level() const { return std::make_tuple(L, ppl.data()); }
+    // what follows them, in front of value_row_stride (forward) / max_level_cells (backward)
+    auto mode() const { return std::make_tuple(pad, ac); }
+    auto fused_mode() const { return std::make_tuple((int)b.size(-1), pad, ac); }  // (ref_dim first)
+    auto hfbox_mode() const { return std::tuple_cat(std::make_tuple(scale.data(), offset_scale), fused_mode()); }
+};
+
+void save(AutogradContext *ctx, const Call &c, const Extra &x)
+{
+    ctx->save_for_backward({c.img, c.shapes, c.a, c.b});
+    ctx->saved_data["padding_mode"] = x.padding_mode;
+    ctx->saved_data["align_corners"] = x.align_corners;
+    ctx->saved_data["level_cells"] = x.level_cells;
+    ctx->saved_data["vrow"] = c.vrow;
+    if (!x.counts.empty()) ctx->saved_data["counts"] = x.counts;
+    if (!x.level_scale.empty()) {
+        ctx->saved_data["level_scale"] = x.level_scale;
+        ctx->saved_data["offset_scale"] = x.offset_scale;
+    }
+}
+
+Call saved_call(AutogradContext *ctx)
+{
+    const auto saved = ctx->get_saved_variables();
+    auto &data = ctx->saved_data;
+    Extra x{data["padding_mode"].toInt(), data["align_corners"].toBool(), data["level_cells"].toInt()};
+    if (data.count("counts")) x.counts = data["counts"].toIntVector();
+    if (data.count("level_scale")) {
+        x.level_scale = data["level_scale"].toDoubleVector();
+        x.offset_scale = data["offset_scale"].toDouble();
+    }
+    return Call(saved[0], data["vrow"].toInt(), saved[1], saved[2], saved[3], x);
+}
+
+// The forward of every node.  value_rows(img_) is taken once: its tensor and stride are what the backward launches with.
+template <typename Node>
+at::Tensor node_forward(AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
+                        const at::Tensor &a_, const at::Tensor &b_, const Extra &x)
+{
+    const auto [img, vrow] = value_rows(img_);
+    const Call c(img, vrow, shapes_.to(at::kLong).contiguous() /* stays on the device */, a_.contiguous(), b_.contiguous(), x);
+    at::Tensor out = at::empty({c.B, c.Q, c.H, c.D}, c.a.options());
+    const c10::DeviceGuard guard(img.device());
+    check_rc(std::apply(Node::family.of(img.scalar_type(), c.a.scalar_type()).fwd,
+                        std::tuple_cat(c.inputs(), std::make_tuple(out.data_ptr()), c.dims(), Node::samples(c), Node::mode(c),
+                                       std::make_tuple(vrow, current_stream(img)))),
+             Node::family.fwd_name);
+    save(ctx, c, x);
+    return out;
+}
+
+at::Tensor grad_out_as(const at::Tensor &grad, at::ScalarType dtype)
+{
+    at::Tensor gout = grad.contiguous();
+    return gout.scalar_type() == dtype ? gout : gout.to(dtype);
+}
+
+bool aligned16(const at::Tensor &t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+void *ptr_or_null(const at::Tensor &t) { return t.defined() ? t.data_ptr() : nullptr; }
+
+// grad_value (dense, whatever the pyramid's row stride) and the workspace its passes need (scratch: no initialisation
+// needed).  `lend_grads`: the call asks for the sample gradients too and their buffers may hold the sorted records — the
+// library's own conditions: 16-byte aligned buffers, no forced side-stream fork.
+struct ValueGrad {
+    at::Tensor g_img, ws;
+    int64_t ws_bytes = 0;
+};
+template <typename Node> ValueGrad value_grad(const Call &c, bool lend_grads)
+{
+    ValueGrad v;
+    v.g_img = at::empty(c.img.sizes(), c.img.options());
+    const int flags = lend_grads && aligned16(v.g_img) && msda_get_option("overlap") != 1 ? MSDA_WS_RECORDS_IN_GRADS : 0;
+    v.ws_bytes = std::apply(Node::workspace_bytes,
+                            std::tuple_cat(c.dims(), Node::samples(c),
+                                           std::make_tuple((int)c.a.element_size(), (int)c.img.element_size(), c.level_cells, flags)));
+    v.ws = at::empty({v.ws_bytes}, c.img.options().dtype(at::kByte));
+    return v;
+}
+
+// `grads`: the gradient buffers in the entry point's order, grad_value first (null: not wanted)
+template <typename Node, typename Grads>
+void launch_backward(const Call &c, const at::Tensor &gout, const ValueGrad &v, const Grads &grads)
+{
+    const c10::DeviceGuard guard(c.img.device());
+    check_rc(std::apply(Node::family.of(c.img.scalar_type(), c.a.scalar_type()).bwd,
+                        std::tuple_cat(std::make_tuple(gout.data_ptr()), c.inputs(), grads, c.dims(), Node::samples(c), Node::mode(c),
+                                       std::make_tuple(c.level_cells, c.vrow, ptr_or_null(v.ws), v.ws_bytes, current_stream(c.img)))),
+             Node::family.bwd_name);
+}
+
+// one entry per argument of the node's `apply`: the three gradients in their places, the rest undefined
+template <typename Node>
+variable_list node_grads(AutogradContext *ctx, const variable_list &grads,
+                                          at::Tensor g_img, at::Tensor g_a, at::Tensor g_b)
+{
+    variable_list outs(Node::arguments);
+    outs[0] = std::move(g_img);
+    if (ctx->needs_input_grad(2)) outs[2] = std::move(g_a);
+    if (ctx->needs_input_grad(3)) outs[3] = std::move(g_b);
+    return once_differentiable(grads, std::move(outs));
+}
+
+// Sampling points and weights in, gradients for both out: allocated together when either is needed (discrete sampling has
+// none for the points), all three gradients in one call, no launch when nothing is wanted.
+template <typename Node>
+variable_list sampling_backward(AutogradContext *ctx, variable_list grads)
+{
+    const Call c = saved_call(ctx);
+    const at::Tensor gout = grad_out_as(grads[0], c.a.scalar_type());
+    const bool want_value = ctx->needs_input_grad(0);
+    const bool want_sample = (Node::points_grad && ctx->needs_input_grad(2)) || ctx->needs_input_grad(3);
+    at::Tensor g_pts, g_att;
+    ValueGrad v;
+    if (want_sample) {
+        if (Node::points_grad) g_pts = at::empty_like(c.a);
+        g_att = at::empty_like(c.b);
+    }
+    if (want_value) v = value_grad<Node>(c, Node::records_in_grads && want_sample && aligned16(g_pts) && aligned16(g_att));
+    if (want_value || want_sample) {
+        if constexpr (Node::points_grad)
+            launch_backward<Node>(c, gout, v, std::make_tuple(ptr_or_null(v.g_img), ptr_or_null(g_pts), ptr_or_null(g_att)));
+        else
+            launch_backward<Node>(c, gout, v, std::make_tuple(ptr_or_null(v.g_img), ptr_or_null(g_att)));
+    }
+    return node_grads<Node>(ctx, grads, v.g_img, g_pts, g_att);
+}
+
+// Projection and reference points in, grad_proj and the kernel's per-head partials of grad_ref out — [B, Q, H, ref_dim], or
+// [B, Q, H, L, ref_dim] for per-level reference points — always allocated, always launched; the partials are summed over
+// the heads only when the reference points need a gradient.
+template <typename Node>
+variable_list fused_backward(AutogradContext *ctx, variable_list grads)
+{
+    const Call c = saved_call(ctx);
+    const at::Tensor gout = grad_out_as(grads[0], c.a.scalar_type());
+    const int64_t ref_dim = c.b.size(-1);
+    at::Tensor g_proj = at::empty_like(c.a);
+    at::Tensor g_ref_part = Node::per_level_ref ? at::empty({c.B, c.Q, c.H, c.L, ref_dim}, c.a.options())
+                                                : at::empty({c.B, c.Q, c.H, ref_dim}, c.a.options());
+    ValueGrad v;
+    if (ctx->needs_input_grad(0)) v = value_grad<Node>(c, false);
+    launch_backward<Node>(c, gout, v, std::make_tuple(ptr_or_null(v.g_img), g_proj.data_ptr(), g_ref_part.data_ptr()));
+    return node_grads<Node>(ctx, grads, v.g_img, g_proj, ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor());
+}
+
+// msda_fwd_ / msda_bwd_<dtype>: sampling points [B, Q, H, L, P, 2], attention weights [B, Q, H, L, P]
 class MSDAFunction : public torch::autograd::Function<MSDAFunction> {
 public:
-    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
-                              const at::Tensor &pts_, const at::Tensor &att_, int64_t padding_mode, bool align_corners,
-                              int64_t level_cells)
+    static constexpr auto &family = kPlain;
+    static constexpr auto workspace_bytes = &msda_bwd_workspace_bytes;
+    static constexpr bool points_grad = true, records_in_grads = true;
+    static constexpr size_t arguments = 7;
+    static auto samples(const Call &c) { return c.uniform(); }
+    static auto mode(const Call &c) { return c.mode(); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &pts,
+                              const at::Tensor &att, int64_t padding_mode, bool align_corners, int64_t level_cells)
     {
-        const auto [img, vrow] = value_rows(img_);
-        const at::Tensor pts = pts_.contiguous(), att = att_.contiguous();
-        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();  // stays on the device
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
-        const int64_t Q = pts.size(1), L = pts.size(3), P = pts.size(4);
-        at::Tensor out = at::empty({B, Q, H, D}, pts.options());
-        const c10::DeviceGuard guard(img.device());
-        check_rc(fns_for(img.scalar_type(), pts.scalar_type())
-                     .fwd(img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(), out.data_ptr(), B, I,
-                          H, D, Q, L, P, (int)padding_mode, align_corners ? 1 : 0, vrow, current_stream(img)),
-                 "msda_fwd");
-        ctx->save_for_backward({img, shapes, pts, att});
-        ctx->saved_data["padding_mode"] = padding_mode;
-        ctx->saved_data["align_corners"] = align_corners;
-        ctx->saved_data["level_cells"] = level_cells;
-        ctx->saved_data["vrow"] = vrow;
-        return out;
+        return node_forward<MSDAFunction>(ctx, img, shapes, pts, att, {padding_mode, align_corners, level_cells});
     }
-
-    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
-                                                   torch::autograd::variable_list grads)
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        const auto saved = ctx->get_saved_variables();
-        const at::Tensor &img = saved[0], &shapes = saved[1], &pts = saved[2], &att = saved[3];
-        const int64_t vrow = ctx->saved_data["vrow"].toInt();
-        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
-        const bool align_corners = ctx->saved_data["align_corners"].toBool();
-        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();  // bound on the largest level's cells (0: unknown)
-        at::Tensor gout = grads[0].contiguous();
-        if (gout.scalar_type() != pts.scalar_type()) gout = gout.to(pts.scalar_type());
-        const bool want_value = ctx->needs_input_grad(0);
-        const bool want_sample = ctx->needs_input_grad(2) || ctx->needs_input_grad(3);
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
-        const int64_t Q = pts.size(1), L = pts.size(3), P = pts.size(4);
-        at::Tensor g_img, g_pts, g_att, ws;
-        int64_t ws_bytes = 0;
-        if (want_sample) {
-            g_pts = at::empty_like(pts);
-            g_att = at::empty_like(att);
-        }
-        if (want_value) {
-            g_img = at::empty(img.sizes(), img.options());  // (dense, whatever the pyramid's row stride)
-            // all three gradients in one call: the sorted records may use the gradient buffers themselves (the library's
-            // own conditions: 16-byte aligned buffers, no forced side-stream fork)
-            const bool in_grads = want_sample && reinterpret_cast<uintptr_t>(g_pts.data_ptr()) % 16 == 0 &&
-                                  reinterpret_cast<uintptr_t>(g_att.data_ptr()) % 16 == 0 &&
-                                  reinterpret_cast<uintptr_t>(g_img.data_ptr()) % 16 == 0 && msda_get_option("overlap") != 1;
-            ws_bytes = msda_bwd_workspace_bytes(B, I, H, D, Q, L, P, (int)pts.element_size(), (int)img.element_size(),
-                                                level_cells, in_grads ? MSDA_WS_RECORDS_IN_GRADS : 0);
-            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));  // scratch: no initialisation needed
-        }
-        if (want_value || want_sample) {
-            const c10::DeviceGuard guard(img.device());
-            check_rc(fns_for(img.scalar_type(), pts.scalar_type())
-                         .bwd(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(),
-                              want_value ? g_img.data_ptr() : nullptr, want_sample ? g_pts.data_ptr() : nullptr,
-                              want_sample ? g_att.data_ptr() : nullptr, B, I, H, D, Q, L, P, padding_mode,
-                              align_corners ? 1 : 0, level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr, ws_bytes,
-                              current_stream(img)),
-                     "msda_bwd");
-        }
-        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_pts : at::Tensor(),
-                                           ctx->needs_input_grad(3) ? g_att : at::Tensor(), at::Tensor(), at::Tensor(),
-                                           at::Tensor()});
+        return sampling_backward<MSDAFunction>(ctx, std::move(grads));
     }
 };
 
 // Per-level point counts (msda_fwd_ragged_ / msda_bwd_ragged_<dtype>, ABI 12): sampling points [B, Q, H, S, 2], attention
-// weights [B, Q, H, S], `counts` the L point counts (host numbers; the Python caller checked them and that they are not
-// all equal).  The same node as MSDAFunction otherwise: decoder-sized calls spend more host time than device time.
-using FwdRaggedFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
-                            int64_t, int64_t, int64_t, const int32_t *, int, int, int64_t, void *);
-using BwdRaggedFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *, void *,
-                            int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int, int, int64_t,
-                            int64_t, void *, int64_t, void *);
-std::pair<FwdRaggedFn, BwdRaggedFn> ragged_fns_for(at::ScalarType t, at::ScalarType c)
-{
-    if (t != c) {
-        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
-                          "unsupported dtype combination: value ", t, " with ", c);
-        if (t == at::kBFloat16) return {msda_fwd_ragged_f32_vbf16, msda_bwd_ragged_f32_vbf16};
-        return {msda_fwd_ragged_f32_vf16, msda_bwd_ragged_f32_vf16};
-    }
-    switch (t) {
-    case at::kFloat: return {msda_fwd_ragged_f32, msda_bwd_ragged_f32};
-    case at::kHalf: return {msda_fwd_ragged_f16, msda_bwd_ragged_f16};
-    case at::kBFloat16: return {msda_fwd_ragged_bf16, msda_bwd_ragged_bf16};
-    case at::kDouble: return {msda_fwd_ragged_f64, msda_bwd_ragged_f64};
-    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
-    }
-}
-
+// weights [B, Q, H, S]; the Python caller checked the counts and that they are not all equal.
 class MSDARaggedFunction : public torch::autograd::Function<MSDARaggedFunction> {
 public:
-    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
-                              const at::Tensor &pts_, const at::Tensor &att_, int64_t padding_mode, bool align_corners,
-                              int64_t level_cells, const std::vector<int64_t> &counts)
-    {
-        const auto [img, vrow] = value_rows(img_);
-        const at::Tensor pts = pts_.contiguous(), att = att_.contiguous();
-        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        at::Tensor out = at::empty({B, Q, H, D}, pts.options());
-        const c10::DeviceGuard guard(img.device());
-        check_rc(ragged_fns_for(img.scalar_type(), pts.scalar_type())
-                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(), out.data_ptr(), B,
-                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), (int)padding_mode, align_corners ? 1 : 0, vrow,
-                            current_stream(img)),
-                 "msda_fwd_ragged");
-        ctx->save_for_backward({img, shapes, pts, att});
-        ctx->saved_data["padding_mode"] = padding_mode;
-        ctx->saved_data["align_corners"] = align_corners;
-        ctx->saved_data["level_cells"] = level_cells;
-        ctx->saved_data["vrow"] = vrow;
-        ctx->saved_data["counts"] = counts;
-        return out;
-    }
-
-    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
-                                                   torch::autograd::variable_list grads)
-    {
-        const auto saved = ctx->get_saved_variables();
-        const at::Tensor &img = saved[0], &shapes = saved[1], &pts = saved[2], &att = saved[3];
-        const int64_t vrow = ctx->saved_data["vrow"].toInt();
-        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
-        const bool align_corners = ctx->saved_data["align_corners"].toBool();
-        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
-        const auto counts = ctx->saved_data["counts"].toIntVector();
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        const int64_t L = (int64_t)ppl.size();
-        at::Tensor gout = grads[0].contiguous();
-        if (gout.scalar_type() != pts.scalar_type()) gout = gout.to(pts.scalar_type());
-        const bool want_value = ctx->needs_input_grad(0);
-        const bool want_sample = ctx->needs_input_grad(2) || ctx->needs_input_grad(3);
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
-        at::Tensor g_img, g_pts, g_att, ws;
-        int64_t ws_bytes = 0;
-        if (want_sample) {
-            g_pts = at::empty_like(pts);
-            g_att = at::empty_like(att);
-        }
-        if (want_value) {
-            g_img = at::empty(img.sizes(), img.options());
-            const bool in_grads = want_sample && reinterpret_cast<uintptr_t>(g_pts.data_ptr()) % 16 == 0 &&
-                                  reinterpret_cast<uintptr_t>(g_att.data_ptr()) % 16 == 0 &&
-                                  reinterpret_cast<uintptr_t>(g_img.data_ptr()) % 16 == 0 && msda_get_option("overlap") != 1;
-            ws_bytes = msda_bwd_ragged_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)pts.element_size(),
-                                                       (int)img.element_size(), level_cells,
-                                                       in_grads ? MSDA_WS_RECORDS_IN_GRADS : 0);
-            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
-        }
-        if (want_value || want_sample) {
-            const c10::DeviceGuard guard(img.device());
-            check_rc(ragged_fns_for(img.scalar_type(), pts.scalar_type())
-                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(),
-                                 want_value ? g_img.data_ptr() : nullptr, want_sample ? g_pts.data_ptr() : nullptr,
-                                 want_sample ? g_att.data_ptr() : nullptr, B, I, H, D, Q, L, ppl.data(), padding_mode,
-                                 align_corners ? 1 : 0, level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr, ws_bytes,
-                                 current_stream(img)),
-                     "msda_bwd_ragged");
-        }
-        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_pts : at::Tensor(),
-                                           ctx->needs_input_grad(3) ? g_att : at::Tensor(), at::Tensor(), at::Tensor(),
-                                           at::Tensor(), at::Tensor()});
-    }
-};
-
-// Discrete (nearest-pixel) sampling (msda_fwd_discrete_ / msda_bwd_discrete_<dtype>, additions within ABI 12): the ragged
-// layout, one pixel per sample, no padding mode, no gradient for the sampling points.  A node of its own for the reason
-// MSDARaggedFunction has one: decoder-sized calls spend more host time than device time.
-using FwdDiscreteFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
-                              int64_t, int64_t, int64_t, const int32_t *, int64_t, void *);
-using BwdDiscreteFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *, int64_t,
-                              int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int64_t, int64_t, void *, int64_t,
-                              void *);
-std::pair<FwdDiscreteFn, BwdDiscreteFn> discrete_fns_for(at::ScalarType t, at::ScalarType c)
-{
-    if (t != c) {
-        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
-                          "unsupported dtype combination: value ", t, " with ", c);
-        if (t == at::kBFloat16) return {msda_fwd_discrete_f32_vbf16, msda_bwd_discrete_f32_vbf16};
-        return {msda_fwd_discrete_f32_vf16, msda_bwd_discrete_f32_vf16};
-    }
-    switch (t) {
-    case at::kFloat: return {msda_fwd_discrete_f32, msda_bwd_discrete_f32};
-    case at::kHalf: return {msda_fwd_discrete_f16, msda_bwd_discrete_f16};
-    case at::kBFloat16: return {msda_fwd_discrete_bf16, msda_bwd_discrete_bf16};
-    case at::kDouble: return {msda_fwd_discrete_f64, msda_bwd_discrete_f64};
-    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
-    }
-}
-
-class MSDADiscreteFunction : public torch::autograd::Function<MSDADiscreteFunction> {
-public:
-    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
-                              const at::Tensor &pts_, const at::Tensor &att_, int64_t level_cells,
+    static constexpr auto &family = kRagged;
+    static constexpr auto workspace_bytes = &msda_bwd_ragged_workspace_bytes;
+    static constexpr bool points_grad = true, records_in_grads = true;
+    static constexpr size_t arguments = 8;
+    static auto samples(const Call &c) { return c.per_level(); }
+    static auto mode(const Call &c) { return c.mode(); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &pts,
+                              const at::Tensor &att, int64_t padding_mode, bool align_corners, int64_t level_cells,
                               const std::vector<int64_t> &counts)
     {
-        const auto [img, vrow] = value_rows(img_);
-        const at::Tensor pts = pts_.contiguous(), att = att_.contiguous();
-        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        at::Tensor out = at::empty({B, Q, H, D}, pts.options());
-        const c10::DeviceGuard guard(img.device());
-        check_rc(discrete_fns_for(img.scalar_type(), pts.scalar_type())
-                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(), out.data_ptr(), B,
-                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), vrow, current_stream(img)),
-                 "msda_fwd_discrete");
-        ctx->save_for_backward({img, shapes, pts, att});
-        ctx->saved_data["level_cells"] = level_cells;
-        ctx->saved_data["vrow"] = vrow;
-        ctx->saved_data["counts"] = counts;
-        return out;
+        return node_forward<MSDARaggedFunction>(ctx, img, shapes, pts, att, {padding_mode, align_corners, level_cells, counts});
     }
-
-    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
-                                                   torch::autograd::variable_list grads)
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        const auto saved = ctx->get_saved_variables();
-        const at::Tensor &img = saved[0], &shapes = saved[1], &pts = saved[2], &att = saved[3];
-        const int64_t vrow = ctx->saved_data["vrow"].toInt();
-        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
-        const auto counts = ctx->saved_data["counts"].toIntVector();
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        const int64_t L = (int64_t)ppl.size();
-        at::Tensor gout = grads[0].contiguous();
-        if (gout.scalar_type() != pts.scalar_type()) gout = gout.to(pts.scalar_type());
-        const bool want_value = ctx->needs_input_grad(0), want_attn = ctx->needs_input_grad(3);
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = pts.size(1);
-        at::Tensor g_img, g_att, ws;
-        int64_t ws_bytes = 0;
-        if (want_attn) g_att = at::empty_like(att);
-        if (want_value) {
-            g_img = at::empty(img.sizes(), img.options());
-            ws_bytes = msda_bwd_discrete_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)pts.element_size(),
-                                                         (int)img.element_size(), level_cells, 0);
-            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
-        }
-        if (want_value || want_attn) {
-            const c10::DeviceGuard guard(img.device());
-            check_rc(discrete_fns_for(img.scalar_type(), pts.scalar_type())
-                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), pts.data_ptr(), att.data_ptr(),
-                                 want_value ? g_img.data_ptr() : nullptr, want_attn ? g_att.data_ptr() : nullptr, B, I, H, D,
-                                 Q, L, ppl.data(), level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr, ws_bytes,
-                                 current_stream(img)),
-                     "msda_bwd_discrete");
-        }
-        // (the sampling points: no gradient in this mode)
-        return once_differentiable(grads, {g_img, at::Tensor(), at::Tensor(), g_att, at::Tensor(), at::Tensor()});
+        return sampling_backward<MSDARaggedFunction>(ctx, std::move(grads));
     }
 };
 
-// The module core with its prologue fused in (msda_fwd_fused_ / msda_bwd_fused_<dtype>).  The caller has checked
-// L*P <= msda_fused_lp_limit(D, element size): the library then never declines.
+// Discrete (nearest-pixel) sampling (msda_fwd_discrete_ / msda_bwd_discrete_<dtype>, additions within ABI 12): the
+// per-level-count layout, one pixel per sample, no padding mode, no gradient for the sampling points (and so no gradient
+// buffers to lend the sorted records).
+class MSDADiscreteFunction : public torch::autograd::Function<MSDADiscreteFunction> {
+public:
+    static constexpr auto &family = kDiscrete;
+    static constexpr auto workspace_bytes = &msda_bwd_discrete_workspace_bytes;
+    static constexpr bool points_grad = false, records_in_grads = false;
+    static constexpr size_t arguments = 6;
+    static auto samples(const Call &c) { return c.per_level(); }
+    static auto mode(const Call &) { return std::make_tuple(); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &pts,
+                              const at::Tensor &att, int64_t level_cells, const std::vector<int64_t> &counts)
+    {
+        return node_forward<MSDADiscreteFunction>(ctx, img, shapes, pts, att, {0, false, level_cells, counts});
+    }
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
+    {
+        return sampling_backward<MSDADiscreteFunction>(ctx, std::move(grads));
+    }
+};
+
+// The module core with its prologue fused in (msda_fwd_fused_ / msda_bwd_fused_<dtype>): proj [B, Q, H, L, P, 3], ref
+// [B, Q, ref_dim].  For this and the fused nodes below the Python caller has checked that the fused kernels take the call
+// (L * P, or S, within msda_fused_lp_limit(D, element size); at most 8 levels with counts): the library then never declines.
 class MSDAFusedFunction : public torch::autograd::Function<MSDAFusedFunction> {
 public:
-    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
-                              const at::Tensor &proj_, const at::Tensor &ref_, int64_t padding_mode, bool align_corners,
-                              int64_t level_cells)
+    static constexpr auto &family = kFused;
+    static constexpr auto workspace_bytes = &msda_bwd_fused_workspace_bytes;
+    static constexpr bool per_level_ref = false;
+    static constexpr size_t arguments = 7;
+    static auto samples(const Call &c) { return c.uniform(); }
+    static auto mode(const Call &c) { return c.fused_mode(); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj,
+                              const at::Tensor &ref, int64_t padding_mode, bool align_corners, int64_t level_cells)
     {
-        const auto [img, vrow] = value_rows(img_);
-        const at::Tensor proj = proj_.contiguous(), ref = ref_.contiguous();
-        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
-        const int64_t Q = proj.size(1), L = proj.size(3), P = proj.size(4);
-        at::Tensor out = at::empty({B, Q, H, D}, proj.options());
-        const c10::DeviceGuard guard(img.device());
-        check_rc(fns_for(img.scalar_type(), proj.scalar_type())
-                     .fwd_fused(img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(), out.data_ptr(),
-                                B, I, H, D, Q, L, P, (int)ref.size(-1), (int)padding_mode, align_corners ? 1 : 0, vrow,
-                                current_stream(img)),
-                 "msda_fwd_fused");
-        ctx->save_for_backward({img, shapes, proj, ref});
-        ctx->saved_data["padding_mode"] = padding_mode;
-        ctx->saved_data["align_corners"] = align_corners;
-        ctx->saved_data["level_cells"] = level_cells;
-        ctx->saved_data["vrow"] = vrow;
-        return out;
+        return node_forward<MSDAFusedFunction>(ctx, img, shapes, proj, ref, {padding_mode, align_corners, level_cells});
     }
-
-    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
-                                                   torch::autograd::variable_list grads)
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        const auto saved = ctx->get_saved_variables();
-        const at::Tensor &img = saved[0], &shapes = saved[1], &proj = saved[2], &ref = saved[3];
-        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
-        const bool align_corners = ctx->saved_data["align_corners"].toBool();
-        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
-        const int64_t vrow = ctx->saved_data["vrow"].toInt();
-        at::Tensor gout = grads[0].contiguous();
-        if (gout.scalar_type() != proj.scalar_type()) gout = gout.to(proj.scalar_type());
-        const bool want_value = ctx->needs_input_grad(0);
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
-        const int64_t Q = proj.size(1), L = proj.size(3), P = proj.size(4);
-        const int64_t ref_dim = ref.size(-1);
-        at::Tensor g_img, ws;
-        at::Tensor g_proj = at::empty_like(proj), g_ref_part = at::empty({B, Q, H, ref_dim}, proj.options());
-        int64_t ws_bytes = 0;
-        if (want_value) {
-            g_img = at::empty(img.sizes(), img.options());
-            ws_bytes = msda_bwd_fused_workspace_bytes(B, I, H, D, Q, L, P, (int)proj.element_size(),
-                                                      (int)img.element_size(), level_cells, 0);
-            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
-        }
-        {
-            const c10::DeviceGuard guard(img.device());
-            check_rc(fns_for(img.scalar_type(), proj.scalar_type())
-                         .bwd_fused(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(),
-                                    ref.data_ptr(), want_value ? g_img.data_ptr() : nullptr, g_proj.data_ptr(),
-                                    g_ref_part.data_ptr(), B, I, H, D, Q, L, P, (int)ref_dim, padding_mode,
-                                    align_corners ? 1 : 0, level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr,
-                                    ws_bytes, current_stream(img)),
-                     "msda_bwd_fused");
-        }
-        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_proj : at::Tensor(),
-                                           ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor(), at::Tensor(),
-                                           at::Tensor(), at::Tensor()});
+        return fused_backward<MSDAFusedFunction>(ctx, std::move(grads));
     }
 };
 
-// The fused module core with per-level point counts (msda_fwd_fused_ragged_ / msda_bwd_fused_ragged_<dtype>, additions
-// within ABI 12): proj [B, Q, H, S, 3], `counts` the L point counts (host numbers; the Python caller checked them, that
-// they are not all equal and that the fused kernels take them — S within msda_fused_lp_limit, at most 8 levels — so the
-// library never declines).  A node of its own for the reason MSDARaggedFunction has one.
-using FwdFusedRaggedFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
-                                 int64_t, int64_t, int64_t, const int32_t *, int, int, int, int64_t, void *);
-using BwdFusedRaggedFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *,
-                                 void *, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, int, int, int,
-                                 int64_t, int64_t, void *, int64_t, void *);
-std::pair<FwdFusedRaggedFn, BwdFusedRaggedFn> fused_ragged_fns_for(at::ScalarType t, at::ScalarType c)
-{
-    if (t != c) {
-        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
-                          "unsupported dtype combination: value ", t, " with ", c);
-        if (t == at::kBFloat16) return {msda_fwd_fused_ragged_f32_vbf16, msda_bwd_fused_ragged_f32_vbf16};
-        return {msda_fwd_fused_ragged_f32_vf16, msda_bwd_fused_ragged_f32_vf16};
-    }
-    switch (t) {
-    case at::kFloat: return {msda_fwd_fused_ragged_f32, msda_bwd_fused_ragged_f32};
-    case at::kHalf: return {msda_fwd_fused_ragged_f16, msda_bwd_fused_ragged_f16};
-    case at::kBFloat16: return {msda_fwd_fused_ragged_bf16, msda_bwd_fused_ragged_bf16};
-    case at::kDouble: return {msda_fwd_fused_ragged_f64, msda_bwd_fused_ragged_f64};
-    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
-    }
-}
-
+// ... with per-level point counts (msda_fwd_fused_ragged_ / msda_bwd_fused_ragged_<dtype>, additions within ABI 12):
+// proj [B, Q, H, S, 3]
 class MSDAFusedRaggedFunction : public torch::autograd::Function<MSDAFusedRaggedFunction> {
 public:
-    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
-                              const at::Tensor &proj_, const at::Tensor &ref_, int64_t padding_mode, bool align_corners,
-                              int64_t level_cells, const std::vector<int64_t> &counts)
+    static constexpr auto &family = kFusedRagged;
+    static constexpr auto workspace_bytes = &msda_bwd_fused_ragged_workspace_bytes;
+    static constexpr bool per_level_ref = false;
+    static constexpr size_t arguments = 8;
+    static auto samples(const Call &c) { return c.per_level(); }
+    static auto mode(const Call &c) { return c.fused_mode(); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj,
+                              const at::Tensor &ref, int64_t padding_mode, bool align_corners, int64_t level_cells,
+                              const std::vector<int64_t> &counts)
     {
-        const auto [img, vrow] = value_rows(img_);
-        const at::Tensor proj = proj_.contiguous(), ref = ref_.contiguous();
-        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        at::Tensor out = at::empty({B, Q, H, D}, proj.options());
-        const c10::DeviceGuard guard(img.device());
-        check_rc(fused_ragged_fns_for(img.scalar_type(), proj.scalar_type())
-                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(), out.data_ptr(), B,
-                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), (int)ref.size(-1), (int)padding_mode,
-                            align_corners ? 1 : 0, vrow, current_stream(img)),
-                 "msda_fwd_fused_ragged");
-        ctx->save_for_backward({img, shapes, proj, ref});
-        ctx->saved_data["padding_mode"] = padding_mode;
-        ctx->saved_data["align_corners"] = align_corners;
-        ctx->saved_data["level_cells"] = level_cells;
-        ctx->saved_data["vrow"] = vrow;
-        ctx->saved_data["counts"] = counts;
-        return out;
+        return node_forward<MSDAFusedRaggedFunction>(ctx, img, shapes, proj, ref,
+                                                     {padding_mode, align_corners, level_cells, counts});
     }
-
-    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
-                                                   torch::autograd::variable_list grads)
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        const auto saved = ctx->get_saved_variables();
-        const at::Tensor &img = saved[0], &shapes = saved[1], &proj = saved[2], &ref = saved[3];
-        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
-        const bool align_corners = ctx->saved_data["align_corners"].toBool();
-        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
-        const int64_t vrow = ctx->saved_data["vrow"].toInt();
-        const auto counts = ctx->saved_data["counts"].toIntVector();
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        const int64_t L = (int64_t)ppl.size();
-        at::Tensor gout = grads[0].contiguous();
-        if (gout.scalar_type() != proj.scalar_type()) gout = gout.to(proj.scalar_type());
-        const bool want_value = ctx->needs_input_grad(0);
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
-        const int64_t ref_dim = ref.size(-1);
-        at::Tensor g_img, ws;
-        at::Tensor g_proj = at::empty_like(proj), g_ref_part = at::empty({B, Q, H, ref_dim}, proj.options());
-        int64_t ws_bytes = 0;
-        if (want_value) {
-            g_img = at::empty(img.sizes(), img.options());
-            ws_bytes = msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)proj.element_size(),
-                                                             (int)img.element_size(), level_cells, 0);
-            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
-        }
-        {
-            const c10::DeviceGuard guard(img.device());
-            check_rc(fused_ragged_fns_for(img.scalar_type(), proj.scalar_type())
-                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(),
-                                 want_value ? g_img.data_ptr() : nullptr, g_proj.data_ptr(), g_ref_part.data_ptr(), B, I, H,
-                                 D, Q, L, ppl.data(), (int)ref_dim, padding_mode, align_corners ? 1 : 0, level_cells, vrow,
-                                 ws.defined() ? ws.data_ptr() : nullptr, ws_bytes, current_stream(img)),
-                     "msda_bwd_fused_ragged");
-        }
-        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_proj : at::Tensor(),
-                                           ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor(), at::Tensor(),
-                                           at::Tensor(), at::Tensor(), at::Tensor()});
+        return fused_backward<MSDAFusedRaggedFunction>(ctx, std::move(grads));
     }
 };
 
-// The fused module core for Hugging Face's box rule with per-level point counts (msda_fwd_fused_hfbox_ /
-// msda_bwd_fused_hfbox_<dtype>, additions within ABI 12): proj [B, Q, H, S, 3], ref [B, Q, 4], `counts` the L point counts
-// and `level_scale` the L fp32 scales as host numbers (float32(1 / P_l): the Python caller computed them on the host and
-// checked that the fused kernels take the counts, so the library never declines), `offset_scale` the module's.  The
-// workspace is the fused per-level-count pair's.
-using FwdFusedHfBoxFn = int (*)(const void *, const int64_t *, const void *, const void *, void *, int64_t, int64_t, int64_t,
-                                int64_t, int64_t, int64_t, const int32_t *, const float *, double, int, int, int, int64_t,
-                                void *);
-using BwdFusedHfBoxFn = int (*)(const void *, const void *, const int64_t *, const void *, const void *, void *, void *,
-                                void *, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, const float *,
-                                double, int, int, int, int64_t, int64_t, void *, int64_t, void *);
-std::pair<FwdFusedHfBoxFn, BwdFusedHfBoxFn> fused_hfbox_fns_for(at::ScalarType t, at::ScalarType c)
-{
-    if (t != c) {
-        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
-                          "unsupported dtype combination: value ", t, " with ", c);
-        if (t == at::kBFloat16) return {msda_fwd_fused_hfbox_f32_vbf16, msda_bwd_fused_hfbox_f32_vbf16};
-        return {msda_fwd_fused_hfbox_f32_vf16, msda_bwd_fused_hfbox_f32_vf16};
-    }
-    switch (t) {
-    case at::kFloat: return {msda_fwd_fused_hfbox_f32, msda_bwd_fused_hfbox_f32};
-    case at::kHalf: return {msda_fwd_fused_hfbox_f16, msda_bwd_fused_hfbox_f16};
-    case at::kBFloat16: return {msda_fwd_fused_hfbox_bf16, msda_bwd_fused_hfbox_bf16};
-    case at::kDouble: return {msda_fwd_fused_hfbox_f64, msda_bwd_fused_hfbox_f64};
-    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
-    }
-}
-
+// ... for Hugging Face's box rule with per-level point counts (msda_fwd_fused_hfbox_ / msda_bwd_fused_hfbox_<dtype>,
+// additions within ABI 12): proj [B, Q, H, S, 3], ref [B, Q, 4], `level_scale` float32(1 / P_l) as the Python caller
+// computed it on the host, `offset_scale` the module's.  The workspace is the fused per-level-count pair's.
 class MSDAFusedHfBoxFunction : public torch::autograd::Function<MSDAFusedHfBoxFunction> {
 public:
-    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
-                              const at::Tensor &proj_, const at::Tensor &ref_, int64_t padding_mode, bool align_corners,
-                              int64_t level_cells, const std::vector<int64_t> &counts, const std::vector<double> &level_scale,
-                              double offset_scale)
+    static constexpr auto &family = kFusedHfBox;
+    static constexpr auto workspace_bytes = &msda_bwd_fused_ragged_workspace_bytes;
+    static constexpr bool per_level_ref = false;
+    static constexpr size_t arguments = 10;
+    static auto samples(const Call &c) { return c.per_level(); }
+    static auto mode(const Call &c) { return c.hfbox_mode(); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj,
+                              const at::Tensor &ref, int64_t padding_mode, bool align_corners, int64_t level_cells,
+                              const std::vector<int64_t> &counts, const std::vector<double> &level_scale, double offset_scale)
     {
         TORCH_CHECK_VALUE(level_scale.size() == counts.size(), "level_scale and points_per_level differ in length");
-        const auto [img, vrow] = value_rows(img_);
-        const at::Tensor proj = proj_.contiguous(), ref = ref_.contiguous();
-        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        const std::vector<float> scale(level_scale.begin(), level_scale.end());  // (fp32 values: the conversion is exact)
-        at::Tensor out = at::empty({B, Q, H, D}, proj.options());
-        const c10::DeviceGuard guard(img.device());
-        check_rc(fused_hfbox_fns_for(img.scalar_type(), proj.scalar_type())
-                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(), out.data_ptr(), B,
-                            I, H, D, Q, (int64_t)ppl.size(), ppl.data(), scale.data(), offset_scale, (int)ref.size(-1),
-                            (int)padding_mode, align_corners ? 1 : 0, vrow, current_stream(img)),
-                 "msda_fwd_fused_hfbox");
-        ctx->save_for_backward({img, shapes, proj, ref});
-        ctx->saved_data["padding_mode"] = padding_mode;
-        ctx->saved_data["align_corners"] = align_corners;
-        ctx->saved_data["level_cells"] = level_cells;
-        ctx->saved_data["vrow"] = vrow;
-        ctx->saved_data["counts"] = counts;
-        ctx->saved_data["level_scale"] = level_scale;
-        ctx->saved_data["offset_scale"] = offset_scale;
-        return out;
+        return node_forward<MSDAFusedHfBoxFunction>(
+            ctx, img, shapes, proj, ref, {padding_mode, align_corners, level_cells, counts, level_scale, offset_scale});
     }
-
-    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
-                                                   torch::autograd::variable_list grads)
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        const auto saved = ctx->get_saved_variables();
-        const at::Tensor &img = saved[0], &shapes = saved[1], &proj = saved[2], &ref = saved[3];
-        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
-        const bool align_corners = ctx->saved_data["align_corners"].toBool();
-        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
-        const int64_t vrow = ctx->saved_data["vrow"].toInt();
-        const auto counts = ctx->saved_data["counts"].toIntVector();
-        const auto level_scale = ctx->saved_data["level_scale"].toDoubleVector();
-        const double offset_scale = ctx->saved_data["offset_scale"].toDouble();
-        const std::vector<int32_t> ppl(counts.begin(), counts.end());
-        const std::vector<float> scale(level_scale.begin(), level_scale.end());
-        const int64_t L = (int64_t)ppl.size();
-        at::Tensor gout = grads[0].contiguous();
-        if (gout.scalar_type() != proj.scalar_type()) gout = gout.to(proj.scalar_type());
-        const bool want_value = ctx->needs_input_grad(0);
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3), Q = proj.size(1);
-        const int64_t ref_dim = ref.size(-1);
-        at::Tensor g_img, ws;
-        at::Tensor g_proj = at::empty_like(proj), g_ref_part = at::empty({B, Q, H, ref_dim}, proj.options());
-        int64_t ws_bytes = 0;
-        if (want_value) {
-            g_img = at::empty(img.sizes(), img.options());
-            ws_bytes = msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, L, ppl.data(), (int)proj.element_size(),
-                                                             (int)img.element_size(), level_cells, 0);
-            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
-        }
-        {
-            const c10::DeviceGuard guard(img.device());
-            check_rc(fused_hfbox_fns_for(img.scalar_type(), proj.scalar_type())
-                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(),
-                                 want_value ? g_img.data_ptr() : nullptr, g_proj.data_ptr(), g_ref_part.data_ptr(), B, I, H,
-                                 D, Q, L, ppl.data(), scale.data(), offset_scale, (int)ref_dim, padding_mode,
-                                 align_corners ? 1 : 0, level_cells, vrow, ws.defined() ? ws.data_ptr() : nullptr, ws_bytes,
-                                 current_stream(img)),
-                     "msda_bwd_fused_hfbox");
-        }
-        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_proj : at::Tensor(),
-                                           ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor(), at::Tensor(),
-                                           at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()});
+        return fused_backward<MSDAFusedHfBoxFunction>(ctx, std::move(grads));
     }
 };
 
-// The fused module core for per-level reference points and transformers' point rule (msda_fwd_fused_levelref_ /
-// msda_bwd_fused_levelref_<dtype>, additions within ABI 12): ref [B, Q, L, ref_dim], the kernel's partials
-// [B, Q, H, L, ref_dim] summed over the heads here.  The Python caller has checked L * P <= msda_fused_lp_limit, so the
-// library never declines; the workspace is the uniform fused pair's.
-std::pair<FwdFusedFn, BwdFusedFn> fused_levelref_fns_for(at::ScalarType t, at::ScalarType c)
-{
-    if (t != c) {
-        TORCH_CHECK_VALUE(c == at::kFloat && (t == at::kBFloat16 || t == at::kHalf),
-                          "unsupported dtype combination: value ", t, " with ", c);
-        if (t == at::kBFloat16) return {msda_fwd_fused_levelref_f32_vbf16, msda_bwd_fused_levelref_f32_vbf16};
-        return {msda_fwd_fused_levelref_f32_vf16, msda_bwd_fused_levelref_f32_vf16};
-    }
-    switch (t) {
-    case at::kFloat: return {msda_fwd_fused_levelref_f32, msda_bwd_fused_levelref_f32};
-    case at::kHalf: return {msda_fwd_fused_levelref_f16, msda_bwd_fused_levelref_f16};
-    case at::kBFloat16: return {msda_fwd_fused_levelref_bf16, msda_bwd_fused_levelref_bf16};
-    case at::kDouble: return {msda_fwd_fused_levelref_f64, msda_bwd_fused_levelref_f64};
-    default: TORCH_CHECK_VALUE(false, "unsupported dtype ", t);
-    }
-}
-
+// ... for per-level reference points and transformers' point rule (msda_fwd_fused_levelref_ / msda_bwd_fused_levelref_<dtype>,
+// additions within ABI 12): ref [B, Q, L, ref_dim].  The workspace is the uniform fused pair's.
 class MSDAFusedLevelRefFunction : public torch::autograd::Function<MSDAFusedLevelRefFunction> {
 public:
-    static at::Tensor forward(torch::autograd::AutogradContext *ctx, const at::Tensor &img_, const at::Tensor &shapes_,
-                              const at::Tensor &proj_, const at::Tensor &ref_, int64_t padding_mode, bool align_corners,
-                              int64_t level_cells)
+    static constexpr auto &family = kFusedLevelRef;
+    static constexpr auto workspace_bytes = &msda_bwd_fused_workspace_bytes;
+    static constexpr bool per_level_ref = true;
+    static constexpr size_t arguments = 7;
+    static auto samples(const Call &c) { return c.uniform(); }
+    static auto mode(const Call &c) { return c.fused_mode(); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj,
+                              const at::Tensor &ref, int64_t padding_mode, bool align_corners, int64_t level_cells)
     {
-        const auto [img, vrow] = value_rows(img_);
-        const at::Tensor proj = proj_.contiguous(), ref = ref_.contiguous();
-        const at::Tensor shapes = shapes_.to(at::kLong).contiguous();
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
-        const int64_t Q = proj.size(1), L = proj.size(3), P = proj.size(4);
-        at::Tensor out = at::empty({B, Q, H, D}, proj.options());
-        const c10::DeviceGuard guard(img.device());
-        check_rc(fused_levelref_fns_for(img.scalar_type(), proj.scalar_type())
-                     .first(img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(), out.data_ptr(), B,
-                            I, H, D, Q, L, P, (int)ref.size(-1), (int)padding_mode, align_corners ? 1 : 0, vrow,
-                            current_stream(img)),
-                 "msda_fwd_fused_levelref");
-        ctx->save_for_backward({img, shapes, proj, ref});
-        ctx->saved_data["padding_mode"] = padding_mode;
-        ctx->saved_data["align_corners"] = align_corners;
-        ctx->saved_data["level_cells"] = level_cells;
-        ctx->saved_data["vrow"] = vrow;
-        return out;
+        return node_forward<MSDAFusedLevelRefFunction>(ctx, img, shapes, proj, ref, {padding_mode, align_corners, level_cells});
     }
-
-    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
-                                                   torch::autograd::variable_list grads)
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        const auto saved = ctx->get_saved_variables();
-        const at::Tensor &img = saved[0], &shapes = saved[1], &proj = saved[2], &ref = saved[3];
-        const int padding_mode = (int)ctx->saved_data["padding_mode"].toInt();
-        const bool align_corners = ctx->saved_data["align_corners"].toBool();
-        const int64_t level_cells = ctx->saved_data["level_cells"].toInt();
-        const int64_t vrow = ctx->saved_data["vrow"].toInt();
-        at::Tensor gout = grads[0].contiguous();
-        if (gout.scalar_type() != proj.scalar_type()) gout = gout.to(proj.scalar_type());
-        const bool want_value = ctx->needs_input_grad(0);
-        const int64_t B = img.size(0), I = img.size(1), H = img.size(2), D = img.size(3);
-        const int64_t Q = proj.size(1), L = proj.size(3), P = proj.size(4);
-        const int64_t ref_dim = ref.size(-1);
-        at::Tensor g_img, ws;
-        at::Tensor g_proj = at::empty_like(proj), g_ref_part = at::empty({B, Q, H, L, ref_dim}, proj.options());
-        int64_t ws_bytes = 0;
-        if (want_value) {
-            g_img = at::empty(img.sizes(), img.options());
-            ws_bytes = msda_bwd_fused_workspace_bytes(B, I, H, D, Q, L, P, (int)proj.element_size(),
-                                                      (int)img.element_size(), level_cells, 0);
-            ws = at::empty({ws_bytes}, img.options().dtype(at::kByte));
-        }
-        {
-            const c10::DeviceGuard guard(img.device());
-            check_rc(fused_levelref_fns_for(img.scalar_type(), proj.scalar_type())
-                         .second(gout.data_ptr(), img.data_ptr(), shapes.data_ptr<int64_t>(), proj.data_ptr(), ref.data_ptr(),
-                                 want_value ? g_img.data_ptr() : nullptr, g_proj.data_ptr(), g_ref_part.data_ptr(), B, I, H,
-                                 D, Q, L, P, (int)ref_dim, padding_mode, align_corners ? 1 : 0, level_cells, vrow,
-                                 ws.defined() ? ws.data_ptr() : nullptr, ws_bytes, current_stream(img)),
-                     "msda_bwd_fused_levelref");
-        }
-        return once_differentiable(grads, {g_img, at::Tensor(), ctx->needs_input_grad(2) ? g_proj : at::Tensor(),
-                                           ctx->needs_input_grad(3) ? g_ref_part.sum(2) : at::Tensor(), at::Tensor(),
-                                           at::Tensor(), at::Tensor()});
+        return fused_backward<MSDAFusedLevelRefFunction>(ctx, std::move(grads));
     }
 };
 

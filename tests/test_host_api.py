@@ -181,6 +181,47 @@ def test_optional_cpp_binding_builds_and_matches_the_abi():
     assert mod is not None and int(mod.abi_version()) == _lib.ABI_VERSION
 
 
+# first line of each callable's __doc__ (pybind11's rendered signature: argument names, order and defaults) — recorded
+# literals, not derived from the source: the Python callers depend on them
+_T, _I, _F = "torch.Tensor", "typing.SupportsInt", "typing.SupportsFloat"
+_COUNTS = f"points_per_level: collections.abc.Sequence[{_I}]"
+_SAMPLING = f"img: {_T}, shapes: {_T}, sampling_points: {_T}, attention_weights: {_T}"
+_FUSED = f"img: {_T}, shapes: {_T}, proj: {_T}, reference_points: {_T}"
+_MODE = f"padding_mode: {_I}, align_corners: bool"
+CPP_BINDING_SIGNATURES = {
+    "abi_version": "abi_version() -> int",
+    "fused_lp_limit": f"fused_lp_limit(arg0: {_I}, arg1: {_I}) -> int",
+    "msda": f"msda({_SAMPLING}, {_MODE}, level_cells: {_I} = 0) -> {_T}",
+    "msda_discrete": f"msda_discrete({_SAMPLING}, level_cells: {_I}, {_COUNTS}) -> {_T}",
+    "msda_fused": f"msda_fused({_FUSED}, {_MODE}, level_cells: {_I} = 0) -> {_T}",
+    "msda_fused_hfbox": f"msda_fused_hfbox({_FUSED}, {_MODE}, level_cells: {_I}, {_COUNTS}, "
+                        f"level_scale: collections.abc.Sequence[{_F}], offset_scale: {_F}) -> {_T}",
+    "msda_fused_levelref": f"msda_fused_levelref({_FUSED}, {_MODE}, level_cells: {_I} = 0) -> {_T}",
+    "msda_fused_ragged": f"msda_fused_ragged({_FUSED}, {_MODE}, level_cells: {_I}, {_COUNTS}) -> {_T}",
+    "msda_ragged": f"msda_ragged({_SAMPLING}, {_MODE}, level_cells: {_I}, {_COUNTS}) -> {_T}",
+    "msda_rows": f"msda_rows(img: {_T}, shapes: {_T}, sampling_points_rows: {_T}, attention_weights_rows: {_T}, {_MODE}, "
+                 f"num_queries: {_I}, r0: {_I}, r1: {_I}, chunks: {_I} = 1, level_cells: {_I} = 0) -> {_T}",
+    "rows_backward": f"rows_backward(arg0: {_T}, arg1: {_T}, arg2: {_T}, arg3: {_T}, arg4: {_T}, arg5: {_I}, arg6: {_I}, "
+                     f"arg7: {_I}, arg8: {_I}, arg9: bool, arg10: bool, arg11: bool, arg12: bool, arg13: {_I}) "
+                     f"-> tuple[{_T}, {_T}, {_T}]",
+    "rows_forward": f"rows_forward(arg0: {_T}, arg1: {_T}, arg2: {_T}, arg3: {_T}, arg4: {_I}, arg5: {_T}, arg6: {_I}, "
+                    f"arg7: {_I}, arg8: {_I}, arg9: {_I}, arg10: bool) -> None",
+}
+
+
+def test_cpp_binding_exports_the_same_callables_with_the_same_signatures():
+    """What Python sees of csrc/msda_torch_ext.cpp: exactly these callables, each with these argument names, order and
+    defaults (functional.py, ragged.py, discrete.py and distributed.py call them by position and by keyword)."""
+    from msda_triton_amd import _ext
+    _ext.build()
+    mod = _ext.load()
+    assert mod is not None
+    public = {n for n in dir(mod) if not n.startswith("_") and callable(getattr(mod, n))}
+    assert public == set(CPP_BINDING_SIGNATURES), public ^ set(CPP_BINDING_SIGNATURES)
+    for name, signature in CPP_BINDING_SIGNATURES.items():
+        assert getattr(mod, name).__doc__.splitlines()[0] == signature, name
+
+
 def test_backward_workspace_sizes_stay_within_budget():
     """msda_bwd_workspace_bytes (no GPU needed): the sorted pipeline's scratch is sized from the shapes alone —
     round 1 asked for 319 MB at c2 @ 10k and 5.6 GB at c5; the pixel-indexed partial rows brought that down, and
