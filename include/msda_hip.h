@@ -48,7 +48,10 @@
  * (offset gradients scaled back, softmax backward applied to the logits) and grad_ref_partial
  * [B, Q, H, ref_dim] — the per-head partial sums of the reference points' gradient, which the caller adds up
  * over H.  It needs msda_bwd_fused_workspace_bytes(...) of workspace when grad_value is wanted (the derived
- * sampling points / attention weights are parked there for the grad_value passes).  Same
+ * sampling points / attention weights are parked there for the grad_value passes — in the arithmetic type, except
+ * that the 16-bit operators (bf16, f16) park them in float32 and run the float32 grad_value passes on their 16-bit rows,
+ * as the f32_s* suffixes do: grad_value is sampled where `out` and grad_proj are.  The fused workspace queries therefore
+ * size an elem_size of 2 as 4, and such a backward with grad_value has the float32 size limits).  Same
  * MSDA_ERR_UNSUPPORTED rule as the fused forward (nothing is launched then).
  *
  * Backward workspace: grad_value is computed as a gather over a per-call inverted index (sample
@@ -561,6 +564,14 @@ MSDA_API int msda_get_option(const char *key);
  * of the level list that fits);  "fwd_lds_planes";  "fwd_workgroups";  "sample_variant", "sample_lds_level_bytes" the same
  * for the sample-gradient kernel (2 = the discrete attention-weight gradient);  "value_path" 1 = single-launch kernel, 2 = sorted pipeline;  "value_passes" its passes
  * over the batch.
+ * WHICH TEMPLATE INSTANTIATION ran (last values too, added within ABI 12 — keys are looked up by name): "fwd_vec",
+ * "fwd_group", "fwd_chunks" of the last forward launch (plain, LDS-served, one wave per unit — group = D / vec, one chunk —,
+ * discrete, and the fused forwards);  "sample_vec", "sample_group", "sample_chunks" of the last sample-gradient launch
+ * (discrete: the attention-weight gradient);  "value_vec", "value_group", "value_chunks" of the last grad_value launch (the
+ * single-launch kernel, or the sorted pipeline's gather and finish passes).  vec: channels per lane — 16 bytes of the
+ * arithmetic type, or 1 when D is no multiple of that or a row pointer is not 16-byte aligned;  group: lanes per (b, q, h)
+ * unit, the smallest of 4, 8, 16, 32, 64 that holds ceil(D / vec) — 64 beyond;  chunks: ceil(D / (group * vec)) trips
+ * of the kernels' channel loop.  0 before the first launch of that kind.
  * "grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches" are COUNTERS, not last values: launches so far in this
  * process whose (plane, slot) grid took the XCD-aware 3-D form dim3(8, slots, ceil(planes / 8)), the linear 2-D form
  * dim3(slots, planes), or the flat 1-D form that decodes its block index with a division (more than 65535 slots, plane

@@ -186,10 +186,11 @@ void profile_end(void *token, hipStream_t stream)
 
 // ---- measurement only: what the last launches were (msda_last_launch_info) — process-wide, like the profile records:
 //      autograd issues the backward from its own thread ----
-static std::atomic<int> g_info[8];
+constexpr int kLaunchInfoSlots = 17;  // (msda_launch.hpp, note_launch: 0-7 as before, 8-16 the instantiations)
+static std::atomic<int> g_info[kLaunchInfoSlots];
 void note_launch(int slot, int value)
 {
-    if (slot >= 0 && slot < 8) g_info[slot].store(value, std::memory_order_relaxed);
+    if (slot >= 0 && slot < kLaunchInfoSlots) g_info[slot].store(value, std::memory_order_relaxed);
 }
 // ... and launches per grid form (plane_grid): counters, not last values — a route makes several plane_grid launches, and a
 // test wants to know that NONE of them took another form (reported modulo 2^31)
@@ -235,6 +236,9 @@ extern "C" int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t 
     // the sorted pipeline's own workspace (msda_launch.hpp: fused_mat_bytes)
     (void)value_elem_size;
     if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, P, elem_size, 0)) return 0;  // (a call of this size is refused)
+    // the 16-bit operators park the derived points in float and run the float grad_value passes (msda_common.hpp, ParkType)
+    if (elem_size == 2) elem_size = 4;
+    if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, P, elem_size, 0)) return 0;
     const int64_t mat = (B * Q * H * L * P * 3 * (int64_t)elem_size + 255) / 256 * 256;
     return mat + msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, P, elem_size, 0, 0, max_level_cells,
                                                ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), 0);
@@ -256,9 +260,13 @@ extern "C" const char *msda_last_error(void) { return msda::g_err; }
 
 extern "C" int msda_last_launch_info(const char *key)
 {
-    static const char *const kKeys[8] = {"fwd_variant", "fwd_lds_level_bytes", "fwd_lds_planes", "fwd_workgroups",
-                                         "sample_variant", "sample_lds_level_bytes", "value_path", "value_passes"};
-    for (int i = 0; key != nullptr && i < 8; ++i)
+    static const char *const kKeys[msda::kLaunchInfoSlots] = {
+        "fwd_variant", "fwd_lds_level_bytes", "fwd_lds_planes", "fwd_workgroups", "sample_variant", "sample_lds_level_bytes",
+        "value_path", "value_passes",
+        // the template instantiation of the last forward / sample-gradient / grad_value launch (note_instance)
+        "fwd_vec", "fwd_group", "fwd_chunks", "sample_vec", "sample_group", "sample_chunks", "value_vec", "value_group",
+        "value_chunks"};
+    for (int i = 0; key != nullptr && i < msda::kLaunchInfoSlots; ++i)
         if (strcmp(key, kKeys[i]) == 0) return msda::g_info[i].load(std::memory_order_relaxed);
     static const char *const kGridKeys[3] = {"grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches"};
     for (int i = 0; key != nullptr && i < 3; ++i)

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/msda_hip.h"
 
 namespace msda {
@@ -19,6 +21,11 @@ constexpr uint32_t kMaskedOffset = 0x80000000u;  // >= any buffer size we accept
 // storage type traits: how many bytes, what we accumulate in, how to convert
 // ------------------------------------------------------------------------------------------
 template <typename T> struct Traits;
+// The type in which a fused backward parks the sampling points and attention weights it derives for the grad_value passes
+// (run_bwd_fused): the arithmetic type, except that the 16-bit operators park in float — their coordinates are float
+// everywhere else, and points rounded to 8 / 11 bits moved grad_value's samples away from the forward's.
+template <typename T> using ParkType = std::conditional_t<sizeof(T) == 2, float, T>;
+
 template <> struct Traits<float> {
     using acc = float;
     static constexpr bool kDot2 = false;

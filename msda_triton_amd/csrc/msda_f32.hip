@@ -102,6 +102,9 @@ extern "C" int64_t msda_bwd_fused_ragged_workspace_bytes(int64_t B, int64_t I, i
         return 0;
     (void)value_elem_size;
     if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, pmax, elem_size, S)) return 0;
+    // the 16-bit operators park the derived points in float and run the float grad_value passes (msda_common.hpp, ParkType)
+    if (elem_size == 2) elem_size = 4;
+    if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, pmax, elem_size, S)) return 0;
     const int64_t mat = (B * Q * H * S * 3 * (int64_t)elem_size + 255) / 256 * 256;
     return mat + msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, pmax, elem_size, 0, 0, max_level_cells,
                                                ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), S);

@@ -3,3 +3,4 @@
 #include "msda_launch.hpp"
 
 MSDA_DEFINE_FUSED_STORAGE_ENTRY_POINTS(f32_sbf16, float, __bf16)
+MSDA_DEFINE_RUN_VALUE_FLOAT(__bf16)  // (for msda_bf16.hip's fused backwards)

@@ -2,3 +2,4 @@
 #include "msda_launch.hpp"
 
 MSDA_DEFINE_FUSED_STORAGE_ENTRY_POINTS(f32_sf16, float, _Float16)
+MSDA_DEFINE_RUN_VALUE_FLOAT(_Float16)  // (for msda_f16.hip's fused backwards)

@@ -1769,30 +1769,33 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                             // the sampling point and attention weight this kernel derived, for the grad_value passes
                             // (stored here, at the end of the wave's life, where nothing waits behind the stores)
                             const A ox = w_ox[rs_], oy = w_oy[rs_];
-                            Pack<T, 2> m;
+                            // (parked in float by the 16-bit operators too — ParkType: grad_value samples where `out` and grad_proj do)
+                            using MT = ParkType<T>;
+                            using MR = Traits<MT>;
+                            Pack<MT, 2> m;
                             if constexpr (kHfBox<PP>) {  // (ox, oy: the products phase 0 parked; the same operations)
-                                m.v[0] = TR::from_acc(hfbox_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]), (A)p.off_scale));
-                                m.v[1] = TR::from_acc(hfbox_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]), (A)p.off_scale));
+                                m.v[0] = MR::from_acc(hfbox_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]), (A)p.off_scale));
+                                m.v[1] = MR::from_acc(hfbox_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]), (A)p.off_scale));
                             } else if constexpr (kLevelRef<PP>) {  // (ox, oy: the quotients phase 0 parked; the same operations)
                                 if (p.ref_dim == 2) {
-                                    m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox);
-                                    m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy);
+                                    m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox);
+                                    m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy);
                                 } else {
-                                    m.v[0] = TR::from_acc(levelref_box_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2])));
-                                    m.v[1] = TR::from_acc(levelref_box_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3])));
+                                    m.v[0] = MR::from_acc(levelref_box_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2])));
+                                    m.v[1] = MR::from_acc(levelref_box_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3])));
                                 }
                             } else if (p.ref_dim == 2) {
-                                m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox / (A)tab->h[l]);
-                                m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy / (A)tab->w[l]);
+                                m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox / (A)tab->h[l]);
+                                m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy / (A)tab->w[l]);
                             } else if constexpr (kRagged<PP>) {  // (ox, oy: scaled when they were parked)
-                                m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]));
-                                m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]));
+                                m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]));
+                                m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]));
                             } else {
-                                m.v[0] = TR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) * half_inv_P);
-                                m.v[1] = TR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) * half_inv_P);
+                                m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) * half_inv_P);
+                                m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) * half_inv_P);
                             }
-                            *reinterpret_cast<Pack<T, 2> *>(static_cast<T *>(p.mat_loc) + 2 * (plane_s0 + sidx)) = m;
-                            static_cast<T *>(p.mat_attn)[plane_s0 + sidx] = TR::from_acc(a);
+                            *reinterpret_cast<Pack<MT, 2> *>(static_cast<MT *>(p.mat_loc) + 2 * (plane_s0 + sidx)) = m;
+                            static_cast<MT *>(p.mat_attn)[plane_s0 + sidx] = MR::from_acc(a);
                         }
                         Pack<TS, 1> g0, g1, g2;
                         g0.v[0] = SR::from_acc(res.v[1] * kx);

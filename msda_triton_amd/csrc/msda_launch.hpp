@@ -33,6 +33,15 @@ void set_error(const char *fmt, ...);
 // bytes, planes per workgroup, workgroups}, 4-5 sample gradients {variant, LDS level bytes}, 6 grad_value path (1 single launch,
 // 2 sorted pipeline), 7 its passes over the batch
 void note_launch(int slot, int value);
+// ... and WHICH template instantiation a launch runs: VEC channels per lane, G lanes per unit, ceil(D / (G * VEC)) channel
+// chunks — slots 8-10 the forward ("fwd_vec", "fwd_group", "fwd_chunks"), 11-13 the sample gradients, 14-16 grad_value (the
+// single-launch kernel or the sorted gather + finish).  For tests: a changed threshold must not turn a G = 64 case into a G = 16 one.
+inline void note_instance(int first_slot, int vec, int group, int D)
+{
+    note_launch(first_slot, vec);
+    note_launch(first_slot + 1, group);
+    note_launch(first_slot + 2, (D + group * vec - 1) / (group * vec));
+}
 // ... and which grid form plane_grid gave a launch: 0 XCD-aware 3-D, 1 linear 2-D, 2 flat 1-D — one process-wide counter per
 // form that only ever rises ("grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches"; callers take differences)
 void note_grid(int form);
@@ -367,9 +376,11 @@ template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T, ty
         note_launch(1, pl.lev_bytes);
         note_launch(2, pl.planes);
         note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, G, p.D);
     } else {
         note_launch(4, 1);
         note_launch(5, pl.lev_bytes);
+        note_instance(11, VEC, G, p.D);
     }
     const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
     if constexpr (MODE == 0 || MODE == 2) {
@@ -411,6 +422,7 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
             note_launch(1, 0);
             note_launch(2, 1);
             note_launch(3, (int)units);
+            note_instance(8, VEC, gl, p.D);  // (D / VEC lanes hold the row: one chunk)
             static std::atomic<uint64_t> big_lds_unit{0}, big_lds_unit2{0};
             // two units per wave (option "unit_waves" 2; msda_kernels.hpp): faster with the rows in HBM, slower with them
             // cached — which is the usual case, so one unit per wave is the default.  In-process A/B at B = 4, H = 8, one / two
@@ -470,9 +482,11 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         note_launch(1, 0);
         note_launch(2, 1);
         note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, G, p.D);
     } else {
         note_launch(4, 0);
         note_launch(5, 0);
+        note_instance(11, VEC, G, p.D);
     }
     static std::atomic<uint64_t> big_lds_done{0};  // one per template instantiation
     const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
@@ -540,6 +554,7 @@ template <typename T, int VEC, int G, int GB, typename TV = T, typename TS = T, 
         set_error("grid too large");
         return MSDA_ERR_TOO_LARGE;
     }
+    note_instance(14, VEC, G, p.D);
     {
         const ProfileScope prof("msda_value_gather_kernel", stream);
         // The gather's many small workgroups are handed to an XCD's CUs as they come free, so the planes of an XCD balance
@@ -961,6 +976,7 @@ template <typename T, int VEC, int G, typename TV = T, typename TS = T, typename
         set_error("grid too large");
         return MSDA_ERR_TOO_LARGE;
     }
+    note_instance(14, VEC, G, p.D);
     static std::atomic<uint64_t> big_lds_done{0};
     allow_big_lds(msda_value_small_kernel<T, VEC, G, TV, TS, PP>, big_lds_done);
     const ProfileScope prof("msda_value_small_kernel", stream);
@@ -1116,6 +1132,22 @@ inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_by
     return rc;
 }
 
+// The float grad_value pipeline on 16-bit rows, for the fused backwards of the 16-bit operators (ParkType).  NOT inline: the
+// 16-bit translation units declare their instantiations `extern template` (MSDA_DECLARE_RUN_VALUE_FLOAT) and the
+// float-arithmetic 16-bit-storage units, which instantiate these very kernels for themselves anyway and are built with
+// their flags, define them (MSDA_DEFINE_RUN_VALUE_FLOAT) — one copy of each kernel in the library.
+template <typename TV, typename TS, typename PP>
+int run_value_float(PP &p, const Dims &d, void *workspace, int64_t workspace_bytes, hipStream_t stream)
+{
+    return run_value<float, TV, TS>(p, d, workspace, workspace_bytes, stream);
+}
+#define MSDA_RUN_VALUE_FLOAT_(KW, TS, PP) \
+    KW template int msda::run_value_float<TS, TS, msda::PP>(msda::PP &, const msda::Dims &, void *, int64_t, hipStream_t);
+#define MSDA_DECLARE_RUN_VALUE_FLOAT(TS) \
+    MSDA_RUN_VALUE_FLOAT_(extern, TS, Params) MSDA_RUN_VALUE_FLOAT_(extern, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(extern, TS, MaskedParams)
+#define MSDA_DEFINE_RUN_VALUE_FLOAT(TS) \
+    MSDA_RUN_VALUE_FLOAT_(, TS, Params) MSDA_RUN_VALUE_FLOAT_(, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(, TS, MaskedParams)
+
 template <typename T, typename TV = T, typename PP = Params>
 int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, const void *loc, const void *attn,
             void *grad_value, void *grad_loc, void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,
@@ -1250,11 +1282,13 @@ template <typename T, int VEC, int G, int MODE, typename TV> inline int launch_d
         note_launch(1, 0);
         note_launch(2, 1);
         note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, G, p.D);
         const ProfileScope prof("msda_fwd_discrete_kernel", stream);
         hipLaunchKernelGGL((msda_fwd_discrete_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
     } else {
         note_launch(4, 2);
         note_launch(5, 0);
+        note_instance(11, VEC, G, p.D);
         const ProfileScope prof("msda_bwd_discrete_attn_kernel", stream);
         hipLaunchKernelGGL((msda_bwd_discrete_attn_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
     }
@@ -1444,7 +1478,14 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         return MSDA_ERR_MISALIGNED;
     }
     const bool want_value = grad_value != nullptr;
-    const size_t mat = fused_mat_bytes(B, H, Q, samples(d), sizeof(T));
+    // the derived points and weights are parked in float by the 16-bit operators too (ParkType), and their grad_value passes
+    // are the float pipeline on 16-bit rows — so those calls have the float limits, as the workspace queries say
+    using MT = ParkType<T>;
+    if (want_value && sizeof(MT) != sizeof(T) && common_limits_exceeded(d, (int64_t)sizeof(MT))) {
+        set_error("tensor too large for the fused backward's float32 grad_value passes");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    const size_t mat = fused_mat_bytes(B, H, Q, samples(d), sizeof(MT));
     if (want_value && (workspace == nullptr || !aligned_to(workspace, 256) || (uint64_t)workspace_bytes < mat)) {
         set_error("the fused backward needs a 256-byte aligned workspace of at least %zu bytes for grad_value", mat);
         return MSDA_ERR_BAD_ARG;
@@ -1469,7 +1510,7 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     if (want_value) {
         p.mat_loc = ws;
-        p.mat_attn = ws + ns * 2 * sizeof(T);
+        p.mat_attn = ws + ns * 2 * sizeof(MT);
     }
     const bool vec_ok = aligned_to(value, 16) && aligned_to(grad_out, 16) && p.v_row % 16 == 0;
     rc = dispatch_gather<T, 3, TV, TS>(p, vec_ok, stream);
@@ -1482,7 +1523,10 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         p.attn = p.mat_attn;
         p.ref = nullptr;
         p.ref_dim = 0;
-        rc = run_value<T, TV, TS>(value_pass_params(p), d, ws + mat, workspace_bytes - (int64_t)mat, stream);
+        if constexpr (sizeof(MT) != sizeof(T))
+            rc = run_value_float<TV, TS>(value_pass_params(p), d, ws + mat, workspace_bytes - (int64_t)mat, stream);
+        else
+            rc = run_value<T, TV, TS>(value_pass_params(p), d, ws + mat, workspace_bytes - (int64_t)mat, stream);
     }
     return rc;
 }

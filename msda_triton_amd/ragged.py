@@ -551,8 +551,10 @@ def hf_box_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padd
     _lib.check(rc, f"msda_bwd_fused_hfbox_{suf}")
     res = (g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None))
     if parked_points and ws is not None:
-        n = B * Q * H * S * 2 * reference_points.element_size()
-        res += (ws[:n].view(reference_points.dtype).view(B, Q, H, S, 2).clone(),)
+        # (the 16-bit operators park them in float32: msda_common.hpp, ParkType)
+        pdt = torch.float32 if reference_points.element_size() == 2 else reference_points.dtype
+        n = B * Q * H * S * 2 * pdt.itemsize
+        res += (ws[:n].view(pdt).view(B, Q, H, S, 2).clone(),)
     return res
 
 

@@ -111,6 +111,27 @@ CASES = {
 }
 BILINEAR = [n for n, c in CASES.items() if c[0] != "discrete"]
 DISCRETE = [n for n, c in CASES.items() if c[0] == "discrete"]
+
+# the head-dimension sweep (tests/head_dim_cases.py says which template instantiation each D reaches in each storage type):
+# the smallest shape that has two batch elements, two heads, two levels and a last workgroup that is not full, with
+# three points per level ("hd<D>_p3"), with per-level counts [2, 5] ("hd<D>_c25") and sampled discretely ("hd<D>_disc").
+# value and grad_out in {-1, 0, 1}: grad_loc sums D of them per sample, so D = 520 leaves no room for more (21 of 24 bits)
+HEAD_DIMS = (17, 33, 34, 65, 66, 68, 72, 130, 132, 136, 260, 264, 520)
+HEAD_DIM_BASE = (2, 11, 2, [(5, 4), (3, 2)])  # B, Q, H, levels
+HEAD_DIM_COUNTS = [2, 5]
+HEAD_DIM = []
+for _d in HEAD_DIMS + (128, 256):  # (128, 256: the one-wave-per-unit forward's D / VEC of 32 and 64 in float32)
+    _B, _Q, _H, _lv = HEAD_DIM_BASE
+    _kw = dict(loc_bits=5, attn_bits=2, vmax=1, gmax=1)
+    CASES[f"hd{_d}_p3"] = ("bilinear", (_B, _Q, _H, _d, _lv, 3), _kw, (F16, BF16))
+    CASES[f"hd{_d}_c25"] = ("bilinear", (_B, _Q, _H, _d, _lv, HEAD_DIM_COUNTS), _kw, (F16, BF16))
+    CASES[f"hd{_d}_disc"] = ("discrete", (_B, _Q, _H, _d, _lv, HEAD_DIM_COUNTS),
+                             dict(attn_bits=5, value_bits=3, grad_bits=3), (BF16,))
+    HEAD_DIM += [f"hd{_d}_p3", f"hd{_d}_c25", f"hd{_d}_disc"]
+# the LDS-served levels at G = 32 and G = 64: Q as in lds_q200 (the variant's workgroups hold 1024 / G units)
+for _d in (68, 132):
+    CASES[f"hd{_d}_lds"] = ("bilinear", (2, 200, 2, _d, [(5, 4), (3, 2)], 3), dict(loc_bits=5, attn_bits=2, vmax=1, gmax=1), (BF16,))
+    HEAD_DIM.append(f"hd{_d}_lds")
 SHAPE_MATRIX = ["d32_vec_g8", "d64_vec_g16", "d8_vec_g4", "d5_scalar", "d1", "one_query", "many_levels"]
 
 
@@ -279,6 +300,22 @@ def precondition(name, pm="border", ac=False):
 def checked_reference(name, pm="border", ac=False):
     precondition(name, pm, ac)
     return reference(name, pm, ac)
+
+
+def masked_reference(name, pm, ac, mask):
+    """The reference of a value-mask call (`mask` [B, I] bool, True = real pixel): the oracle on where(mask, value, 0),
+    grad_value zeroed in the padding rows.  Exact whenever the unmasked case is — the condition sums only shrink — and the
+    float32 oracle is again held to the float64 one."""
+    precondition(name, pm, ac)
+    c = get_case(name)
+    m = np.asarray(mask, dtype=bool)[:, :, None, None]
+    pre = dict(c, value=np.where(m, c["value"], 0.0))
+    ref = _oracle_all(_oracle(), pre, pm, ac, np.float64)
+    f32 = _oracle_all(_oracle(), pre, pm, ac, np.float32)
+    for k, r in ref.items():
+        assert np.array_equal(f32[k].astype(np.float64), r), f"{name} {pm} {ac} masked: float32 and float64 differ in {k}"
+    ref["grad_value"] = np.where(m, ref["grad_value"], 0.0)
+    return ref
 
 
 def expected(ref64, torch_dtype):

@@ -38,6 +38,10 @@ PLAIN_SHAPES = {k: SHAPE_MATRIX[k] for k in ("d32_vec_g8", "d5_scalar", "d8_vec_
                                              "d512_two_channel_chunks", "many_samples_chunked")}
 PLAIN_SHAPES.update({k: LDS_CASES[k][:6] for k in ("c2_like_f32", "no_level_fits_but_last", "coarse_first_order", "bf16_g4",
                                                     "fp16_d64", "f64")})
+# a partly filled lane group (17 of 32 lanes in float32; 16-bit: the scalar kernels' second chunk of 4 lanes) and a second
+# channel chunk of ONE lane (16-bit: five scalar chunks) — d512_two_channel_chunks fills its lanes exactly
+PLAIN_SHAPES["d68_partly_filled_group"] = (2, 11, 2, 68, [(5, 4), (3, 2)], 3)
+PLAIN_SHAPES["d260_one_lane_second_chunk"] = (2, 11, 2, 260, [(5, 4), (3, 2)], 3)
 # test_grad_value_without_workspace's pyramid: the sorted records' three homes (grad_loc, grad_attn, grad_value itself)
 PLAIN_SHAPES["three_homes"] = (1, 2500, 2, 32, [(40, 40), (20, 20)], 2)
 

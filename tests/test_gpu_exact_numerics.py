@@ -48,12 +48,15 @@ def _dev(a, dtype):
     return torch.from_numpy(np.array(a)).to(DEV, dtype)
 
 
-def run(c, pm, ac, vdt, cdt, layout="dense", discrete=False):
+def run(c, pm, ac, vdt, cdt, layout="dense", discrete=False, mask=None):
     """The case through the public API (autograd -> C ABI -> HIP) the way test_gpu_parity.run_hip goes; the results
-    on the CPU in the types they came back in."""
+    on the CPU in the types they came back in.  `mask` ([B, I] bool on the host, True = real pixel): the value-mask twins,
+    on a pyramid whose padding pixels hold NaN."""
     from msda_triton_amd import multiscale_deformable_attention
     from msda_triton_amd.functional import padded_value_rows
     v = _dev(c["value"], vdt)
+    if mask is not None:
+        v = torch.where(mask.to(DEV)[:, :, None, None], v, torch.full_like(v, float("nan")))
     if layout == "padded":
         vp = padded_value_rows(*v.shape, v.dtype, v.device, pad_bytes=128)
         vp.copy_(v)
@@ -71,6 +74,8 @@ def run(c, pm, ac, vdt, cdt, layout="dense", discrete=False):
     kw = dict(points_per_level=c["counts"]) if "counts" in c else {}
     if discrete:
         kw["sampling_mode"] = "discrete"
+    if mask is not None:
+        kw["value_mask"] = mask.to(DEV)
     out = multiscale_deformable_attention(v, torch.from_numpy(np.array(c["shapes"])).to(DEV), loc, attn, pm, ac, **kw)
     out.backward(_dev(c["grad_out"], cdt))
     torch.cuda.synchronize()

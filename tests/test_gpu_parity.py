@@ -135,7 +135,9 @@ SHAPE_MATRIX = {
     "d512_two_channel_chunks": (1, 3, 1, 512, [(3, 3)], 2),
     "d8_vec_g4": (2, 19, 3, 8, [(7, 9), (3, 4)], 5),
     "d5_scalar": (2, 13, 3, 5, [(6, 4), (3, 2), (2, 5)], 3),
+    # (despite its name: 36 % 4 == 0, so float32 takes nine 16-byte lanes, G = 16; 16-bit storage runs it scalar, 36 lanes)
     "d36_scalar_g64": (1, 7, 2, 36, [(5, 5), (2, 2)], 2),
+    "d33_scalar_g64": (1, 7, 2, 33, [(5, 5), (2, 2)], 2),  # the scalar kernels at G = 64 in every type, 33 of 64 lanes
     "d1": (1, 11, 2, 1, [(5, 6)], 3),
     "pairs_not_multiple_of_8": (3, 21, 5, 16, [(8, 8), (4, 4)], 2),
     "many_samples_chunked": (1, 6, 2, 8, [(6, 6), (3, 3), (2, 2), (1, 1), (4, 2), (2, 4), (5, 1), (1, 5)], 64),

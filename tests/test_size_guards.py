@@ -207,8 +207,8 @@ def _queries(lib, d, es, ves, flags=0):
 
 def _fused_points(d, es):
     """The fused queries' own part (include/msda_hip.h): the derived sampling points and attention weights, 3 elements
-    per sample, rounded up to 256 bytes."""
-    return -(-(d["B"] * d["Q"] * d["H"] * d["S"] * 3 * es) // 256) * 256
+    per sample, rounded up to 256 bytes — float32 elements for a 2-byte call: the 16-bit operators park them in float."""
+    return -(-(d["B"] * d["Q"] * d["H"] * d["S"] * 3 * max(es, 4)) // 256) * 256
 
 
 def _sorted_part(name, got, d, es):
