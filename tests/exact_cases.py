@@ -11,7 +11,12 @@ conversion: round to nearest even).
 
 `checked_reference(name, pm, ac)` is what the GPU tests compare against: it asserts the precondition (budget <= 24 for
 every tensor, float32 oracle == float64 oracle bitwise, no sample on an integer pixel coordinate) before it hands out
-the cached fp64 reference.  A case that fails it is a broken fixture: nothing is dropped at run time."""
+the cached fp64 reference.  A case that fails it is a broken fixture: nothing is dropped at run time.
+
+The pixel lattice itself — samples ON integer pixel coordinates, where grad_loc jumps and the padding modes switch
+corners and gradients off — has a kind of its own, "lattice" (`lattice_case`): there the precondition asks for the
+opposite, at least half of the samples with a coordinate on an integer, and tests/test_lattice_cases.py shows that three
+independent references agree on them bit for bit."""
 import functools
 import math
 import zlib
@@ -73,6 +78,58 @@ def flood_case(rng, B, Q, H, D, levels, P, coords, **kw):
     return c
 
 
+# ----------------------------------------------------------------------------------------- ON the pixel lattice
+# Full-lattice pyramids: power-of-two axes for align_corners=False, 2^k + 1 axes for align_corners=True (one-pixel axes
+# included), so that every pixel coordinate -2, -1.5, ..., n + 1.5 is a short dyadic sampling point.
+LATTICE_LEVELS = {False: [(4, 8), (2, 2), (1, 1), (1, 4)], True: [(5, 9), (3, 3), (2, 2), (1, 5)]}
+UNIVERSAL_LEVELS = [(7, 5), (3, 6), (1, 3)]
+# coordinates that sit on a kink whatever the size: 0 and 1 are px = 0 and px = n - 1 under align_corners, 0.5 is an integer
+# pixel coordinate of every odd-sized axis in either mode; (value, share) and the off-lattice dyadic neighbours of the rest
+UNIVERSAL_VALUES = ((0.0, 0.15), (0.5, 0.40), (1.0, 0.15), (-0.0, 0.15))
+UNIVERSAL_NEIGHBOURS = (-1 / 32, 1 / 32, 15 / 32, 17 / 32, 31 / 32, 33 / 32)
+LATTICE_LOC_BITS = {False: 4, True: 4, None: 5}  # pixel coordinates in halves on axes up to 8 (+ 1) pixels; the neighbours
+
+
+def lattice_axis(n, align):
+    """The sampling coordinates whose pixel coordinate on an axis of n pixels is -2, -1.5, ..., n + 1.5, exactly."""
+    px = np.arange(-4, 2 * n + 4) / 2.0
+    if align:
+        assert n == 1 or (n - 1) & (n - 2) == 0, n
+        return px / max(n - 1, 1)  # (one pixel: the coordinate is x * 0 whatever x)
+    assert n & (n - 1) == 0, n
+    return (px + 0.5) / n
+
+
+def lattice_case(rng, B, Q, H, D, levels, P, *, align, attn_bits=2, vmax=3, gmax=3, dtype=np.float64):
+    """`exact_case` whose sampling points sit ON the pixel lattice, where grad_loc is discontinuous and the padding modes
+    switch corners and gradients off.  align False / True: a full lattice for that align_corners — per level every (x, y)
+    pair of pixel coordinates -2, -1.5, ..., n + 1.5 at least once, dealt over batch, queries, heads and points.
+    align None: levels of any size, most coordinates from UNIVERSAL_VALUES, the rest their off-lattice neighbours."""
+    c = exact_case(rng, B, Q, H, D, levels, P, loc_bits=LATTICE_LOC_BITS[align], attn_bits=attn_bits, vmax=vmax, gmax=gmax, dtype=dtype)
+    counts = c.get("counts") or [P] * len(levels)
+    loc, s0 = c["loc"], 0
+    for lvl, ((h, w), p) in enumerate(zip(levels, counts)):
+        n = B * Q * H * p
+        if align is None:
+            vals = np.asarray([v for v, _ in UNIVERSAL_VALUES] + list(UNIVERSAL_NEIGHBOURS))
+            rest = 1.0 - sum(s for _, s in UNIVERSAL_VALUES)
+            prob = [s for _, s in UNIVERSAL_VALUES] + [rest / len(UNIVERSAL_NEIGHBOURS)] * len(UNIVERSAL_NEIGHBOURS)
+            pts = vals[rng.choice(len(vals), size=(n, 2), p=prob)]  # (by index: -0.0 keeps its sign)
+        else:
+            xs, ys = lattice_axis(w, align), lattice_axis(h, align)
+            pairs = np.stack(np.meshgrid(xs, ys, indexing="ij"), -1).reshape(-1, 2)
+            assert n >= len(pairs), f"level {lvl}: {len(pairs)} lattice pairs, {n} samples"
+            pts = np.resize(pairs, (n, 2))[rng.permutation(n)]
+        pts = pts.reshape(B, Q, H, p, 2).astype(dtype)
+        if "counts" in c:
+            loc[:, :, :, s0:s0 + p] = pts
+        else:
+            loc[:, :, :, lvl] = pts
+        s0 += p
+    c["align"] = align
+    return c
+
+
 # ----------------------------------------------------------------------------------------- the cases the GPU file uses
 PYRAMID = [(16, 16), (8, 8), (4, 4), (2, 2)]
 # name: (kind, (B, Q, H, D, levels, P), generator keywords, 16-bit storage types the GPU file runs the case in)
@@ -109,8 +166,33 @@ CASES = {
     "discrete_sorted": ("discrete", (1, 1200, 2, 32, [(32, 32), (16, 16), (8, 8)], [2, 4, 2]),
                         dict(attn_bits=5, value_bits=3, grad_bits=3, loc_bits=6), (BF16,)),
 }
-BILINEAR = [n for n, c in CASES.items() if c[0] != "discrete"]
+BILINEAR = [n for n, c in CASES.items() if c[0] in ("bilinear", "flood")]
 DISCRETE = [n for n, c in CASES.items() if c[0] == "discrete"]
+
+# the pixel lattice (kind "lattice", a precondition of its own below): B = 2, H = 2, Q = 384 — every (x, y) pair of level 0
+# (24 x 16 and 25 x 17 pixel coordinates) at least three times.  "f" / "t": the full lattice of align_corners False / True,
+# "u": the universal values; D = 32 (16-byte pieces) and D = 5 (the scalar path); "_c": per-level point counts
+_ALL16 = (F16, BF16)
+for _tag, _al in (("f", False), ("t", True)):
+    _lv = LATTICE_LEVELS[_al]
+    CASES[f"lat_{_tag}_d32"] = ("lattice", (2, 384, 2, 32, _lv, 1), dict(align=_al), _ALL16)
+    CASES[f"lat_{_tag}_d5"] = ("lattice", (2, 384, 2, 5, _lv, 1), dict(align=_al), _ALL16)
+    CASES[f"lat_{_tag}_d4"] = ("lattice", (2, 384, 2, 4, _lv, 1), dict(align=_al), _ALL16)
+    CASES[f"lat_{_tag}_c"] = ("lattice", (2, 384, 2, 32, _lv, [2, 5, 1, 3]), dict(align=_al), _ALL16)
+CASES["lat_u_d32"] = ("lattice", (2, 200, 2, 32, UNIVERSAL_LEVELS, 4), dict(align=None), _ALL16)
+CASES["lat_u_d5"] = ("lattice", (2, 200, 2, 5, UNIVERSAL_LEVELS, 4), dict(align=None), _ALL16)
+CASES["lat_u_c"] = ("lattice", (2, 200, 2, 32, UNIVERSAL_LEVELS, [2, 5, 3]), dict(align=None), _ALL16)
+LATTICE = [n for n, c in CASES.items() if c[0] == "lattice"]
+
+
+def lattice_modes(name):
+    """The modes a lattice case is ON the lattice in: its own align_corners for a full lattice, all four otherwise."""
+    align = CASES[name][2]["align"]
+    return [(pm, ac) for pm, ac in MODES if align is None or ac == align]
+
+
+LATTICE_RUNS = [(n, pm, ac) for n in LATTICE for pm, ac in lattice_modes(n)]
+LATTICE_MIN_SHARE = 0.5
 
 # the head-dimension sweep (tests/head_dim_cases.py says which template instantiation each D reaches in each storage type):
 # the smallest shape that has two batch elements, two heads, two levels and a last workgroup that is not full, with
@@ -140,7 +222,7 @@ def get_case(name):
     """The case's fp64 inputs (cached; treat as read-only)."""
     kind, dims, kw, _ = CASES[name]
     rng = np.random.default_rng(zlib.crc32(name.encode()))
-    c = flood_case(rng, *dims, **kw) if kind == "flood" else exact_case(rng, *dims, **kw)
+    c = {"flood": flood_case, "lattice": lattice_case}.get(kind, exact_case)(rng, *dims, **kw)
     for v in c.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
@@ -260,6 +342,31 @@ def pixel_coordinates(c, ac):
     return d["loc"] * (size - 1) if ac else d["loc"] * size - 0.5
 
 
+def real_samples(c, t):
+    """A per-sample array of the dense layout ([B, Q, H, L, P, ...]) without the padding `dense` added, samples flattened."""
+    t = _unpad(t, c["counts"]) if "counts" in c else t.reshape(t.shape[:3] + (-1,) + t.shape[5:])
+    return t.reshape((-1,) + t.shape[4:])
+
+
+def lattice_share(c, ac):
+    """The share of the case's samples with x or y ON an integer pixel coordinate."""
+    pix = pixel_coordinates(c, ac)
+    return float(real_samples(c, (pix == np.round(pix)).any(-1)).mean())
+
+
+POSITION_CLASSES = ("px < -1", "px = -1", "-1 < px < 0", "px = 0", "interior integer", "interior half", "px = n - 1",
+                    "n - 1 < px < n", "px = n", "px > n")
+
+
+def position_classes(px, n):
+    """Per coordinate, a bool [10, ...]: which of POSITION_CLASSES the pixel coordinate px belongs to on an axis of n
+    pixels (on one pixel, px = 0 is px = n - 1 as well, and -1 is never `n`: the classes are tested one by one)."""
+    whole = px == np.round(px)
+    inside = (px > 0) & (px < n - 1)
+    return np.stack([px < -1, px == -1, (px > -1) & (px < 0), px == 0, inside & whole, inside & ~whole, px == n - 1,
+                     (px > n - 1) & (px < n), px == n, px > n])
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name, pm="border", ac=False):
     """The fp64 reference of a case (cached): the CPU oracle, or test_discrete_sampling.ref_discrete."""
@@ -281,9 +388,24 @@ def precondition(name, pm="border", ac=False):
         frac = dict(out=b["attn"] + b["value"], grad_value=b["attn"] + b["grad"], grad_attn=b["value"] + b["grad"])
         bud = {k: frac[k] + _magnitude_bits(sums[k]) for k in frac}
         f32 = _discrete_all(c, _index_discrete, F32)  # evaluated in float32, independent of the package
+    elif CASES[name][0] == "lattice":
+        # The lattice has a kind of its own: its samples sit ON integer pixel coordinates by construction, where the
+        # oracle, grid_sample's autograd and the gather formulation agree bit for bit (tests/test_lattice_cases.py), so
+        # the rule below is replaced by its opposite — at least half of the samples have a coordinate on an integer, in
+        # the modes the case is made for — and the inputs must survive every 16-bit storage type the case is run in.
+        assert (pm, ac) in lattice_modes(name), f"{name}: not a lattice case under {pm} {ac}"
+        share = lattice_share(c, ac)
+        assert share >= LATTICE_MIN_SHARE, f"{name} {ac}: only {share:.1%} of the samples have a coordinate on an integer"
+        for k in ("value", "loc", "attn", "grad_out"):
+            t = torch.from_numpy(np.array(c[k]))
+            for dt in storage_types(name) + (F32,):
+                assert torch.equal(t.to(dt).double(), t), f"{name}: {k} does not survive {dt}"
+        bud = budget(c, pm, ac)
+        f32 = _oracle_all(_oracle(), c, pm, ac, np.float32)
     else:
         # no sample on an integer pixel coordinate, where grad_loc is discontinuous; an axis of ONE pixel under
         # align_corners is no exception to the rule but outside it: its coordinate is x * 0, zero in any arithmetic
+        # (the lattice itself is held by the cases of kind "lattice", which have the branch above to themselves)
         pix = pixel_coordinates(c, ac)
         wh = np.stack([c["shapes"][:, 1], c["shapes"][:, 0]], -1).reshape(1, 1, 1, -1, 1, 2)
         on_grid = (pix == np.round(pix)) & ~((wh == 1) & bool(ac))
@@ -340,15 +462,16 @@ def truncate(t32, dtype):
     return torch.where(over, toward_zero, r)
 
 
-def taps(c, pm, ac):
+def taps(c, pm, ac, pix=None, cell=None):
     """The oracle's bilinear taps in numpy fp64 for the (dense) case: (index [4][B, Q, H, L, P] into the pyramid, mask
-    [4], weight [4]), corners ordered 00, 01, 10, 11 (y, x)."""
+    [4], weight [4]), corners ordered 00, 01, 10, 11 (y, x).  pix / cell ([..., 2]): a mutant's pixel coordinates and its
+    cell's corner 00 in place of the oracle's `pixel_coordinates` and their floor."""
     d = dense(c)
-    pix = pixel_coordinates(c, ac)
+    pix = pixel_coordinates(c, ac) if pix is None else pix
     h = d["shapes"][:, 0].reshape(1, 1, 1, -1, 1)
     w = d["shapes"][:, 1].reshape(1, 1, 1, -1, 1)
     start = (np.cumsum(d["shapes"][:, 0] * d["shapes"][:, 1]) - d["shapes"][:, 0] * d["shapes"][:, 1]).reshape(1, 1, 1, -1, 1)
-    x0, y0 = np.floor(pix[..., 0]), np.floor(pix[..., 1])
+    x0, y0 = (np.floor(pix[..., 0]), np.floor(pix[..., 1])) if cell is None else (cell[..., 0], cell[..., 1])
     dx, dy = pix[..., 0] - x0, pix[..., 1] - y0
     idx, mask, wgt = [], [], []
     for oy, ox in ((0, 0), (0, 1), (1, 0), (1, 1)):
@@ -396,3 +519,57 @@ def smallest_corner_of_one_sample(c, pm, ac):
     flat = int(np.argmax(carried.reshape(-1)))
     assert carried.reshape(-1)[flat] > 0, "no sample whose smallest corner matters: the fixture has no teeth"
     return int(k.reshape(-1)[flat]), flat
+
+
+# ----------------------------------------------------------------------------------------- location gradients, and wrong ones
+# Emulated kernels that are right everywhere but ON the pixel lattice (tests/test_lattice_cases.py): the padding mode each
+# can show in, None = both
+LATTICE_MUTANTS = {
+    # the reference's Triton kernel: the clamped-corner formula with no gate, which is `px >= 0` where the oracle has `>`
+    "border_gradient_alive_at_zero": "border",
+    # the left-hand cell at integer coordinates: x0 = ceil(px) - 1, dx = 1
+    "left_cell_at_integers": None,
+    # "zeros" treating the cell x0 = -1 as outside when dx = 0: px = -1 loses its gradient (its weights ARE all zero)
+    "zeros_drops_minus_one": "zeros",
+    # "border" with the coordinate clamped FIRST and cell and fraction taken from the clamped coordinate, the cell kept
+    # inside the image (x0 <= n - 2), the gradient alive wherever the clamp left the coordinate alone: alive at 0 and n - 1
+    "border_gradient_after_clamp": "border",
+}
+
+
+def location_gradients(c, pm, ac, rule=None):
+    """grad_loc of the (dense) case in numpy fp64, [B, Q, H, L, P, 2], by the oracle's expression; rule: one of
+    LATTICE_MUTANTS in its place."""
+    assert rule is None or rule in LATTICE_MUTANTS, rule
+    d = dense(c)
+    pix = pixel_coordinates(c, ac)
+    n = np.stack([d["shapes"][:, 1], d["shapes"][:, 0]], -1).astype(np.float64).reshape(1, 1, 1, -1, 1, 2)
+    border = pm == "border"
+    alive = ((pix > 0) & (pix < n - 1)) if border else np.ones(pix.shape, bool)
+    at, cell = pix, None
+    if rule == "border_gradient_alive_at_zero" and border:
+        alive = np.ones(pix.shape, bool)
+    elif rule == "left_cell_at_integers":
+        cell = np.ceil(pix) - 1
+    elif rule == "zeros_drops_minus_one" and not border:
+        alive = np.broadcast_to((pix > -1).all(-1, keepdims=True), pix.shape)
+    elif rule == "border_gradient_after_clamp" and border:
+        at = np.clip(pix, 0, n - 1)
+        cell = np.maximum(np.minimum(np.floor(at), n - 2), 0)
+        alive = at == pix
+    idx, mask, _ = taps(c, pm, ac, at, cell)
+    x0, y0 = (np.floor(at[..., 0]), np.floor(at[..., 1])) if cell is None else (cell[..., 0], cell[..., 1])
+    dx, dy = (at[..., 0] - x0)[..., None], (at[..., 1] - y0)[..., None]
+    B, _, H, D = d["value"].shape
+    bi, hi = np.arange(B).reshape(B, 1, 1, 1, 1), np.arange(H).reshape(1, 1, H, 1, 1)
+    v00, v01, v10, v11 = (np.where(m[..., None], d["value"][bi, i, hi], 0.0) for i, m in zip(idx, mask))
+    g = d["grad_out"][:, :, :, None, None, :]
+    gx = (g * ((1 - dy) * (v01 - v00) + dy * (v11 - v10))).sum(-1)
+    gy = (g * ((1 - dx) * (v10 - v00) + dx * (v11 - v01))).sum(-1)
+    scale = n - 1 if ac else n
+    return np.where(alive, d["attn"][..., None] * scale * np.stack([gx, gy], -1), 0.0)
+
+
+def real_grad_loc(c, gl):
+    """`location_gradients`' dense result in the case's own layout (the oracle's grad_loc)."""
+    return _unpad(gl, c["counts"]) if "counts" in c else gl

@@ -239,21 +239,108 @@ def fused_inputs(family, storage, D, S, ref_dim):
     raise AssertionError(f"no kink-free draw for {family} {storage} {D} {S} {ref_dim}")
 
 
-def fused_reference(inp, pm, ac, oracle=None):
+def fused_reference(inp, pm, ac, oracle=None, real="float64"):
     """(out, grad_value, grad_proj, grad_ref) in float64 on the host — the prologue in PyTorch, the operator and its three
     gradients from the C oracle (per-level counts zero-padded to a dense layout, exact_cases.dense), the prologue's chain
-    rule by autograd; with a value mask the oracle runs on where(mask, value, 0) and grad_value's padding rows are zero."""
+    rule by autograd; with a value mask the oracle runs on where(mask, value, 0) and grad_value's padding rows are zero.
+    real="float32": the same composition in float32 throughout (what the reference alone loses in that type)."""
     import numpy as np
     import torch
-    v64 = inp["value"].double()
+    tdt = getattr(torch, real)
+    v64 = inp["value"].to(tdt)
     if inp["mask"] is not None:
         v64 = torch.where(inp["mask"][:, :, None, None], v64, torch.zeros_like(v64))
-    p64, r64 = (inp[k].double().detach().clone().requires_grad_(True) for k in ("proj", "ref"))  # (never the cached tensors)
+    p64, r64 = (inp[k].to(tdt).detach().clone().requires_grad_(True) for k in ("proj", "ref"))  # (never the cached tensors)
     pts, att = fused_sampling_inputs(inp["family"], p64, inp["shapes"], r64, inp["counts"])
-    r = ec._oracle_all(oracle or ec._oracle(), _as_case(inp, pts, att, v64), pm, ac, np.float64)
+    r = ec._oracle_all(oracle or ec._oracle(), _as_case(inp, pts, att, v64), pm, ac, getattr(np, real))
     gl, ga = (torch.from_numpy(np.ascontiguousarray(r[k])) for k in ("grad_loc", "grad_attn"))
     gp, gr = torch.autograd.grad([pts, att], [p64, r64], [gl, ga])
     gv = torch.from_numpy(r["grad_value"])
     if inp["mask"] is not None:
         gv = torch.where(inp["mask"][:, :, None, None], gv, torch.zeros_like(gv))
     return torch.from_numpy(r["out"]), gv, gp, gr
+
+
+# ----------------------------------------------------------------------------------------- the fused families ON the lattice
+# Points the prologues form EXACTLY in float32, in either order of operations (offset / w or offset * (1 / w)): the offset
+# is zero, or every factor it meets is a power of two — the level sizes of exact_cases.LATTICE_LEVELS[False], point counts
+# of 1, 2, 4, box sizes of 1/4, 1/2, 1 — and reference points and offsets are short dyadic numbers.  The kernels, the
+# float32 composition and the float64 reference then sample the SAME points, on the same side of every kink, and the
+# location gradients can be compared with no sample masked out.  align_corners with 2-d reference points divides the
+# offsets by 2^k + 1: those draws have zero offsets (the zero-initialised module) and put the reference points themselves
+# on the lattice.
+LATTICE_B, LATTICE_Q, LATTICE_H = 2, 384, 2
+LATTICE_P, LATTICE_COUNTS = 2, [2, 4, 1, 1]
+LATTICE_FUSED_DIMS = {"f32": (32, 5), "f64": (32, 5), "bf16": (32,), "fp16": (32,), "sbf16": (32,), "sf16": (32,),
+                      "vbf16": (32,), "vf16": (32,)}
+LATTICE_FUSED_MODES = ec.MODES
+# ... and the universal values on arbitrary sizes (exact_cases.UNIVERSAL_LEVELS): with 2-d reference points the
+# zero-initialised module on reference points out of a clamp(0, 1) — 0, 0.5, 1 and -0 —, with boxes (whose rule knows no
+# level size) offsets that put every sample on one of those values or a dyadic neighbour; one 16-byte D per arithmetic
+UNIVERSAL_COUNTS = [2, 4, 1]
+UNIVERSAL_FUSED_DIMS = {"f32": (32,), "f64": (32,), "sbf16": (32,), "bf16": (32,)}
+
+
+def fused_lattice_case_list():
+    """(family, storage, D, ref_dim, universal)"""
+    return [(f, s, d, rd, u) for u, table in ((False, LATTICE_FUSED_DIMS), (True, UNIVERSAL_FUSED_DIMS)) for f in FUSED_FAMILIES
+            for s, dims in table.items() for d in dims for rd in fused_ref_dims(f)]
+
+
+@functools.lru_cache(maxsize=None)
+def fused_lattice_inputs(family, storage, D, ref_dim, ac, universal=False):
+    """The inputs of `_fused_draw` (host tensors in their storage types; cached, read-only) with offsets and reference
+    points such that the family's prologue lands on the lattice targets of `exact_cases.lattice_case` — the full lattice
+    of align_corners = ac, or the universal values on UNIVERSAL_LEVELS — plus "points" (the float64 sampling points, the
+    family's layout) and "factor" (what the prologue multiplies the offsets by, float64)."""
+    import zlib
+    import numpy as np
+    import torch
+    B, Q, H = LATTICE_B, LATTICE_Q, LATTICE_H
+    levels = ec.UNIVERSAL_LEVELS if universal else ec.LATTICE_LEVELS[ac]
+    align = None if universal else ac
+    L = len(levels)
+    ragged = family in ("ragged", "hfbox")
+    perlevel = family in ("levelref", "levelref_masked")
+    counts = (UNIVERSAL_COUNTS if universal else LATTICE_COUNTS) if ragged else None
+    per = counts if ragged else [LATTICE_P] * L
+    S = sum(per)
+    seed = zlib.crc32(f"lattice {family} {ref_dim} {ac} {universal}".encode()) % 100000  # (one draw of points for every storage and D)
+    rng = np.random.default_rng(seed)
+    vdt, pdt, rdt = (getattr(torch, n) for n in FUSED_STORAGE[storage])
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    big = torch.float64 if storage == "f64" else torch.float32
+    value = torch.randn(B, sum(h * w for h, w in levels), H, D, generator=g, dtype=big).to(vdt)
+    logits = (torch.randn((B, Q, H, S), generator=g, dtype=big) * 1.5).to(pdt)
+    gout = torch.rand(B, Q, H, D, generator=g, dtype=big).to(pdt)
+    mask = (torch.rand(B, value.shape[1], generator=g) < 0.5) if family == "levelref_masked" else None
+    # targets [B, Q, H, S, 2], level-major, and each sample's level
+    target = ec.lattice_case(rng, B, Q, H, 1, levels, per, align=align)["loc"]
+    level = np.repeat(np.arange(L), per)
+    hw = np.asarray(levels, dtype=np.float64)[level]              # [S, 2] (h, w)
+    pl = np.asarray(per, dtype=np.float64)[level][:, None]         # [S, 1] the count of the sample's level
+    zero_offsets = (universal or bool(ac)) and ref_dim == 2        # offsets divided by 2^k + 1 (or any) pixels: none
+    # reference points [B, Q, (L,) ref_dim]
+    rshape = (B, Q, L) if perlevel else (B, Q)
+    if zero_offsets:  # the reference points ARE the sampling points: a level's own lattice (per-level), level 0's otherwise
+        own = ec.lattice_case(rng, B, Q, 1, 1, levels, 1, align=align)["loc"][:, :, 0, :, 0]  # [B, Q, L, 2]: every pair, per level
+        xy = own if perlevel else own[:, :, 0]
+    else:
+        xy = rng.integers(0, 17, size=rshape + (2,)) / 16.0
+    ref = xy if ref_dim == 2 else np.concatenate([xy, rng.choice([0.25, 0.5, 1.0], size=rshape + (2,))], -1)
+    rs = ref[:, :, None, level] if perlevel else ref[:, :, None, None]   # -> [B, Q, 1, S, ref_dim] per sample
+    if ref_dim == 2:
+        # (the reference module and its per-level-count form divide (x, y) by the stored (h, w); transformers by (w, h))
+        factor = 1.0 / (hw[:, ::-1] if perlevel else hw) * np.ones((B, Q, 1, S, 2))
+    else:
+        factor = rs[..., 2:] / (2.0 * pl)
+    offsets = np.zeros((B, Q, H, S, 2)) if zero_offsets else (target - rs[..., :2]) / factor
+    points = rs[..., :2] + offsets * factor
+    assert zero_offsets or np.array_equal(points, target)
+    proj = torch.cat([torch.from_numpy(offsets).to(pdt), logits[..., None]], -1)
+    if family == "hfbox":
+        ref = ref[:, :, None]
+    if not ragged:
+        proj, points, factor = (t.reshape((B, Q, -1, L, LATTICE_P) + tuple(t.shape[4:])) for t in (proj, points, factor))
+    return dict(value=value, shapes=torch.tensor(levels), proj=proj, ref=torch.from_numpy(ref).to(rdt), gout=gout, counts=counts,
+                mask=mask, family=family, seed=seed, points=points, factor=factor, zero_offsets=zero_offsets)

@@ -157,6 +157,33 @@ def _worst(got, want, atol, rtol):
     return float(((got - want).abs() / (atol + rtol * want.abs())).max())
 
 
+def assert_16_bit_close(storage, got, w32, sdt, what):
+    """A 16-bit storage variant's (out, grad_value, grad_proj, grad_ref) against the float32 kernels' on the same rounded
+    inputs, with the bounds of tests/test_gpu_fused_storage.py."""
+    out, gv, gp, gr = got
+    if storage.startswith("v"):  # 16-bit value rows only: float32 numbers everywhere but grad_value
+        torch.testing.assert_close(out, w32[0], atol=2e-5, rtol=1e-4)
+        close16(gv, w32[1], sdt, what + " grad_value", scale_tol=3.0)
+        torch.testing.assert_close(gp, w32[2], atol=1e-3, rtol=1e-3)
+        torch.testing.assert_close(gr, w32[3], atol=1e-3, rtol=1e-3)
+    else:
+        close(out, w32[0], sdt, what + " out")
+        close(gp, w32[2], sdt, what + " grad_proj")
+        if storage.startswith("s"):
+            close(gv, w32[1], sdt, what + " grad_value", scale_tol=3.0)
+            assert gr.dtype == torch.float32
+            torch.testing.assert_close(gr, w32[3], rtol=2e-4, atol=2e-4 * float(w32[3].abs().max()))
+        else:
+            # One 16-bit type for every tensor.  grad_value as the other 16-bit variants': the derived points are
+            # parked in float32 for the grad_value passes (ParkType), which are the float pipeline on 16-bit rows.
+            close(gv, w32[1], sdt, what + " grad_value", scale_tol=3.0)
+            # grad_ref: the per-head partials are rounded to 16 bits and summed, so an element carries half an ulp
+            # of EVERY partial, not of itself — norm-wise, with the bound tests/test_gpu_fused_storage.py holds a
+            # 16-bit call's reference-point gradients to.
+            rel = float((gr.double() - w32[3].double()).norm() / w32[3].double().norm().clamp_min(1e-30))
+            assert rel < 2e-2, (what, "grad_ref", rel)
+
+
 @pytest.mark.parametrize("family,storage,D,S", hd.fused_case_list(), ids=FUSED_IDS)
 def test_fused_families_in_the_expected_instantiation(family, storage, D, S):
     """float64 and float32 against the host fp64 module core (1e-8; FWD_TOL / BWD_TOL of tests/test_gpu_parity.py, offsets
@@ -192,25 +219,4 @@ def test_fused_families_in_the_expected_instantiation(family, storage, D, S):
             # 16-bit storage: the float32 kernels on the same rounded inputs
             w32, names32, _ = fused_run(inp, pm, ac, cast=torch.float32)
             assert names32 == hd.FUSED_NAMES[family], (what, names32)
-            out, gv, gp, gr = got
-            if storage.startswith("v"):  # 16-bit value rows only: float32 numbers everywhere but grad_value
-                torch.testing.assert_close(out, w32[0], atol=2e-5, rtol=1e-4)
-                close16(gv, w32[1], sdt, what + " grad_value", scale_tol=3.0)
-                torch.testing.assert_close(gp, w32[2], atol=1e-3, rtol=1e-3)
-                torch.testing.assert_close(gr, w32[3], atol=1e-3, rtol=1e-3)
-            else:
-                close(out, w32[0], sdt, what + " out")
-                close(gp, w32[2], sdt, what + " grad_proj")
-                if storage.startswith("s"):
-                    close(gv, w32[1], sdt, what + " grad_value", scale_tol=3.0)
-                    assert gr.dtype == torch.float32
-                    torch.testing.assert_close(gr, w32[3], rtol=2e-4, atol=2e-4 * float(w32[3].abs().max()))
-                else:
-                    # One 16-bit type for every tensor.  grad_value as the other 16-bit variants': the derived points are
-                    # parked in float32 for the grad_value passes (ParkType), which are the float pipeline on 16-bit rows.
-                    close(gv, w32[1], sdt, what + " grad_value", scale_tol=3.0)
-                    # grad_ref: the per-head partials are rounded to 16 bits and summed, so an element carries half an ulp
-                    # of EVERY partial, not of itself — norm-wise, with the bound tests/test_gpu_fused_storage.py holds a
-                    # 16-bit call's reference-point gradients to.
-                    rel = float((gr.double() - w32[3].double()).norm() / w32[3].double().norm().clamp_min(1e-30))
-                    assert rel < 2e-2, (what, "grad_ref", rel)
+            assert_16_bit_close(storage, got, w32, sdt, what)
