@@ -13,33 +13,16 @@
 #include <string>
 
 #include "../../include/msda_hip.h"
+#include "msda_options.hpp"
 
 namespace msda {
 
-static std::atomic<int> g_xcd_map{1};
-static std::atomic<int> g_value_path{0};
-static std::atomic<int> g_wg_target{1 << 30};
-static std::atomic<int> g_cell_slices{0};
-static std::atomic<int> g_debug{0};
-static std::atomic<int> g_small_ns{0};
-static std::atomic<int> g_q_round{0};
-static std::atomic<int> g_level_cells{0};
-static std::atomic<int> g_overlap{-1};
-static std::atomic<int> g_gather_win{0};
-static std::atomic<int> g_place_path{0};
-static std::atomic<int> g_profile{0};
-static std::atomic<int> g_records_in_grads{1};
-static std::atomic<int> g_strict{0};
-static std::atomic<int> g_lds_levels{1};
-static std::atomic<int> g_lds_budget{-1};
-static std::atomic<int> g_unit_fwd{1};
-static std::atomic<int> g_lds_over{1};
-static std::atomic<int> g_lds_planes{0};
-static std::atomic<int> g_linear_slots{320};
-static std::atomic<int> g_touch{1};
-static std::atomic<int> g_unit_waves{1};
-static std::atomic<int> g_ws_passes{1};
-static std::atomic<int> g_lds_stagger{0};  // (measured 0 / 4 / 12 / 24 at c2 @ 10k: 0 is fastest — the work counter desynchronises the waves by itself)
+// the options: one atomic and one getter per line of the list (msda_options.hpp)
+#define MSDA_OPTION_SLOT(key, def, lo, hi, dev) \
+    static std::atomic<int> g_##key{def};       \
+    int option_##key() { return g_##key.load(std::memory_order_relaxed); }
+MSDA_OPTION_LIST(MSDA_OPTION_SLOT)
+#undef MSDA_OPTION_SLOT
 
 // One side stream + two events per (host thread, device), created on first use and kept for the life of the thread.
 // Per THREAD, because the fork (record on the user's stream, wait on the side stream) and the join are two calls
@@ -102,30 +85,6 @@ int side_stream_join(hipStream_t user)
 }
 static thread_local char g_err[256] = "";
 
-int option_xcd_map() { return g_xcd_map.load(std::memory_order_relaxed); }
-int option_value_path() { return g_value_path.load(std::memory_order_relaxed); }
-int option_wg_target() { return g_wg_target.load(std::memory_order_relaxed); }
-int option_cell_slices() { return g_cell_slices.load(std::memory_order_relaxed); }
-int option_debug() { return g_debug.load(std::memory_order_relaxed); }
-int option_small_ns() { return g_small_ns.load(std::memory_order_relaxed); }
-int option_q_round() { return g_q_round.load(std::memory_order_relaxed); }
-int option_level_cells() { return g_level_cells.load(std::memory_order_relaxed); }  // process-wide promise (0: unknown)
-int option_overlap() { return g_overlap.load(std::memory_order_relaxed); }
-int option_gather_win() { return g_gather_win.load(std::memory_order_relaxed); }
-int option_place_path() { return g_place_path.load(std::memory_order_relaxed); }
-int option_profile() { return g_profile.load(std::memory_order_relaxed); }
-int option_records_in_grads() { return g_records_in_grads.load(std::memory_order_relaxed); }
-int option_strict() { return g_strict.load(std::memory_order_relaxed); }
-int option_lds_levels() { return g_lds_levels.load(std::memory_order_relaxed); }
-int option_lds_stagger() { return g_lds_stagger.load(std::memory_order_relaxed); }
-int option_lds_over() { return g_lds_over.load(std::memory_order_relaxed); }
-int option_lds_planes() { return g_lds_planes.load(std::memory_order_relaxed); }
-int option_linear_slots() { return g_linear_slots.load(std::memory_order_relaxed); }
-int option_unit_fwd() { return g_unit_fwd.load(std::memory_order_relaxed); }
-int option_touch() { return g_touch.load(std::memory_order_relaxed); }
-int option_unit_waves() { return g_unit_waves.load(std::memory_order_relaxed); }
-int option_ws_passes() { return g_ws_passes.load(std::memory_order_relaxed); }
-int option_lds_budget() { return g_lds_budget.load(std::memory_order_relaxed); }  // dev knob: cap on the level bytes (-1: none)
 // CUs of the current device, asked once per device (the LDS-level gather variants size their grid by it)
 int device_cu_count()
 {
@@ -212,50 +171,6 @@ void set_error(const char *fmt, ...)
 
 extern "C" int msda_abi_version(void) { return MSDA_ABI_VERSION; }
 
-// the layout lives in a device header (msda_value_sorted.hpp); msda_f32.hip exposes its size formula
-extern "C" int64_t msda_bwd_workspace_bytes_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int, int64_t, int, int64_t);
-
-extern "C" int64_t msda_bwd_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
-                                            int64_t P, int elem_size, int value_elem_size, int64_t max_level_cells,
-                                            int flags)
-{
-    if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || L < 0 || P < 0) return 0;
-    return msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, P, elem_size, (flags & MSDA_WS_RECORDS_IN_GRADS) ? 1 : 0,
-                                         value_elem_size > 0 ? value_elem_size : elem_size, max_level_cells,
-                                         ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), 0);
-}
-
-extern "C" int msda_fused_dims_refused_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t);
-
-extern "C" int64_t msda_bwd_fused_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
-                                                  int64_t P, int elem_size, int value_elem_size, int64_t max_level_cells,
-                                                  int flags)
-{
-    if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || L < 0 || P < 0 || elem_size <= 0) return 0;
-    // the derived sampling points + attention weights (3 elements per sample, rounded up to 256 bytes), then
-    // the sorted pipeline's own workspace (msda_launch.hpp: fused_mat_bytes)
-    (void)value_elem_size;
-    if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, P, elem_size, 0)) return 0;  // (a call of this size is refused)
-    // the 16-bit operators park the derived points in float and run the float grad_value passes (msda_common.hpp, ParkType)
-    if (elem_size == 2) elem_size = 4;
-    if (msda_fused_dims_refused_impl(B, I, H, D, Q, L, P, elem_size, 0)) return 0;
-    const int64_t mat = (B * Q * H * L * P * 3 * (int64_t)elem_size + 255) / 256 * 256;
-    return mat + msda_bwd_workspace_bytes_impl(B, I, H, D, Q, L, P, elem_size, 0, 0, max_level_cells,
-                                               ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) : msda::option_ws_passes(), 0);
-}
-
-extern "C" int msda_bwd_supported_impl(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int64_t);
-
-extern "C" int msda_bwd_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int elem_size)
-{
-    if (B < 0 || I < 0 || H < 0 || D < 0 || Q < 0 || L < 0 || P < 0 || elem_size <= 0) return 0;
-    return msda_bwd_supported_impl(B, I, H, D, Q, L, P, elem_size, 0);
-}
-
-extern "C" int64_t msda_fused_lp_limit_impl(int64_t, int);
-
-extern "C" int64_t msda_fused_lp_limit(int64_t D, int elem_size) { return msda_fused_lp_limit_impl(D, elem_size); }
-
 extern "C" const char *msda_last_error(void) { return msda::g_err; }
 
 extern "C" int msda_last_launch_info(const char *key)
@@ -312,39 +227,18 @@ extern "C" int msda_profile_read(char *buf, int cap)
     return n;
 }
 
-// One table for set and get.  dev: an experiment knob, reachable only in builds with -DMSDA_DEV (include/msda_hip.h).
+// One table for set and get, made from the option list (msda_options.hpp).  dev: an experiment knob, reachable only in builds with -DMSDA_DEV (include/msda_hip.h).
 namespace msda {
 struct OptionEntry {
     const char *key;
     std::atomic<int> *slot;
-    int lo, hi;  // accepted range (values outside are clamped to `fallback` when clamp, rejected otherwise)
+    int lo, hi;  // accepted range (values outside are rejected)
     bool dev;
 };
 static const OptionEntry kOptions[] = {
-    {"xcd_map", &g_xcd_map, 0, 2, false},
-    {"value_path", &g_value_path, 0, 3, false},
-    {"level_cells", &g_level_cells, 0, 0x7fffffff, false},
-    {"q_round", &g_q_round, 0, 0x7fffffff, false},
-    {"small_ns", &g_small_ns, 0, 16, false},
-    {"overlap", &g_overlap, -1, 1, false},
-    {"place_path", &g_place_path, 0, 3, false},
-    {"strict", &g_strict, 0, 1, false},
-    {"records_in_grads", &g_records_in_grads, 0, 1, false},
-    {"profile", &g_profile, 0, 1, false},
-    {"lds_levels", &g_lds_levels, 0, 2, false},
-    {"unit_fwd", &g_unit_fwd, 0, 2, false},
-    {"debug", &g_debug, (int)0x80000000, 0x7fffffff, true},
-    {"gather_win", &g_gather_win, 0, 4096, true},
-    {"cell_slices", &g_cell_slices, 0, 64, true},
-    {"wg_target", &g_wg_target, 1, 0x7fffffff, true},
-    {"lds_budget", &g_lds_budget, -1, 0x7fffffff, true},
-    {"lds_stagger", &g_lds_stagger, 0, 4096, true},
-    {"lds_over", &g_lds_over, 1, 8, true},
-    {"lds_planes", &g_lds_planes, 0, 2, false},
-    {"linear_slots", &g_linear_slots, 1, 1 << 30, false},
-    {"touch", &g_touch, 0, 2, false},
-    {"unit_waves", &g_unit_waves, 1, 2, false},
-    {"ws_passes", &g_ws_passes, 1, 128, false},
+#define MSDA_OPTION_ROW(key, def, lo, hi, dev) {#key, &g_##key, lo, hi, dev},
+    MSDA_OPTION_LIST(MSDA_OPTION_ROW)
+#undef MSDA_OPTION_ROW
 };
 static const OptionEntry *find_option(const char *key)
 {

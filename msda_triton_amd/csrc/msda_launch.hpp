@@ -5,26 +5,17 @@
 #include <stdio.h>
 
 #include <atomic>
+#include <initializer_list>
 
 #include "msda_value_sorted.hpp"
 #include "msda_value_place.hpp"
 #include "msda_value_small.hpp"
 #include "msda_discrete.hpp"
+#include "msda_options.hpp"
 
 namespace msda {
 
-// ---- process-wide options and per-thread error text (defined in msda_api.hip) ----
-int option_xcd_map();
-int option_value_path();  // 0: auto (single-launch LDS kernel when a plane-level fits, else sorted gather), 2: sorted, 3: single-launch
-int option_wg_target();     // gather workgroups to aim for when choosing query chunks per workgroup
-int option_small_ns();      // workgroups per (plane, level) of the single-launch grad_value kernel (0: automatic)
-int option_level_cells();   // caller's promise: no level has more than this many bilinear cells (0: unknown)
-int option_q_round();       // queries per round of the sorted grad_value path (0: automatic)
-int option_debug();         // dev-only ablation mask
-int option_place_path();    // 0: level-major place pass with LDS-staged runs (msda_value_place.hpp); 1: the plane-major place pass
-int option_records_in_grads();  // 1 (default): the sorted records may live in the caller's grad_loc / grad_attn buffers
-int option_strict();        // 1: refuse a backward whose grad_value would not be bitwise reproducible
-int option_overlap();       // 1: grad_loc/grad_attn and grad_value run concurrently on a forked side stream; 0: never; -1: automatic
+// ---- per-thread error text, side stream and measurement hooks (defined in msda_api.hip; the options: msda_options.hpp) ----
 // fork-join helpers around a lazily created per-device side stream (msda_api.hip)
 hipStream_t side_stream_fork(hipStream_t user);   // side stream that waits for everything queued on `user`
 int side_stream_join(hipStream_t user);            // `user` waits for everything queued on the side stream
@@ -96,8 +87,10 @@ inline bool common_limits_exceeded(const Dims &d, int64_t es)
 // ... and of the fused entry points' projection [B, Q, H, S, 3]
 inline bool fused_limit_exceeded(const Dims &d) { return d.Q * d.H * samples(d) * 3 >= ((int64_t)1 << 31); }
 
-template <typename T>
-inline int check_common(const Dims &d, int padding_mode, const void *const *ptrs, int nptrs)
+// ---- the shared steps of an entry point, part 1 (part 2: behind fill_params).  Every run_* applies them in its OWN order,
+//      and that order is contract (which of two faults a call reports): see the run_* bodies and DESIGN.md 1. ----
+// dimensions, padding mode, level count, size limits (`es`: size of the arithmetic / sampling type)
+inline int check_common(const Dims &d, int64_t es, int padding_mode)
 {
     if (d.B < 0 || d.I < 0 || d.H < 0 || d.D < 0 || d.Q < 0 || d.L < 0 || d.P < 0) {
         set_error("negative dimension");
@@ -111,19 +104,53 @@ inline int check_common(const Dims &d, int padding_mode, const void *const *ptrs
         set_error("L=%lld exceeds MSDA_MAX_LEVELS=%d", (long long)d.L, MSDA_MAX_LEVELS);
         return MSDA_ERR_TOO_MANY_LEVELS;
     }
-    if (common_limits_exceeded(d, (int64_t)sizeof(T))) {
-        set_error("tensor too large for 32-bit plane offsets (I*H*D*sizeof = %lld bytes)",
-                  (long long)(d.I * d.H * d.D * (int64_t)sizeof(T)));
+    if (common_limits_exceeded(d, es)) {
+        set_error("tensor too large for 32-bit plane offsets (I*H*D*sizeof = %lld bytes)", (long long)(d.I * d.H * d.D * es));
         return MSDA_ERR_TOO_LARGE;
-    }
-    for (int i = 0; i < nptrs; ++i) {
-        if (ptrs[i] == nullptr) {
-            set_error("null buffer (argument %d)", i);
-            return MSDA_ERR_BAD_ARG;
-        }
     }
     return 0;
 }
+// buffers a call cannot do without (the index in the message counts within the list)
+inline int require_buffers(std::initializer_list<const void *> ptrs)
+{
+    int i = 0;
+    for (const void *ptr : ptrs) {
+        if (ptr == nullptr) {
+            set_error("null buffer (argument %d)", i);
+            return MSDA_ERR_BAD_ARG;
+        }
+        ++i;
+    }
+    return 0;
+}
+// every buffer on a multiple of its element size (a null pointer, an output not asked for, passes)
+struct AlignedTo {
+    const void *ptr;
+    size_t bytes;
+};
+inline int check_aligned(std::initializer_list<AlignedTo> bufs)
+{
+    for (const AlignedTo &b : bufs) {
+        if (aligned_to(b.ptr, b.bytes)) continue;
+        set_error("misaligned buffer");
+        return MSDA_ERR_MISALIGNED;
+    }
+    return 0;
+}
+// the empty-problem shortcut: zeros into every output that was asked for and has bytes
+struct ZeroFill {
+    void *ptr;
+    size_t bytes;
+};
+inline int zero_outputs(std::initializer_list<ZeroFill> outs, hipStream_t stream)
+{
+    hipError_t e = hipSuccess;
+    for (const ZeroFill &o : outs)
+        if (e == hipSuccess && o.ptr != nullptr && o.bytes != 0) e = hipMemsetAsync(o.ptr, 0, o.bytes, stream);
+    return (int)e;
+}
+// no sample touches anything: all gradients are zero
+inline bool nothing_sampled(const Dims &d) { return d.B * d.Q * d.H * d.D == 0 || samples(d) == 0 || d.I == 0; }
 
 // Grid for a (plane, slot) decomposition.  Prefers the 3-D shapes whose linear dispatch order equals
 // decode_block's 1-D formula, so the kernel needs no integer division; falls back to 1-D when a
@@ -135,7 +162,6 @@ inline int check_common(const Dims &d, int padding_mode, const void *const *ptrs
 // instead of one XCD a lot.  c5 (3 125 workgroups per plane): forward 2.92 -> 2.45 ms, sample gradients 3.44 -> 2.89 ms; its
 // shards of 12 500 / 25 000 / 50 000 queries per plane (391 ... 1 563 workgroups): step -8 % each.  The threshold (option
 // "linear_slots", default 320) is empirical: c3's sample-gradient kernel (279 workgroups per plane) loses 2 % in linear order.
-int option_linear_slots();
 inline bool plane_grid(Params &p, int npairs, int64_t slots, dim3 &grid)
 {
     if (slots < 1) slots = 1;
@@ -176,7 +202,6 @@ inline bool plane_grid(Params &p, int npairs, int64_t slots, dim3 &grid)
 // touch_settle's rule below).
 // (The one-wave-per-unit kernel does not touch: its waves all start together, the touches only queue in front of the rows
 // they want — Q = 100 10.7 -> 15.0 us, 300 15.7 -> 17.5.)
-int option_touch();
 inline int touch_plan(const Dims &d)
 {
     const int o = option_touch();
@@ -188,7 +213,7 @@ inline int touch_plan(const Dims &d)
 // wave instruction), which is free while everything waits for memory and is not when the rows are already in L2: c4 (64
 // planes x 4 workgroups, 1 360 rows each) 23.7 -> 26.5 us warm with the touches; c2 @ 1k and c1 (680 rows each) unchanged
 // within +-0.5 us (rocprofv3, options alternated on one box).
-int device_cu_count();
+int device_cu_count();  // CUs of the current device (cached; msda_api.hip)
 inline void touch_settle(Params &p, const dim3 &grid, long long slots)
 {
     if (p.touch == 1 && ((long long)grid.x * grid.y * grid.z > device_cu_count() || (p.I + slots - 1) / slots > 768)) p.touch = 0;
@@ -229,17 +254,9 @@ inline void plan_gather(int NU, int LP, size_t acc_bytes, int &sc, size_t &lds, 
 // MODE 0: forward, 1: grad_loc/grad_attn, 2: fused forward, 3: fused backward (sample half)
 // ---- the gather kernels with the coarsest levels in LDS (msda_kernels.hpp, LDSL): ONE 1024-thread workgroup per CU,
 // every (b, h) plane cut into as many runs of query chunks as fill the chip once ----
-int option_lds_levels();  // 0: never, 1: where lds_levels_plan says so, 2: wherever the kernels exist
-int option_unit_fwd();  // 1 (default): small problems take the one-wave-per-unit forward; 2: every problem it can; 0: never
 // (b, q, h) units up to which the one-wave-per-unit forward is taken: cold-cache forward at B = 4, H = 8 (round 5, in-process
 // A/B): Q = 10 10.3 -> 7.5 us, 100 12.8 -> 9.4, 300 ~15 -> 13.2; from Q ~ 500 the general kernel is faster (900: 18-23 against 23.7)
 constexpr long long kUnitFwdMaxUnits = 12288;
-int option_unit_waves();  // 1 (default): one unit per wave; 2: two wherever the variant exists
-int option_lds_budget();  // dev knob: cap on the bytes of LDS-resident levels (-1: none)
-int option_lds_planes();   // 0 (default): two planes per LDS-level workgroup where the plan says so; 1: never; 2: whenever H is even
-int option_lds_over();     // workgroups per CU the LDS-served-level launches are cut into (1: one round)
-int option_lds_stagger();  // dev knob: start-up stagger of an LDSL workgroup's waves, in units of 64 cycles per wave
-int device_cu_count();    // CUs of the current device (cached; msda_api.hip)
 constexpr size_t kRecordLdsBudgetLds = 72 * 1024;  // the records of 16 waves (the fused backward's larger records: 100 KB)
 
 struct LdsLevelsPlan {
@@ -849,109 +866,178 @@ inline void set_value_mask(Params &, const uint8_t *) {}
 inline void advance_value_mask(MaskedParams &pg, const MaskedParams &p, size_t pixels) { pg.vmask = p.vmask + pixels; }
 inline void advance_value_mask(Params &, const Params &, size_t) {}
 
-// PP = RaggedParams: per-level point counts `ppl` (ragged_counts checked them; P is their maximum)
-template <typename T, typename TV = T, typename PP = Params>
-int run_fwd(const void *value, const int64_t *shapes, const void *loc, const void *attn, void *out, int64_t B,
-            int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int padding_mode, int align_corners,
-            int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr, const uint8_t *vmask = nullptr)
+// ---- discrete (nearest-pixel) sampling: msda_{fwd,bwd}_discrete_<dtype>, kernels in msda_discrete.hpp ----
+// MODE 0: the forward, 1: the attention-weight gradient.  G lanes per unit from D as everywhere (pick_group); the
+// workgroups are cut per (b, head) plane, kBlock / G units each.
+template <typename T, int VEC, int G, int MODE, typename TV> inline int launch_discrete(DiscreteParams &p, hipStream_t stream)
 {
-    Dims d{B, I, H, D, Q, L, P};
-    if (ppl != nullptr)
-        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const size_t out_bytes = (size_t)(B * Q * H * D) * sizeof(T);
-    if (out_bytes == 0) return 0;  // nothing to produce
-    const void *ptrs[] = {out};
-    int rc = check_common<T>(d, padding_mode, ptrs, 1);
-    if (rc) return rc;
-    if (samples(d) == 0 || I == 0) {  // empty sum
-        return (int)hipMemsetAsync(out, 0, out_bytes, stream);
+    constexpr int NU = kBlock / G;
+    p.nqc = (p.Q + NU - 1) / NU;
+    dim3 grid;
+    if (!plane_grid(p, p.B * p.H, p.nqc, grid)) {
+        set_error("grid too large");
+        return MSDA_ERR_TOO_LARGE;
     }
-    const void *ptrs2[] = {value, shapes, loc, attn};
-    rc = check_common<T>(d, padding_mode, ptrs2, 4);
-    if (rc) return rc;
-    if (!aligned_to(value, sizeof(TV)) || !aligned_to(out, sizeof(T)) || !aligned_to(loc, 2 * sizeof(T)) ||
-        !aligned_to(attn, sizeof(T)) || !aligned_to(shapes, 8)) {
-        set_error("misaligned buffer");
-        return MSDA_ERR_MISALIGNED;
+    if (MODE == 0) {
+        note_launch(0, 3);
+        note_launch(1, 0);
+        note_launch(2, 1);
+        note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, G, p.D);
+        const ProfileScope prof("msda_fwd_discrete_kernel", stream);
+        hipLaunchKernelGGL((msda_fwd_discrete_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
+    } else {
+        note_launch(4, 2);
+        note_launch(5, 0);
+        note_instance(11, VEC, G, p.D);
+        const ProfileScope prof("msda_bwd_discrete_attn_kernel", stream);
+        hipLaunchKernelGGL((msda_bwd_discrete_attn_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
     }
-    PP p{};
-    p.value = value;
-    p.shapes = shapes;
-    p.loc = loc;
-    p.attn = attn;
-    p.out = out;
-    fill_params(p, d, padding_mode, align_corners);
-    fill_level_starts(p, ppl, L);
-    set_value_mask(p, vmask);
+    return (int)hipGetLastError();
+}
+template <typename T, int VEC, int MODE, typename TV> inline int dispatch_discrete_group(DiscreteParams &p, hipStream_t stream)
+{
+    switch (pick_group((p.D + VEC - 1) / VEC)) {
+    case 4: return launch_discrete<T, VEC, 4, MODE, TV>(p, stream);
+    case 8: return launch_discrete<T, VEC, 8, MODE, TV>(p, stream);
+    case 16: return launch_discrete<T, VEC, 16, MODE, TV>(p, stream);
+    case 32: return launch_discrete<T, VEC, 32, MODE, TV>(p, stream);
+    default: return launch_discrete<T, VEC, 64, MODE, TV>(p, stream);
+    }
+}
+template <typename T, int MODE, typename TV> inline int dispatch_discrete(DiscreteParams &p, bool vec_ok, hipStream_t stream)
+{
+    constexpr int VECF = 16 / sizeof(T);
+    if (vec_ok && (p.D % VECF) == 0) return dispatch_discrete_group<T, VECF, MODE, TV>(p, stream);
+    return dispatch_discrete_group<T, 1, MODE, TV>(p, stream);
+}
+
+// ---- one call of an entry point, by name.  The extern "C" functions (MSDA_DEFINE_* below) fill one and hand it to their
+//      run_*; members a family does not have stay zero. ----
+struct Call {
+    // device buffers: the sampling operators' loc / attn and their gradients, the fused operators' proj / ref and theirs
+    const void *grad_out = nullptr, *value = nullptr;
+    const uint8_t *value_mask = nullptr;  // the masked twins: [B, I] bytes
+    const int64_t *shapes = nullptr;
+    const void *loc = nullptr, *attn = nullptr, *proj = nullptr, *ref = nullptr;
+    void *out = nullptr, *grad_value = nullptr, *grad_loc = nullptr, *grad_attn = nullptr, *grad_proj = nullptr,
+         *grad_ref_partial = nullptr;
+    int64_t B = 0, I = 0, H = 0, D = 0, Q = 0, L = 0;
+    int64_t P = 0, S = 0;  // per-level counts: their maximum and sum (take_counts); else the uniform P and 0
+    const int32_t *points_per_level = nullptr;  // host, L counts
+    const float *level_scale = nullptr;         // host, L scales, and the config's offset_scale: Hugging Face's box rule
+    double offset_scale = 0.0;
+    int ref_dim = 0;
+    int padding_mode = MSDA_PADDING_BORDER, align_corners = 0;  // (what discrete sampling, which has neither, runs with)
+    int64_t max_level_cells = 0, value_row_stride = 0;
+    void *workspace = nullptr;
+    int64_t workspace_bytes = 0;
+    void *stream = nullptr;
+};
+// checks points_per_level and notes its maximum and sum: once per call, in front of everything but the mask test
+inline int take_counts(Call &c) { return ragged_counts(c.points_per_level, c.L, c.P, c.S); }
+inline Dims make_dims(const Call &c)
+{
+    Dims d{c.B, c.I, c.H, c.D, c.Q, c.L, c.P, c.max_level_cells > 0 ? c.max_level_cells : 0};
+    d.S = c.S;
+    return d;
+}
+inline int check_ref_dim(int ref_dim)
+{
+    if (ref_dim == 2 || ref_dim == 4) return 0;
+    set_error("ref_dim must be 2 or 4, got %d", ref_dim);
+    return MSDA_ERR_BAD_ARG;
+}
+template <typename PP> constexpr bool kDiscrete = std::is_same<PP, DiscreteParams>::value;
+
+// ---- the shared steps, part 2 ----
+// The kernarg of a call whose buffers passed their checks: the sampling operators' pointers as they are (the fused run_*
+// then put proj / grad_proj / the partials where their kernels read them), sizes and modes, the family's extras (level
+// starts, box scales, mask: no-ops on a kernarg without them) and the row stride — the one argument checked this late.
+template <typename TV, typename PP> inline int fill_kernarg(PP &p, const Call &c, const Dims &d)
+{
+    p.value = c.value;
+    p.shapes = c.shapes;
+    p.loc = c.loc;
+    p.attn = c.attn;
+    p.out = c.out;
+    p.grad_out = c.grad_out;
+    p.grad_value = c.grad_value;
+    p.grad_loc = c.grad_loc;
+    p.grad_attn = c.grad_attn;
+    fill_params(p, d, c.padding_mode, c.align_corners);
+    fill_level_starts(p, c.points_per_level, d.L);
+    fill_box_scales(p, c.level_scale, c.offset_scale, d.L);
+    set_value_mask(p, c.value_mask);
+    p.ref = c.ref;
+    p.ref_dim = c.ref_dim;
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
-    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
-    p.touch = touch_plan(d);
-    const bool vec_ok = aligned_to(value, 16) && aligned_to(out, 16) && p.v_row % 16 == 0;  // (rows that start on 16-byte boundaries)
-    rc = dispatch_gather<T, 0, TV>(p, vec_ok, stream);
-    if (rc > 0) set_error("forward launch failed: %s", hipGetErrorString((hipError_t)rc));  // negative: message already set
+    return set_value_rows<TV>(p, d, c.value_row_stride);
+}
+// can the gather kernels use 16-byte pieces of the value rows and of the rows they read or write next to them?
+inline bool rows_vec_ok(const Params &p, const void *rows) { return aligned_to(p.value, 16) && aligned_to(rows, 16) && p.v_row % 16 == 0; }
+// a launch's own failure (positive: a hipError_t; a negative status has its message already)
+inline int launched(int rc, const char *what)
+{
+    if (rc > 0) set_error("%s launch failed: %s", what, hipGetErrorString((hipError_t)rc));
     return rc;
+}
+
+// PP = RaggedParams: per-level point counts; MaskedParams: the value-mask twin; DiscreteParams: nearest-pixel sampling
+// (msda_fwd_discrete_<dtype>: per-level counts, no padding mode — border —, its own kernels)
+template <typename T, typename TV = T, typename PP = Params> int run_fwd(const Call &c)
+{
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    const size_t out_bytes = (size_t)(d.B * d.Q * d.H * d.D) * sizeof(T);
+    if (out_bytes == 0) return 0;  // nothing to produce
+    int rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc == 0) rc = require_buffers({c.out});
+    if (rc) return rc;
+    if (samples(d) == 0 || d.I == 0) return zero_outputs({{c.out, out_bytes}}, stream);  // empty sum
+    if ((rc = require_buffers({c.value, c.shapes, c.loc, c.attn})) != 0) return rc;
+    if ((rc = check_aligned({{c.value, sizeof(TV)}, {c.out, sizeof(T)}, {c.loc, 2 * sizeof(T)}, {c.attn, sizeof(T)}, {c.shapes, 8}})) != 0)
+        return rc;
+    PP p{};
+    if ((rc = fill_kernarg<TV>(p, c, d)) != 0) return rc;
+    if constexpr (kDiscrete<PP>) {
+        return launched(dispatch_discrete<T, 0, TV>(p, rows_vec_ok(p, c.out), stream), "discrete forward");
+    } else {
+        p.touch = touch_plan(d);
+        return launched(dispatch_gather<T, 0, TV>(p, rows_vec_ok(p, c.out), stream), "forward");
+    }
 }
 
 // Module forward with the prologue fused in: `proj` is the raw query projection
 // [B, Q, H, L, P, 3] = (x offset, y offset, attention logit), `ref` the reference points [B, Q, ref_dim].
 // TS: storage type of `proj` and `out` (T unless the module keeps them in 16 bits next to fp32 reference points)
-// PP = RaggedParams (msda_fwd_fused_ragged_<dtype>): per-level point counts `ppl` (ragged_counts checked them; P is their
-// maximum), `proj` [B, Q, H, S, 3]
+// PP = RaggedParams (msda_fwd_fused_ragged_<dtype>): per-level point counts, `proj` [B, Q, H, S, 3]
 // PP = LevelRefParams (msda_fwd_fused_levelref_<dtype>): `ref` is [B, Q, L, ref_dim] and the points follow transformers'
 // rule (msda_kernels.hpp)
-// PP = HfBoxParams (msda_fwd_fused_hfbox_<dtype>): the per-level-count layout with transformers' box rule — `lscale` holds
-// L fp32 scales on the host, `off_scale` the config's offset_scale (the entry point checked ref_dim == 4)
-template <typename T, typename TV = T, typename TS = T, typename PP = Params>
-int run_fwd_fused(const void *value, const int64_t *shapes, const void *proj, const void *ref, void *out, int64_t B,
-                  int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,
-                  int align_corners, int64_t value_row_stride, void *stream_, const int32_t *ppl = nullptr,
-                  const float *lscale = nullptr, double off_scale = 0.0, const uint8_t *vmask = nullptr)
+// PP = HfBoxParams (msda_fwd_fused_hfbox_<dtype>): the per-level-count layout with transformers' box rule — `level_scale`
+// holds L fp32 scales on the host, `offset_scale` the config's (the entry point checked ref_dim == 4)
+template <typename T, typename TV = T, typename TS = T, typename PP = Params> int run_fwd_fused(const Call &c)
 {
-    Dims d{B, I, H, D, Q, L, P};
-    if (ppl != nullptr)
-        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const size_t out_bytes = (size_t)(B * Q * H * D) * sizeof(TS);
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    const size_t out_bytes = (size_t)(d.B * d.Q * d.H * d.D) * sizeof(TS);
     if (out_bytes == 0) return 0;
-    if (ref_dim != 2 && ref_dim != 4) {
-        set_error("ref_dim must be 2 or 4, got %d", ref_dim);
-        return MSDA_ERR_BAD_ARG;
-    }
-    const void *ptrs[] = {out};
-    int rc = check_common<T>(d, padding_mode, ptrs, 1);
+    int rc = check_ref_dim(c.ref_dim);
+    if (rc == 0) rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc == 0) rc = require_buffers({c.out});
     if (rc) return rc;
-    if (samples(d) == 0 || I == 0) return (int)hipMemsetAsync(out, 0, out_bytes, stream);
-    const void *ptrs2[] = {value, shapes, proj, ref};
-    rc = check_common<T>(d, padding_mode, ptrs2, 4);
-    if (rc) return rc;
+    if (samples(d) == 0 || d.I == 0) return zero_outputs({{c.out, out_bytes}}, stream);
+    if ((rc = require_buffers({c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
     if (fused_limit_exceeded(d)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
-    if (!aligned_to(value, sizeof(TV)) || !aligned_to(out, sizeof(TS)) || !aligned_to(proj, sizeof(TS)) ||
-        !aligned_to(ref, sizeof(T)) || !aligned_to(shapes, 8)) {
-        set_error("misaligned buffer");
-        return MSDA_ERR_MISALIGNED;
-    }
+    if ((rc = check_aligned({{c.value, sizeof(TV)}, {c.out, sizeof(TS)}, {c.proj, sizeof(TS)}, {c.ref, sizeof(T)}, {c.shapes, 8}})) != 0)
+        return rc;
     PP p{};
-    p.value = value;
-    p.shapes = shapes;
-    p.loc = proj;
-    p.attn = nullptr;
-    p.out = out;
-    fill_params(p, d, padding_mode, align_corners);
-    fill_level_starts(p, ppl, L);
-    fill_box_scales(p, lscale, off_scale, L);
-    set_value_mask(p, vmask);
-    p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
-    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
-    p.ref = ref;
-    p.ref_dim = ref_dim;
-    const bool vec_ok = aligned_to(value, 16) && aligned_to(out, 16) && p.v_row % 16 == 0;  // (rows that start on 16-byte boundaries)
-    rc = dispatch_gather<T, 2, TV, TS>(p, vec_ok, stream);
-    if (rc > 0) set_error("fused forward launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return rc;
+    if ((rc = fill_kernarg<TV>(p, c, d)) != 0) return rc;
+    p.loc = c.proj;
+    return launched(dispatch_gather<T, 2, TV, TS>(p, rows_vec_ok(p, c.out), stream), "fused forward");
 }
 
 // ---- single-launch grad_value for small problems (msda_value_small.hpp) ----
@@ -1148,64 +1234,39 @@ int run_value_float(PP &p, const Dims &d, void *workspace, int64_t workspace_byt
 #define MSDA_DEFINE_RUN_VALUE_FLOAT(TS) \
     MSDA_RUN_VALUE_FLOAT_(, TS, Params) MSDA_RUN_VALUE_FLOAT_(, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(, TS, MaskedParams)
 
-template <typename T, typename TV = T, typename PP = Params>
-int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, const void *loc, const void *attn,
-            void *grad_value, void *grad_loc, void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,
-            int64_t L, int64_t P, int padding_mode, int align_corners, int64_t max_level_cells, int64_t value_row_stride,
-            void *workspace, int64_t workspace_bytes, void *stream_, const int32_t *ppl = nullptr,
-            const uint8_t *vmask = nullptr)
+// PP as run_fwd's.  DiscreteParams (msda_bwd_discrete_<dtype>): grad_value and / or grad_attn — the sampling points have no
+// gradient in this mode, so there is no grad_loc buffer, the records always stay in the workspace
+// (msda_bwd_discrete_workspace_bytes sizes for that) and nothing is forked
+template <typename T, typename TV = T, typename PP = Params> int run_bwd(const Call &c)
 {
-    Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
-    if (ppl != nullptr)
-        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = check_common<T>(d, padding_mode, nullptr, 0);
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    void *const workspace = c.workspace, *const grad_value = c.grad_value, *const grad_loc = c.grad_loc, *const grad_attn = c.grad_attn;
+    const int64_t workspace_bytes = c.workspace_bytes;
+    int rc = check_common(d, sizeof(T), c.padding_mode);
     if (rc) return rc;
-    const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
-    const size_t ns = (size_t)(B * Q * H * samples(d));
-    if (B * Q * H * D == 0 || samples(d) == 0 || I == 0) {  // no sample touches anything: all gradients are zero
-        hipError_t e = hipSuccess;
-        if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
-        if (e == hipSuccess && ns && grad_loc) e = hipMemsetAsync(grad_loc, 0, ns * 2 * sizeof(T), stream);
-        if (e == hipSuccess && ns && grad_attn) e = hipMemsetAsync(grad_attn, 0, ns * sizeof(T), stream);
-        return (int)e;
-    }
+    const size_t ns = (size_t)(d.B * d.Q * d.H * samples(d));
+    if (nothing_sampled(d))
+        return zero_outputs({{grad_value, (size_t)(d.B * d.I * d.H * d.D) * sizeof(TV)}, {grad_loc, ns * 2 * sizeof(T)}, {grad_attn, ns * sizeof(T)}}, stream);
     const bool want_value = grad_value != nullptr;
     const bool want_sample = grad_loc != nullptr || grad_attn != nullptr;
-    if (want_sample && (grad_loc == nullptr || grad_attn == nullptr)) {
+    if (!kDiscrete<PP> && want_sample && (grad_loc == nullptr || grad_attn == nullptr)) {
         set_error("grad_loc and grad_attn must be both null or both non-null");
         return MSDA_ERR_BAD_ARG;
     }
-    const void *ptrs[] = {grad_out, value, shapes, loc, attn};
-    rc = check_common<T>(d, padding_mode, ptrs, 5);
-    if (rc) return rc;
-    if (!aligned_to(value, sizeof(TV)) || !aligned_to(grad_out, sizeof(T)) || !aligned_to(grad_value, sizeof(TV)) ||
-        !aligned_to(loc, 2 * sizeof(T)) || !aligned_to(grad_loc, 2 * sizeof(T)) || !aligned_to(attn, sizeof(T)) ||
-        !aligned_to(grad_attn, sizeof(T)) || !aligned_to(shapes, 8)) {
-        set_error("misaligned buffer");
-        return MSDA_ERR_MISALIGNED;
-    }
+    if ((rc = require_buffers({c.grad_out, c.value, c.shapes, c.loc, c.attn})) != 0) return rc;
+    if ((rc = check_aligned({{c.value, sizeof(TV)}, {c.grad_out, sizeof(T)}, {grad_value, sizeof(TV)}, {c.loc, 2 * sizeof(T)},
+                             {grad_loc, 2 * sizeof(T)}, {c.attn, sizeof(T)}, {grad_attn, sizeof(T)}, {c.shapes, 8}})) != 0)
+        return rc;
     PP p{};
-    p.value = value;
-    p.shapes = shapes;
-    p.loc = loc;
-    p.attn = attn;
-    p.grad_out = grad_out;
-    p.grad_value = grad_value;
-    p.grad_loc = grad_loc;
-    p.grad_attn = grad_attn;
-    fill_params(p, d, padding_mode, align_corners);
-    fill_level_starts(p, ppl, L);
-    set_value_mask(p, vmask);
-    p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
-    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
+    if ((rc = fill_kernarg<TV>(p, c, d)) != 0) return rc;
     // Both halves wanted, one after the other: the sorted records are dead once the gather has run and grad_loc /
     // grad_attn are written only by the sample-gradient kernel, so that kernel goes LAST and the records of as many
     // planes as fit live in those two buffers (three quarters of them in fp32: 61 of 82 MB at c2 @ 10k); the rest go
     // into grad_value itself, which only the finish kernel writes, behind the gather (single-round problems).  The
     // workspace layout shrinks accordingly (msda_bwd_workspace_bytes with MSDA_WS_RECORDS_IN_GRADS); a caller that
     // passes the full size loses nothing.
-    bool records_in_grads = want_sample && want_value && option_records_in_grads() != 0 && option_overlap() != 1 &&
+    bool records_in_grads = !kDiscrete<PP> && want_sample && want_value && option_records_in_grads() != 0 && option_overlap() != 1 &&
                             aligned_to(grad_loc, 16) && aligned_to(grad_attn, 16) && aligned_to(grad_value, 16);
     if (records_in_grads) {
         p.ent_alt0 = grad_loc;
@@ -1220,7 +1281,7 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
             p.ent_alt0 = p.ent_alt1 = p.ent_alt2 = nullptr;
         }
     }
-    const bool vec_sample = aligned_to(value, 16) && aligned_to(grad_out, 16) && p.v_row % 16 == 0;
+    const bool vec_sample = rows_vec_ok(p, c.grad_out);
     // The two halves of the backward are independent: when both are wanted, grad_loc/grad_attn run on a
     // forked side stream next to the grad_value pipeline (fork/join with events: still graph-capturable).
     hipStream_t sample_stream = stream;
@@ -1234,7 +1295,7 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
     // the automatic setting never forks; msda_set_option("overlap", 1) still forces it.
     const int ov = option_overlap();
     const bool ov_auto = false;
-    if (want_sample && want_value && (ov == 1 || (ov < 0 && ov_auto))) {
+    if (!kDiscrete<PP> && want_sample && want_value && (ov == 1 || (ov < 0 && ov_auto))) {
         hipStream_t side = side_stream_fork(stream);
         if (side != nullptr) {
             sample_stream = side;
@@ -1242,9 +1303,10 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
         }
     }
     auto run_sample = [&]() -> int {
-        const int r = dispatch_gather<T, 1, TV>(p, vec_sample, sample_stream);
-        if (r > 0) set_error("backward (grad_loc/grad_attn) launch failed: %s", hipGetErrorString((hipError_t)r));
-        return r;
+        if constexpr (kDiscrete<PP>)
+            return launched(dispatch_discrete<T, 1, TV>(p, vec_sample, sample_stream), "discrete backward (grad_attn)");
+        else
+            return launched(dispatch_gather<T, 1, TV>(p, vec_sample, sample_stream), "backward (grad_loc/grad_attn)");
     };
     if (want_sample && !records_in_grads) {
         rc = run_sample();
@@ -1262,149 +1324,6 @@ int run_bwd(const void *grad_out, const void *value, const int64_t *shapes, cons
             rc = jrc;
         }
     }
-    return rc;
-}
-
-// ---- discrete (nearest-pixel) sampling: msda_{fwd,bwd}_discrete_<dtype>, kernels in msda_discrete.hpp ----
-// MODE 0: the forward, 1: the attention-weight gradient.  G lanes per unit from D as everywhere (pick_group); the
-// workgroups are cut per (b, head) plane, kBlock / G units each.
-template <typename T, int VEC, int G, int MODE, typename TV> inline int launch_discrete(DiscreteParams &p, hipStream_t stream)
-{
-    constexpr int NU = kBlock / G;
-    p.nqc = (p.Q + NU - 1) / NU;
-    dim3 grid;
-    if (!plane_grid(p, p.B * p.H, p.nqc, grid)) {
-        set_error("grid too large");
-        return MSDA_ERR_TOO_LARGE;
-    }
-    if (MODE == 0) {
-        note_launch(0, 3);
-        note_launch(1, 0);
-        note_launch(2, 1);
-        note_launch(3, (int)(grid.x * grid.y * grid.z));
-        note_instance(8, VEC, G, p.D);
-        const ProfileScope prof("msda_fwd_discrete_kernel", stream);
-        hipLaunchKernelGGL((msda_fwd_discrete_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
-    } else {
-        note_launch(4, 2);
-        note_launch(5, 0);
-        note_instance(11, VEC, G, p.D);
-        const ProfileScope prof("msda_bwd_discrete_attn_kernel", stream);
-        hipLaunchKernelGGL((msda_bwd_discrete_attn_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
-    }
-    return (int)hipGetLastError();
-}
-template <typename T, int VEC, int MODE, typename TV> inline int dispatch_discrete_group(DiscreteParams &p, hipStream_t stream)
-{
-    switch (pick_group((p.D + VEC - 1) / VEC)) {
-    case 4: return launch_discrete<T, VEC, 4, MODE, TV>(p, stream);
-    case 8: return launch_discrete<T, VEC, 8, MODE, TV>(p, stream);
-    case 16: return launch_discrete<T, VEC, 16, MODE, TV>(p, stream);
-    case 32: return launch_discrete<T, VEC, 32, MODE, TV>(p, stream);
-    default: return launch_discrete<T, VEC, 64, MODE, TV>(p, stream);
-    }
-}
-template <typename T, int MODE, typename TV> inline int dispatch_discrete(DiscreteParams &p, bool vec_ok, hipStream_t stream)
-{
-    constexpr int VECF = 16 / sizeof(T);
-    if (vec_ok && (p.D % VECF) == 0) return dispatch_discrete_group<T, VECF, MODE, TV>(p, stream);
-    return dispatch_discrete_group<T, 1, MODE, TV>(p, stream);
-}
-
-// `ppl`: the L per-level point counts (host), each >= 1; S their sum
-template <typename T, typename TV = T>
-int run_fwd_discrete(const void *value, const int64_t *shapes, const void *loc, const void *attn, void *out, int64_t B,
-                     int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, const int32_t *ppl, int64_t value_row_stride,
-                     void *stream_)
-{
-    int64_t pmax, S;
-    int rc = ragged_counts(ppl, L, pmax, S);
-    if (rc) return rc;
-    Dims d{B, I, H, D, Q, L, pmax};
-    d.S = S;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const size_t out_bytes = (size_t)(B * Q * H * D) * sizeof(T);
-    if (out_bytes == 0) return 0;  // nothing to produce
-    const void *ptrs[] = {out};
-    rc = check_common<T>(d, MSDA_PADDING_BORDER, ptrs, 1);
-    if (rc) return rc;
-    if (samples(d) == 0 || I == 0) return (int)hipMemsetAsync(out, 0, out_bytes, stream);  // empty sum
-    const void *ptrs2[] = {value, shapes, loc, attn};
-    rc = check_common<T>(d, MSDA_PADDING_BORDER, ptrs2, 4);
-    if (rc) return rc;
-    if (!aligned_to(value, sizeof(TV)) || !aligned_to(out, sizeof(T)) || !aligned_to(loc, 2 * sizeof(T)) ||
-        !aligned_to(attn, sizeof(T)) || !aligned_to(shapes, 8)) {
-        set_error("misaligned buffer");
-        return MSDA_ERR_MISALIGNED;
-    }
-    DiscreteParams p{};
-    p.value = value;
-    p.shapes = shapes;
-    p.loc = loc;
-    p.attn = attn;
-    p.out = out;
-    fill_params(p, d, MSDA_PADDING_BORDER, 0);
-    fill_level_starts(p, ppl, L);
-    p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
-    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
-    const bool vec_ok = aligned_to(value, 16) && aligned_to(out, 16) && p.v_row % 16 == 0;
-    rc = dispatch_discrete<T, 0, TV>(p, vec_ok, stream);
-    if (rc > 0) set_error("discrete forward launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return rc;
-}
-
-// grad_value and / or grad_attn (either may be null); the sampling points have no gradient in this mode
-template <typename T, typename TV = T>
-int run_bwd_discrete(const void *grad_out, const void *value, const int64_t *shapes, const void *loc, const void *attn,
-                     void *grad_value, void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
-                     const int32_t *ppl, int64_t max_level_cells, int64_t value_row_stride, void *workspace,
-                     int64_t workspace_bytes, void *stream_)
-{
-    int64_t pmax, S;
-    int rc = ragged_counts(ppl, L, pmax, S);
-    if (rc) return rc;
-    Dims d{B, I, H, D, Q, L, pmax, max_level_cells > 0 ? max_level_cells : 0};
-    d.S = S;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    rc = check_common<T>(d, MSDA_PADDING_BORDER, nullptr, 0);
-    if (rc) return rc;
-    const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
-    const size_t ns = (size_t)(B * Q * H * samples(d));
-    if (B * Q * H * D == 0 || samples(d) == 0 || I == 0) {  // no sample touches anything: all gradients are zero
-        hipError_t e = hipSuccess;
-        if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
-        if (e == hipSuccess && ns && grad_attn) e = hipMemsetAsync(grad_attn, 0, ns * sizeof(T), stream);
-        return (int)e;
-    }
-    const void *ptrs[] = {grad_out, value, shapes, loc, attn};
-    rc = check_common<T>(d, MSDA_PADDING_BORDER, ptrs, 5);
-    if (rc) return rc;
-    if (!aligned_to(value, sizeof(TV)) || !aligned_to(grad_out, sizeof(T)) || !aligned_to(grad_value, sizeof(TV)) ||
-        !aligned_to(loc, 2 * sizeof(T)) || !aligned_to(attn, sizeof(T)) || !aligned_to(grad_attn, sizeof(T)) ||
-        !aligned_to(shapes, 8)) {
-        set_error("misaligned buffer");
-        return MSDA_ERR_MISALIGNED;
-    }
-    DiscreteParams p{};
-    p.value = value;
-    p.shapes = shapes;
-    p.loc = loc;
-    p.attn = attn;
-    p.grad_out = grad_out;
-    p.grad_value = grad_value;
-    p.grad_attn = grad_attn;
-    fill_params(p, d, MSDA_PADDING_BORDER, 0);
-    fill_level_starts(p, ppl, L);
-    p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
-    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
-    if (grad_attn != nullptr) {
-        const bool vec_ok = aligned_to(value, 16) && aligned_to(grad_out, 16) && p.v_row % 16 == 0;
-        rc = dispatch_discrete<T, 1, TV>(p, vec_ok, stream);
-        if (rc > 0) set_error("discrete backward (grad_attn) launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (rc) return rc;
-    }
-    // the records stay in the workspace (there is no grad_loc buffer to lend: msda_bwd_discrete_workspace_bytes sizes for that)
-    if (grad_value != nullptr) rc = run_value<T, TV, T, DiscreteParams>(p, d, workspace, workspace_bytes, stream);
     return rc;
 }
 
@@ -1426,57 +1345,38 @@ inline MaskedParams &value_pass_params(LevelRefMaskedParams &p) { return p; }  /
 // ... and so does Hugging Face's box rule: grad_value is the PER-LEVEL-COUNT pipeline on the parked points.
 inline RaggedParams &value_pass_params(HfBoxParams &p) { return p; }
 
-// PP = RaggedParams (msda_bwd_fused_ragged_<dtype>): per-level point counts `ppl`, proj / grad_proj [B, Q, H, S, 3]; the
+// PP = RaggedParams (msda_bwd_fused_ragged_<dtype>): per-level point counts, proj / grad_proj [B, Q, H, S, 3]; the
 // derived points and weights go to the workspace in the ragged operator's layout and its grad_value pipeline reads them
 // PP = LevelRefParams (msda_bwd_fused_levelref_<dtype>): `ref` [B, Q, L, ref_dim], partials [B, Q, H, L, ref_dim]
 // PP = HfBoxParams (msda_bwd_fused_hfbox_<dtype>): the per-level-count layout and workspace, transformers' box rule with
-// the host's `lscale` [L] and `off_scale`
-template <typename T, typename TV = T, typename TS = T, typename PP = Params>
-int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes, const void *proj, const void *ref,
-                  void *grad_value, void *grad_proj, void *grad_ref_part, int64_t B, int64_t I, int64_t H, int64_t D,
-                  int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode, int align_corners,
-                  int64_t max_level_cells, int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream_,
-                  const int32_t *ppl = nullptr, const float *lscale = nullptr, double off_scale = 0.0,
-                  const uint8_t *vmask = nullptr)
+// the host's `level_scale` [L] and `offset_scale`
+template <typename T, typename TV = T, typename TS = T, typename PP = Params> int run_bwd_fused(const Call &c)
 {
-    Dims d{B, I, H, D, Q, L, P, max_level_cells > 0 ? max_level_cells : 0};
-    if (ppl != nullptr)
-        for (int64_t l = 0; l < L; ++l) d.S += ppl[l];
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = check_common<T>(d, padding_mode, nullptr, 0);
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    void *const workspace = c.workspace, *const grad_value = c.grad_value;
+    const int64_t workspace_bytes = c.workspace_bytes;
+    int rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc == 0) rc = check_ref_dim(c.ref_dim);
     if (rc) return rc;
-    if (ref_dim != 2 && ref_dim != 4) {
-        set_error("ref_dim must be 2 or 4, got %d", ref_dim);
-        return MSDA_ERR_BAD_ARG;
-    }
-    const size_t gv_bytes = (size_t)(B * I * H * D) * sizeof(TV);
-    const size_t ns = (size_t)(B * Q * H * samples(d));
-    const size_t nref = (size_t)(B * Q * H) * (kLevelRef<PP> ? (size_t)L : 1) * ref_dim;
+    const size_t ns = (size_t)(d.B * d.Q * d.H * samples(d));
+    const size_t nref = (size_t)(d.B * d.Q * d.H) * (kLevelRef<PP> ? (size_t)d.L : 1) * c.ref_dim;
     // (a buffer of no elements may be null: PyTorch's empty tensors are — a call with Q = 0 has nothing to produce there)
-    if ((ns && grad_proj == nullptr) || (nref && grad_ref_part == nullptr)) {
+    if ((ns && c.grad_proj == nullptr) || (nref && c.grad_ref_partial == nullptr)) {
         set_error("the fused backward always produces grad_proj and the grad_reference_points partials");
         return MSDA_ERR_BAD_ARG;
     }
-    if (B * Q * H * D == 0 || samples(d) == 0 || I == 0) {  // no sample touches anything: all gradients are zero
-        hipError_t e = hipSuccess;
-        if (gv_bytes && grad_value) e = hipMemsetAsync(grad_value, 0, gv_bytes, stream);
-        if (e == hipSuccess && ns) e = hipMemsetAsync(grad_proj, 0, ns * 3 * sizeof(TS), stream);
-        if (e == hipSuccess && nref) e = hipMemsetAsync(grad_ref_part, 0, nref * sizeof(T), stream);
-        return (int)e;
-    }
-    const void *ptrs[] = {grad_out, value, shapes, proj, ref};
-    rc = check_common<T>(d, padding_mode, ptrs, 5);
-    if (rc) return rc;
+    if (nothing_sampled(d))
+        return zero_outputs({{grad_value, (size_t)(d.B * d.I * d.H * d.D) * sizeof(TV)}, {c.grad_proj, ns * 3 * sizeof(TS)},
+                             {c.grad_ref_partial, nref * sizeof(T)}}, stream);
+    if ((rc = require_buffers({c.grad_out, c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
     if (fused_limit_exceeded(d)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
-    if (!aligned_to(value, sizeof(TV)) || !aligned_to(grad_out, sizeof(TS)) || !aligned_to(grad_value, sizeof(TV)) ||
-        !aligned_to(proj, sizeof(TS)) || !aligned_to(grad_proj, sizeof(TS)) || !aligned_to(ref, sizeof(T)) ||
-        !aligned_to(grad_ref_part, sizeof(T)) || !aligned_to(shapes, 8)) {
-        set_error("misaligned buffer");
-        return MSDA_ERR_MISALIGNED;
-    }
+    if ((rc = check_aligned({{c.value, sizeof(TV)}, {c.grad_out, sizeof(TS)}, {grad_value, sizeof(TV)}, {c.proj, sizeof(TS)},
+                             {c.grad_proj, sizeof(TS)}, {c.ref, sizeof(T)}, {c.grad_ref_partial, sizeof(T)}, {c.shapes, 8}})) != 0)
+        return rc;
     const bool want_value = grad_value != nullptr;
     // the derived points and weights are parked in float by the 16-bit operators too (ParkType), and their grad_value passes
     // are the float pipeline on 16-bit rows — so those calls have the float limits, as the workspace queries say
@@ -1485,39 +1385,22 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         set_error("tensor too large for the fused backward's float32 grad_value passes");
         return MSDA_ERR_TOO_LARGE;
     }
-    const size_t mat = fused_mat_bytes(B, H, Q, samples(d), sizeof(MT));
+    const size_t mat = fused_mat_bytes(d.B, d.H, d.Q, samples(d), sizeof(MT));
     if (want_value && (workspace == nullptr || !aligned_to(workspace, 256) || (uint64_t)workspace_bytes < mat)) {
         set_error("the fused backward needs a 256-byte aligned workspace of at least %zu bytes for grad_value", mat);
         return MSDA_ERR_BAD_ARG;
     }
     PP p{};
-    p.value = value;
-    p.shapes = shapes;
-    p.loc = proj;
-    p.attn = nullptr;
-    p.grad_out = grad_out;
-    p.grad_value = grad_value;
-    p.grad_loc = grad_proj;
-    p.grad_attn = grad_ref_part;
-    fill_params(p, d, padding_mode, align_corners);
-    fill_level_starts(p, ppl, L);
-    fill_box_scales(p, lscale, off_scale, L);
-    set_value_mask(p, vmask);
-    p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
-    if ((rc = set_value_rows<TV>(p, d, value_row_stride)) != 0) return rc;
-    p.ref = ref;
-    p.ref_dim = ref_dim;
+    if ((rc = fill_kernarg<TV>(p, c, d)) != 0) return rc;
+    p.loc = c.proj;
+    p.grad_loc = c.grad_proj;
+    p.grad_attn = c.grad_ref_partial;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     if (want_value) {
         p.mat_loc = ws;
         p.mat_attn = ws + ns * 2 * sizeof(MT);
     }
-    const bool vec_ok = aligned_to(value, 16) && aligned_to(grad_out, 16) && p.v_row % 16 == 0;
-    rc = dispatch_gather<T, 3, TV, TS>(p, vec_ok, stream);
-    if (rc) {
-        if (rc > 0) set_error("fused backward launch failed: %s", hipGetErrorString((hipError_t)rc));
-        return rc;
-    }
+    if ((rc = launched(dispatch_gather<T, 3, TV, TS>(p, rows_vec_ok(p, c.grad_out), stream), "fused backward")) != 0) return rc;
     if (want_value) {
         p.loc = p.mat_loc;
         p.attn = p.mat_attn;
@@ -1533,22 +1416,42 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
 
 }  // namespace msda
 
+// ---- the extern "C" entry points (include/msda_hip.h has the argument lists): each fills a Call by name — the groups
+//      below take the arguments that every list of their kind has, under the header's names — and calls its run_* ----
+#define MSDA_TAKE_SIZES c.B = B; c.I = I; c.H = H; c.D = D; c.Q = Q; c.L = L; c.value_row_stride = value_row_stride; c.stream = stream;
+#define MSDA_TAKE_MODES c.padding_mode = padding_mode; c.align_corners = align_corners;
+#define MSDA_TAKE_FWD msda::Call c; c.value = value; c.shapes = shapes; c.loc = loc; c.attn = attn; c.out = out; MSDA_TAKE_SIZES
+#define MSDA_TAKE_FWD_FUSED \
+    msda::Call c; c.value = value; c.shapes = shapes; c.proj = proj; c.ref = ref; c.out = out; c.ref_dim = ref_dim; MSDA_TAKE_SIZES MSDA_TAKE_MODES
+#define MSDA_TAKE_WORKSPACE c.max_level_cells = max_level_cells; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+#define MSDA_TAKE_BWD /* (grad_loc: not in discrete sampling's list) */ \
+    msda::Call c; c.grad_out = grad_out; c.value = value; c.shapes = shapes; c.loc = loc; c.attn = attn; c.grad_value = grad_value; \
+    c.grad_attn = grad_attn; MSDA_TAKE_SIZES MSDA_TAKE_WORKSPACE
+#define MSDA_TAKE_BWD_FUSED \
+    msda::Call c; c.grad_out = grad_out; c.value = value; c.shapes = shapes; c.proj = proj; c.ref = ref; c.grad_value = grad_value; \
+    c.grad_proj = grad_proj; c.grad_ref_partial = grad_ref_partial; c.ref_dim = ref_dim; MSDA_TAKE_SIZES MSDA_TAKE_MODES MSDA_TAKE_WORKSPACE
+// per-level point counts: checked once, here, and their maximum and sum noted in the record
+#define MSDA_TAKE_COUNTS c.points_per_level = points_per_level; if (const int rc = msda::take_counts(c)) return rc;
+// ... and Hugging Face's box rule behind them
+#define MSDA_TAKE_BOX_RULE \
+    c.level_scale = level_scale; c.offset_scale = offset_scale; if (const int rc = msda::box_rule_args(level_scale, L, ref_dim)) return rc;
+
 #define MSDA_DEFINE_ENTRY_POINTS2(SUF, T, TV)                                                                        \
     extern "C" int msda_fwd_##SUF(const void *value, const int64_t *shapes, const void *loc, const void *attn,  \
                                   void *out, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,  \
                                   int64_t P, int padding_mode, int align_corners, int64_t value_row_stride,     \
                                   void *stream)                                                                  \
     {                                                                                                            \
-        return msda::run_fwd<T, TV>(value, shapes, loc, attn, out, B, I, H, D, Q, L, P, padding_mode,               \
-                                align_corners, value_row_stride, stream);                                        \
+        MSDA_TAKE_FWD MSDA_TAKE_MODES c.P = P;                                                                   \
+        return msda::run_fwd<T, TV>(c);                                                                          \
     }                                                                                                            \
     extern "C" int msda_fwd_fused_##SUF(const void *value, const int64_t *shapes, const void *proj,             \
                                         const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,  \
                                         int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,          \
                                         int align_corners, int64_t value_row_stride, void *stream)               \
     {                                                                                                            \
-        return msda::run_fwd_fused<T, TV>(value, shapes, proj, ref, out, B, I, H, D, Q, L, P, ref_dim, padding_mode, \
-                                      align_corners, value_row_stride, stream);                                  \
+        MSDA_TAKE_FWD_FUSED c.P = P;                                                                             \
+        return msda::run_fwd_fused<T, TV>(c);                                                                    \
     }                                                                                                            \
     extern "C" int msda_bwd_##SUF(const void *grad_out, const void *value, const int64_t *shapes,               \
                                   const void *loc, const void *attn, void *grad_value, void *grad_loc,          \
@@ -1557,9 +1460,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                   int64_t max_level_cells, int64_t value_row_stride, void *workspace,           \
                                   int64_t workspace_bytes, void *stream)                                         \
     {                                                                                                            \
-        return msda::run_bwd<T, TV>(grad_out, value, shapes, loc, attn, grad_value, grad_loc, grad_attn, B, I, H,   \
-                                D, Q, L, P, padding_mode, align_corners, max_level_cells, value_row_stride,      \
-                                workspace, workspace_bytes, stream);                                             \
+        MSDA_TAKE_BWD MSDA_TAKE_MODES c.grad_loc = grad_loc; c.P = P;                                            \
+        return msda::run_bwd<T, TV>(c);                                                                          \
     }                                                                                                            \
     extern "C" int msda_bwd_fused_##SUF(const void *grad_out, const void *value, const int64_t *shapes,         \
                                         const void *proj, const void *ref, void *grad_value, void *grad_proj,   \
@@ -1568,22 +1470,16 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                         int align_corners, int64_t max_level_cells, int64_t value_row_stride,    \
                                         void *workspace, int64_t workspace_bytes, void *stream)                  \
     {                                                                                                            \
-        return msda::run_bwd_fused<T, TV>(grad_out, value, shapes, proj, ref, grad_value, grad_proj,                \
-                                      grad_ref_partial, B, I, H, D, Q, L, P, ref_dim, padding_mode,              \
-                                      align_corners, max_level_cells, value_row_stride, workspace,               \
-                                      workspace_bytes, stream);                                                  \
+        MSDA_TAKE_BWD_FUSED c.P = P;                                                                             \
+        return msda::run_bwd_fused<T, TV>(c);                                                                    \
     }                                                                                                            \
     extern "C" int msda_fwd_ragged_##SUF(const void *value, const int64_t *shapes, const void *loc, const void *attn, \
                                          void *out, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, \
                                          const int32_t *points_per_level, int padding_mode, int align_corners,    \
                                          int64_t value_row_stride, void *stream)                                 \
     {                                                                                                            \
-        int64_t pmax, S;                                                                                         \
-        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
-        if (rc) return rc;                                                                                       \
-        return msda::run_fwd<T, TV, msda::RaggedParams>(value, shapes, loc, attn, out, B, I, H, D, Q, L, pmax,   \
-                                                        padding_mode, align_corners, value_row_stride, stream,   \
-                                                        points_per_level);                                       \
+        MSDA_TAKE_FWD MSDA_TAKE_MODES MSDA_TAKE_COUNTS                                                           \
+        return msda::run_fwd<T, TV, msda::RaggedParams>(c);                                                      \
     }                                                                                                            \
     extern "C" int msda_bwd_ragged_##SUF(const void *grad_out, const void *value, const int64_t *shapes,        \
                                          const void *loc, const void *attn, void *grad_value, void *grad_loc,   \
@@ -1592,21 +1488,16 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                          int align_corners, int64_t max_level_cells, int64_t value_row_stride,   \
                                          void *workspace, int64_t workspace_bytes, void *stream)                 \
     {                                                                                                            \
-        int64_t pmax, S;                                                                                         \
-        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
-        if (rc) return rc;                                                                                       \
-        return msda::run_bwd<T, TV, msda::RaggedParams>(grad_out, value, shapes, loc, attn, grad_value, grad_loc, \
-                                                        grad_attn, B, I, H, D, Q, L, pmax, padding_mode,         \
-                                                        align_corners, max_level_cells, value_row_stride,        \
-                                                        workspace, workspace_bytes, stream, points_per_level);   \
+        MSDA_TAKE_BWD MSDA_TAKE_MODES c.grad_loc = grad_loc; MSDA_TAKE_COUNTS                                    \
+        return msda::run_bwd<T, TV, msda::RaggedParams>(c);                                                      \
     }                                                                                                            \
     extern "C" int msda_fwd_discrete_##SUF(const void *value, const int64_t *shapes, const void *loc,           \
                                            const void *attn, void *out, int64_t B, int64_t I, int64_t H,         \
                                            int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level,     \
                                            int64_t value_row_stride, void *stream)                               \
     {                                                                                                            \
-        return msda::run_fwd_discrete<T, TV>(value, shapes, loc, attn, out, B, I, H, D, Q, L, points_per_level,  \
-                                             value_row_stride, stream);                                          \
+        MSDA_TAKE_FWD MSDA_TAKE_COUNTS                                                                           \
+        return msda::run_fwd<T, TV, msda::DiscreteParams>(c);                                                    \
     }                                                                                                            \
     extern "C" int msda_bwd_discrete_##SUF(const void *grad_out, const void *value, const int64_t *shapes,      \
                                            const void *loc, const void *attn, void *grad_value, void *grad_attn, \
@@ -1615,9 +1506,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                            int64_t value_row_stride, void *workspace, int64_t workspace_bytes,   \
                                            void *stream)                                                         \
     {                                                                                                            \
-        return msda::run_bwd_discrete<T, TV>(grad_out, value, shapes, loc, attn, grad_value, grad_attn, B, I, H, \
-                                             D, Q, L, points_per_level, max_level_cells, value_row_stride,       \
-                                             workspace, workspace_bytes, stream);                                \
+        MSDA_TAKE_BWD MSDA_TAKE_COUNTS                                                                           \
+        return msda::run_bwd<T, TV, msda::DiscreteParams>(c);                                                    \
     }                                                                                                            \
     MSDA_DEFINE_MASKED_ENTRY_POINTS(SUF, T, TV)                                                                   \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)                                                          \
@@ -1633,8 +1523,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                         int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,          \
                                         int align_corners, int64_t value_row_stride, void *stream)               \
     {                                                                                                            \
-        return msda::run_fwd_fused<T, TS, TS>(value, shapes, proj, ref, out, B, I, H, D, Q, L, P, ref_dim,          \
-                                          padding_mode, align_corners, value_row_stride, stream);                \
+        MSDA_TAKE_FWD_FUSED c.P = P;                                                                             \
+        return msda::run_fwd_fused<T, TS, TS>(c);                                                                \
     }                                                                                                            \
     extern "C" int msda_bwd_fused_##SUF(const void *grad_out, const void *value, const int64_t *shapes,         \
                                         const void *proj, const void *ref, void *grad_value, void *grad_proj,   \
@@ -1643,10 +1533,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                         int align_corners, int64_t max_level_cells, int64_t value_row_stride,    \
                                         void *workspace, int64_t workspace_bytes, void *stream)                  \
     {                                                                                                            \
-        return msda::run_bwd_fused<T, TS, TS>(grad_out, value, shapes, proj, ref, grad_value, grad_proj,            \
-                                          grad_ref_partial, B, I, H, D, Q, L, P, ref_dim, padding_mode,          \
-                                          align_corners, max_level_cells, value_row_stride, workspace,           \
-                                          workspace_bytes, stream);                                              \
+        MSDA_TAKE_BWD_FUSED c.P = P;                                                                             \
+        return msda::run_bwd_fused<T, TS, TS>(c);                                                                \
     }                                                                                                            \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)                                                         \
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)                                                       \
@@ -1662,12 +1550,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                                int ref_dim, int padding_mode, int align_corners,                  \
                                                int64_t value_row_stride, void *stream)                            \
     {                                                                                                            \
-        int64_t pmax, S;                                                                                         \
-        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
-        if (rc) return rc;                                                                                       \
-        return msda::run_fwd_fused<T, TV, TS, msda::RaggedParams>(value, shapes, proj, ref, out, B, I, H, D, Q, L, \
-                                                                  pmax, ref_dim, padding_mode, align_corners,     \
-                                                                  value_row_stride, stream, points_per_level);    \
+        MSDA_TAKE_FWD_FUSED MSDA_TAKE_COUNTS                                                                     \
+        return msda::run_fwd_fused<T, TV, TS, msda::RaggedParams>(c);                                            \
     }                                                                                                            \
     extern "C" int msda_bwd_fused_ragged_##SUF(const void *grad_out, const void *value, const int64_t *shapes,   \
                                                const void *proj, const void *ref, void *grad_value,               \
@@ -1678,13 +1562,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                                int64_t value_row_stride, void *workspace,                         \
                                                int64_t workspace_bytes, void *stream)                             \
     {                                                                                                            \
-        int64_t pmax, S;                                                                                         \
-        const int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                        \
-        if (rc) return rc;                                                                                       \
-        return msda::run_bwd_fused<T, TV, TS, msda::RaggedParams>(                                                \
-            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, pmax,  \
-            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
-            stream, points_per_level);                                                                           \
+        MSDA_TAKE_BWD_FUSED MSDA_TAKE_COUNTS                                                                     \
+        return msda::run_bwd_fused<T, TV, TS, msda::RaggedParams>(c);                                            \
     }
 
 // the module's fused kernels for per-level reference points and transformers' point rule:
@@ -1697,9 +1576,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                                  int padding_mode, int align_corners, int64_t value_row_stride,   \
                                                  void *stream)                                                    \
     {                                                                                                            \
-        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefParams>(value, shapes, proj, ref, out, B, I, H, D, Q, L, \
-                                                                    P, ref_dim, padding_mode, align_corners,     \
-                                                                    value_row_stride, stream);                   \
+        MSDA_TAKE_FWD_FUSED c.P = P;                                                                             \
+        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefParams>(c);                                          \
     }                                                                                                            \
     extern "C" int msda_bwd_fused_levelref_##SUF(const void *grad_out, const void *value, const int64_t *shapes, \
                                                  const void *proj, const void *ref, void *grad_value,             \
@@ -1709,10 +1587,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                                  int64_t max_level_cells, int64_t value_row_stride,               \
                                                  void *workspace, int64_t workspace_bytes, void *stream)          \
     {                                                                                                            \
-        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefParams>(                                              \
-            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, P,     \
-            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
-            stream);                                                                                             \
+        MSDA_TAKE_BWD_FUSED c.P = P;                                                                             \
+        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefParams>(c);                                          \
     }
 
 // the module's fused kernels for Hugging Face's box rule with per-level point counts (D-FINE, DEIMv2, RT-DETRv2):
@@ -1726,14 +1602,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                               int padding_mode, int align_corners, int64_t value_row_stride,      \
                                               void *stream)                                                       \
     {                                                                                                            \
-        int64_t pmax, S;                                                                                         \
-        int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                              \
-        if (rc) return rc;                                                                                       \
-        if ((rc = msda::box_rule_args(level_scale, L, ref_dim)) != 0) return rc;                                 \
-        return msda::run_fwd_fused<T, TV, TS, msda::HfBoxParams>(value, shapes, proj, ref, out, B, I, H, D, Q, L, \
-                                                                 pmax, ref_dim, padding_mode, align_corners,      \
-                                                                 value_row_stride, stream, points_per_level,      \
-                                                                 level_scale, offset_scale);                      \
+        MSDA_TAKE_FWD_FUSED MSDA_TAKE_COUNTS MSDA_TAKE_BOX_RULE                                                  \
+        return msda::run_fwd_fused<T, TV, TS, msda::HfBoxParams>(c);                                             \
     }                                                                                                            \
     extern "C" int msda_bwd_fused_hfbox_##SUF(const void *grad_out, const void *value, const int64_t *shapes,    \
                                               const void *proj, const void *ref, void *grad_value,                \
@@ -1745,14 +1615,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                               int64_t value_row_stride, void *workspace,                          \
                                               int64_t workspace_bytes, void *stream)                              \
     {                                                                                                            \
-        int64_t pmax, S;                                                                                         \
-        int rc = msda::ragged_counts(points_per_level, L, pmax, S);                                              \
-        if (rc) return rc;                                                                                       \
-        if ((rc = msda::box_rule_args(level_scale, L, ref_dim)) != 0) return rc;                                 \
-        return msda::run_bwd_fused<T, TV, TS, msda::HfBoxParams>(                                                 \
-            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, pmax,  \
-            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
-            stream, points_per_level, level_scale, offset_scale);                                                \
+        MSDA_TAKE_BWD_FUSED MSDA_TAKE_COUNTS MSDA_TAKE_BOX_RULE                                                  \
+        return msda::run_bwd_fused<T, TV, TS, msda::HfBoxParams>(c);                                             \
     }
 
 // the value-mask twins: msda_{fwd,bwd}_masked_<suffix> and msda_{fwd,bwd}_fused_levelref_masked_<suffix> — the twins'
@@ -1770,9 +1634,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                          int align_corners, int64_t value_row_stride, void *stream)             \
     {                                                                                                            \
         MSDA_MASK_REQUIRED("msda_fwd_masked")                                                                    \
-        return msda::run_fwd<T, TV, msda::MaskedParams>(value, shapes, loc, attn, out, B, I, H, D, Q, L, P,      \
-                                                        padding_mode, align_corners, value_row_stride, stream,   \
-                                                        nullptr, value_mask);                                    \
+        MSDA_TAKE_FWD MSDA_TAKE_MODES c.P = P; c.value_mask = value_mask;                                        \
+        return msda::run_fwd<T, TV, msda::MaskedParams>(c);                                                      \
     }                                                                                                            \
     extern "C" int msda_bwd_masked_##SUF(const void *grad_out, const void *value, const uint8_t *value_mask,    \
                                          const int64_t *shapes, const void *loc, const void *attn,              \
@@ -1782,10 +1645,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                          void *workspace, int64_t workspace_bytes, void *stream)                 \
     {                                                                                                            \
         MSDA_MASK_REQUIRED("msda_bwd_masked")                                                                    \
-        return msda::run_bwd<T, TV, msda::MaskedParams>(grad_out, value, shapes, loc, attn, grad_value, grad_loc, \
-                                                        grad_attn, B, I, H, D, Q, L, P, padding_mode,            \
-                                                        align_corners, max_level_cells, value_row_stride,        \
-                                                        workspace, workspace_bytes, stream, nullptr, value_mask); \
+        MSDA_TAKE_BWD MSDA_TAKE_MODES c.grad_loc = grad_loc; c.P = P; c.value_mask = value_mask;                 \
+        return msda::run_bwd<T, TV, msda::MaskedParams>(c);                                                      \
     }
 #define MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TV, TS)                                            \
     extern "C" int msda_fwd_fused_levelref_masked_##SUF(const void *value, const uint8_t *value_mask,           \
@@ -1796,9 +1657,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
                                                         int64_t value_row_stride, void *stream)                  \
     {                                                                                                            \
         MSDA_MASK_REQUIRED("msda_fwd_fused_levelref_masked")                                                     \
-        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(                                        \
-            value, shapes, proj, ref, out, B, I, H, D, Q, L, P, ref_dim, padding_mode, align_corners,            \
-            value_row_stride, stream, nullptr, nullptr, 0.0, value_mask);                                        \
+        MSDA_TAKE_FWD_FUSED c.P = P; c.value_mask = value_mask;                                                  \
+        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(c);                                    \
     }                                                                                                            \
     extern "C" int msda_bwd_fused_levelref_masked_##SUF(                                                         \
         const void *grad_out, const void *value, const uint8_t *value_mask, const int64_t *shapes,              \
@@ -1808,10 +1668,8 @@ int run_bwd_fused(const void *grad_out, const void *value, const int64_t *shapes
         int64_t workspace_bytes, void *stream)                                                                   \
     {                                                                                                            \
         MSDA_MASK_REQUIRED("msda_bwd_fused_levelref_masked")                                                     \
-        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(                                        \
-            grad_out, value, shapes, proj, ref, grad_value, grad_proj, grad_ref_partial, B, I, H, D, Q, L, P,     \
-            ref_dim, padding_mode, align_corners, max_level_cells, value_row_stride, workspace, workspace_bytes,  \
-            stream, nullptr, nullptr, 0.0, value_mask);                                                          \
+        MSDA_TAKE_BWD_FUSED c.P = P; c.value_mask = value_mask;                                                  \
+        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(c);                                    \
     }
 
 // one storage type for every tensor
