@@ -317,6 +317,32 @@ extern "C" {
  * msda_bwd_workspace_bytes / msda_bwd_fused_workspace_bytes answer for these calls too.  The one-wave-per-unit forward is
  * never chosen for a masked call (msda_last_launch_info("fwd_variant") says 0 or 1).
  *
+ * The QUERY PADDING MASK entry points — ADDITIONS WITHIN ABI 12, probed by symbol: msda_fwd_qmasked_<dtype> /
+ * msda_bwd_qmasked_<dtype> (the six suffixes of the _masked_ pair) and msda_fwd_fused_levelref_qmasked_<suffix> /
+ * msda_bwd_fused_levelref_qmasked_<suffix> (the eight of that pair) take the _masked_ twins' argument lists with one
+ * argument behind `value_mask`, and run the twins' kernels:
+ *
+ *   query_mask   [B, Q] bytes on the device, one per query: non-zero = the query is real, 0 = padding
+ *
+ * BOTH masks are required — a NULL in either is MSDA_ERR_BAD_ARG before anything else is looked at; a caller without a
+ * value mask passes all ones.  With plain(...) the _masked_ call on the same arguments:
+ *
+ *   real queries     their rows of out, grad_loc, grad_attn (grad_proj, grad_ref_partial) are plain's, bit for bit
+ *   masked queries   those rows are zeros, every one of them written; their sampling inputs (points, weights, projection,
+ *                    reference point, grad_out row) are never loaded, so NO BIT of them reaches any output
+ *   grad_value       the sum over the real queries' samples only.  The count and place passes of the sorted pipeline and
+ *                    the single-launch kernel's walks drop a masked query's samples where they drop a "zeros" sample
+ *                    outside every cell; scan, gather and finish see shorter lists.  Against plain on sanitised inputs
+ *                    (masked queries: points 0.5, weights / logits 0, grad_out row 0) it is equal on exactly representable
+ *                    inputs only: removing records moves the gather's window cuts, and on general inputs the last bit can
+ *                    differ (MSDA_WS_PASSES below has the same property).  It is bitwise reproducible under the conditions
+ *                    that hold without the mask.
+ *
+ * The forward and the sample-gradient kernel look a wave's units up before phase 0; a call with a query mask gives up those
+ * kernels' input prefetches (they would request a masked query's points).  Size guards, limits, workspaces,
+ * msda_bwd_supported, MSDA_WS_RECORDS_IN_GRADS and MSDA_WS_PASSES(n) (the mask pointer advances with value_mask) are the
+ * twins'.  The _masked_ entry points are these kernels with query_mask = NULL.
+ *
  * Discrete (nearest-pixel) sampling — ADDITIONS WITHIN ABI 12: no existing signature changes and MSDA_ABI_VERSION stays
  * 12, so a caller PROBES FOR THESE BY SYMBOL (dlsym / hasattr) instead of by version; a library built before them simply
  * lacks them.  msda_fwd_discrete_<dtype> / msda_bwd_discrete_<dtype> take the ragged layout above (`points_per_level`,
@@ -414,6 +440,41 @@ MSDA_DECLARE(f32_vf16)
 MSDA_DECLARE_FUSED_STORAGE(f32_sbf16)
 MSDA_DECLARE_FUSED_STORAGE(f32_sf16)
 #undef MSDA_DECLARE_FUSED_STORAGE
+
+/* The query-mask entry points (see "QUERY PADDING MASK" above), declared by macros of their own: the six suffixes of
+ * msda_fwd_masked_<dtype> for the plain pair, the eight of msda_fwd_fused_levelref_masked_<suffix> for the fused one. */
+#define MSDA_QUERY_MASK_PLAIN(SUF)                                                                     \
+    MSDA_API int msda_fwd_qmasked_##SUF(const void *value, const uint8_t *value_mask,               \
+                       const uint8_t *query_mask, const int64_t *shapes, const void *loc,           \
+                       const void *attn, void *out, int64_t B, int64_t I, int64_t H, int64_t D,     \
+                       int64_t Q, int64_t L, int64_t P, int padding_mode, int align_corners,        \
+                       int64_t value_row_stride, void *stream);                                     \
+    MSDA_API int msda_bwd_qmasked_##SUF(const void *grad_out, const void *value,                    \
+                       const uint8_t *value_mask, const uint8_t *query_mask, const int64_t *shapes, \
+                       const void *loc, const void *attn, void *grad_value, void *grad_loc,         \
+                       void *grad_attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,      \
+                       int64_t L, int64_t P, int padding_mode, int align_corners,                   \
+                       int64_t max_level_cells, int64_t value_row_stride, void *workspace,          \
+                       int64_t workspace_bytes, void *stream);
+#define MSDA_QUERY_MASK_FUSED(SUF)                                                                     \
+    MSDA_API int msda_fwd_fused_levelref_qmasked_##SUF(const void *value, const uint8_t *value_mask,\
+                       const uint8_t *query_mask, const int64_t *shapes, const void *proj,          \
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
+                       int align_corners, int64_t value_row_stride, void *stream);                  \
+    MSDA_API int msda_bwd_fused_levelref_qmasked_##SUF(const void *grad_out, const void *value,     \
+                       const uint8_t *value_mask, const uint8_t *query_mask, const int64_t *shapes, \
+                       const void *proj, const void *ref, void *grad_value, void *grad_proj,        \
+                       void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D,          \
+                       int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);
+MSDA_QUERY_MASK_PLAIN(f32) MSDA_QUERY_MASK_PLAIN(f16) MSDA_QUERY_MASK_PLAIN(bf16) MSDA_QUERY_MASK_PLAIN(f64)
+MSDA_QUERY_MASK_PLAIN(f32_vbf16) MSDA_QUERY_MASK_PLAIN(f32_vf16)
+MSDA_QUERY_MASK_FUSED(f32) MSDA_QUERY_MASK_FUSED(f16) MSDA_QUERY_MASK_FUSED(bf16) MSDA_QUERY_MASK_FUSED(f64)
+MSDA_QUERY_MASK_FUSED(f32_vbf16) MSDA_QUERY_MASK_FUSED(f32_vf16) MSDA_QUERY_MASK_FUSED(f32_sbf16) MSDA_QUERY_MASK_FUSED(f32_sf16)
+#undef MSDA_QUERY_MASK_PLAIN
+#undef MSDA_QUERY_MASK_FUSED
 
 /*
  * Bytes of device workspace msda_bwd_<dtype> wants for these sizes.  elem_size: of everything but `value`;

@@ -49,6 +49,12 @@ EXPORTED_SYMBOLS = tuple(
        "msda_last_launch_info"]
 )
 
+# ... and the query-mask entry points (has_query_mask): the _masked_ families' kernels with `query_mask` behind `value_mask`
+QUERY_MASK_SYMBOLS = tuple(
+    [f"msda_{d}_qmasked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES]
+    + [f"msda_{d}_fused_levelref_qmasked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -192,6 +198,23 @@ def load():
                 glm = getattr(lib, f"msda_bwd_fused_levelref_masked_{suf}")
                 glm.restype = ci
                 glm.argtypes = [vp] * 9 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
+        # the query-mask entry points: additions within ABI 12 (has_query_mask); the _masked_ twins' lists with `query_mask`
+        # behind `value_mask`
+        if hasattr(lib, "msda_bwd_qmasked_f32"):
+            for suf in DTYPE_SUFFIXES:
+                fq = getattr(lib, f"msda_fwd_qmasked_{suf}")
+                fq.restype = ci
+                fq.argtypes = [vp] * 7 + [i64] * 7 + [ci, ci, i64, vp]
+                gq = getattr(lib, f"msda_bwd_qmasked_{suf}")
+                gq.restype = ci
+                gq.argtypes = [vp] * 10 + [i64] * 7 + [ci, ci, i64, i64, vp, i64, vp]
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                flq = getattr(lib, f"msda_fwd_fused_levelref_qmasked_{suf}")
+                flq.restype = ci
+                flq.argtypes = [vp] * 7 + [i64] * 7 + [ci, ci, ci, i64, vp]
+                glq = getattr(lib, f"msda_bwd_fused_levelref_qmasked_{suf}")
+                glq.restype = ci
+                glq.argtypes = [vp] * 10 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -246,6 +269,13 @@ def has_value_mask() -> bool:
     ..., additions within ABI 12, found by symbol)?  Without them a masked call composes ``masked_fill`` with the unmasked
     route."""
     return hasattr(load(), "msda_bwd_masked_f32")
+
+
+def has_query_mask() -> bool:
+    """Does the loaded library have the query-mask entry points (msda_fwd_qmasked_<dtype> ...,
+    msda_fwd_fused_levelref_qmasked_<dtype> ..., additions within ABI 12, found by symbol)?  Without them a call with a
+    query mask composes ``functional.apply_query_mask`` with its route."""
+    return hasattr(load(), "msda_bwd_qmasked_f32")
 
 
 def check(rc: int, what: str) -> None:

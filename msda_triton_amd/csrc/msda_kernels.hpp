@@ -197,11 +197,31 @@ struct LevelRefParams : Params {};
 //                                never loaded); the single-launch kernel stores zeros for it
 // The fused pair for per-level reference points has its masked kernarg below the plain one, so that the grad_value passes
 // behind the fused backward run on the plain masked pipeline (value_pass_params, msda_launch.hpp).
+// ---- query padding mask (msda_*_qmasked_<dtype>, msda_*_fused_levelref_qmasked_<dtype>): hooks in the value-mask twins ----
+// `qmask` is [B, Q] bytes, non-zero = the query is real, behind `vmask`; NULL (what the _masked_ entry points pass) = every
+// query is real.  Every hook sits under `if constexpr (kValueMask<PP>)` plus a wave-uniform test of the pointer:
+//   forward / sample gradients   the wave looks its units' bytes up before phase 0 (one bit per lane, a ballot); a masked unit's
+//                                sampling inputs are never loaded, it gathers nothing and its rows are stored as zeros
+//   grad_value                   the count and place passes and the single-launch kernel's walks drop a masked query's samples
+//                                where they drop a "zeros" sample outside every cell (query_live below)
 struct MaskedParams : Params {
     const uint8_t *vmask;
+    const uint8_t *qmask;
 };
 struct LevelRefMaskedParams : MaskedParams {};
 template <typename PP> constexpr bool kValueMask = std::is_base_of<MaskedParams, PP>::value;
+// the batch element's query mask bytes (uniform), or NULL: no query mask, or a kernarg without one
+template <typename PP> __device__ __forceinline__ const uint8_t *query_mask_row(const PP &p, int b)
+{
+    if constexpr (kValueMask<PP>) return p.qmask != nullptr ? p.qmask + (size_t)b * p.Q : nullptr;
+    else return nullptr;
+}
+// is query q (inside the batch element of `qm`) real?  Constant true for a kernarg without the mask.
+template <typename PP> __device__ __forceinline__ bool query_live(const uint8_t *qm, int q)
+{
+    if constexpr (kValueMask<PP>) return qm == nullptr || qm[q] != 0;
+    else return true;
+}
 // the batch element's mask bytes as a range-checked descriptor (nothing at all in the unmasked kernels)
 template <typename PP, bool = kValueMask<PP>> struct MaskSrc {
     __device__ __forceinline__ MaskSrc(const PP &, int) {}
@@ -558,6 +578,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
     const int b = (int)fast_div((uint32_t)pair, p.div_h);
     int h = pair - b * p.H;
     [[maybe_unused]] const MaskSrc<PP> vmask(p, b);  // (value-mask twins only; two planes per workgroup share the batch element)
+    // (... and their query mask: the batch element's [Q] bytes, NULL without one; the prefetches below would request a
+    // masked query's sampling inputs, so a call with a query mask does without them)
+    [[maybe_unused]] const uint8_t *const qm = query_mask_row(p, b);
+    bool has_qm = false;
+    if constexpr (kValueMask<PP>) has_qm = qm != nullptr;
 
     const int scp = p.sc + 1;  // +1 record of padding: units land on different LDS banks
     const GatherLds<A> lds(NU, scp);
@@ -598,7 +623,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
     // rocprofv3 runs on different boxes had called it noise.)  Plain operator, one channel chunk, all L * P samples
     // parked at once, at most kPre per lane.
     constexpr int kPre = 2;
-    const bool pre = !FUSED && nchan_chunks == 1 && p.sc >= p.LP && UPW * p.LP <= kPre * kWave;
+    const bool pre = !FUSED && nchan_chunks == 1 && p.sc >= p.LP && UPW * p.LP <= kPre * kWave && !has_qm;
     Pack<T, 2> pxy[kPre];
     T pa[kPre];
     // request the sampling points and weights of the wave's units [wq, wq + UPW) (queries below qlim), one sample per
@@ -689,10 +714,25 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
         }
         const int q = wq0 + wunit;
         const bool unit_ok = q < (LDSL ? q_hi : p.Q);
+        // a query mask: which of the wave's units are real — a bit per LANE (the lane's own unit), looked up before phase 0.
+        // A masked unit's sampling inputs are never loaded, it takes no part in the gather and its rows are stored as zeros.
+        bool q_real = true;
+        [[maybe_unused]] unsigned long long qlive = ~0ull;
+        if constexpr (kValueMask<PP>) {
+            if (has_qm) {
+                q_real = unit_ok && qm[q] != 0;
+                qlive = __ballot(q_real);
+            }
+        }
+        auto unit_live = [&](int fu) -> bool {  // (unit fu of the wave: its first lane's bit)
+            if constexpr (kValueMask<PP>) return ((qlive >> (fu * G)) & 1ull) != 0;
+            else return true;
+        };
         const bool use_pre = pre && (LDSL || it == 0);
         for (int cc = 0; cc < nchan_chunks; ++cc) {
             const int c0 = (cc * G + j) * VEC;
-            const bool lane_ok = unit_ok && (c0 < p.D);
+            const bool lane_st = unit_ok && (c0 < p.D);  // the lane stores (a masked unit: the zeros its sum starts from)
+            const bool lane_ok = lane_st && q_real;
             const uint32_t lane_off = (uint32_t)c0 * (uint32_t)sizeof(TV);
             A acc[VEC];
 #pragma unroll
@@ -711,7 +751,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                         const int fu = div_small(f, sc, inv_sc);
                         const int sl = f - imul24(fu, sc);
                         const int fq = wq0 + fu;
-                        if (fq < q_end_) {
+                        if (fq < q_end_ && unit_live(fu)) {
                             [[maybe_unused]] int npts = p.P;  // per-level point counts: the count of the sample's own level
                             int l;
                             if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
@@ -753,7 +793,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                         }
                     }
                     wave_lds_sync();
-                    if (unit_ok) {
+                    if (unit_ok && q_real) {
                         A mx = -__builtin_huge_val();
                         for (int sl = j; sl < sc; sl += G) mx = fmax_t(mx, w_rec[imul24(wunit, scp) + sl].v[0]);
                         mx = group_max<G>(mx);
@@ -772,7 +812,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                     const int fu = div_small(f, sc, inv_sc);
                     const int sl = s0 + (f - imul24(fu, sc));
                     const int fq = wq0 + fu;
-                    if (fq < q_end_) {
+                    if (fq < q_end_ && unit_live(fu)) {
                         int l;
                         if constexpr (!(FUSED && kRagged<PP>)) l = lvl_of(p, sl, inv_P);
                         const int sidx = imul24(fq, HLP) + sl;
@@ -886,7 +926,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                     }
                 }
             }
-            if (lane_ok) {
+            if (lane_st) {
                 Pack<TS, VEC> o;
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) o.v[i] = SR::from_acc(acc[i]);
@@ -1087,6 +1127,15 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
     const int b = (int)fast_div((uint32_t)pair, p.div_h);
     int h = pair - b * p.H;
     [[maybe_unused]] const MaskSrc<PP> vmask(p, b);  // (value-mask twins only; two planes per workgroup share the batch element)
+    // (... and their query mask: the batch element's [Q] bytes, NULL without one; the prefetches below would request a
+    // masked query's sampling inputs, so a call with a query mask does without them.  NOT in the fused kernel with
+    // LDS-served levels: it sits at the 128-VGPR cap of its 1024-thread workgroup with 60 scalars already spilled to
+    // vector lanes, and the hook's scalars cost its 8-lane instantiation 11 vector registers of scratch — a call with a
+    // query mask takes the 256-thread fused kernel instead, msda_launch.hpp)
+    constexpr bool kQueryHook = kValueMask<PP> && !(LDSL && FUSED);
+    [[maybe_unused]] const uint8_t *const qm = query_mask_row(p, b);
+    bool has_qm = false;
+    if constexpr (kQueryHook) has_qm = qm != nullptr;
 
     const int scp = p.sc + 1;
     // record in : {dx, dy, a*sx*gx_on, a*sy*gy_on};  record out (same slot): {gA, gX, gY, -}
@@ -1126,11 +1175,11 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
     // the workgroup's first chunk of samples requested before the level table is waited for, as in the forward
     constexpr int kPre = 2;
     // (not with LDS-served levels: the wave does not know its first queries before the staging barrier)
-    const bool pre = !FUSED && !LDSL && p.sc >= p.LP && UPW * p.LP <= kPre * kWave;
+    const bool pre = !FUSED && !LDSL && p.sc >= p.LP && UPW * p.LP <= kPre * kWave && !has_qm;
     // LDSL: the next slice's points and weights go to the wave's LDS staging area instead (dma_dword: no registers)
     constexpr bool kDma = LDSL && !FUSED && sizeof(T) == 4;
     // (two planes per workgroup: the staging areas do not fit next to two copies of the levels)
-    const bool pre_dma = kDma && !two && p.sc >= p.LP && UPW * p.LP <= kStagePre * kWave;
+    const bool pre_dma = kDma && !two && p.sc >= p.LP && UPW * p.LP <= kStagePre * kWave && !has_qm;
     const size_t rec_bytes = kGatherLdsFixed + (size_t)NU * (p.sc + 1) * (sizeof(uint4) + sizeof(Rec4<A>) + (FUSED ? 3 * sizeof(A) : 0));
     const uint32_t stage_lds = __builtin_amdgcn_readfirstlane((uint32_t)rec_bytes + (uint32_t)(threadIdx.x / kWave) * kStageWaveBytes);
     // (M0 wants the absolute LDS address: the dynamic area starts behind any static __shared__ object)
@@ -1217,7 +1266,36 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
             if (wq0 >= p.Q) break;
         }
         const int q = wq0 + wunit;
-        const bool unit_ok = q < (LDSL ? q_hi : p.Q);
+        bool unit_ok = q < (LDSL ? q_hi : p.Q);
+        // a query mask: which of the wave's units are real — a bit per LANE (the lane's own unit), looked up before phase 0.
+        // A masked unit stores its rows of zeros here and is out of the slice from then on, like a unit beyond the last
+        // query: its sampling inputs are never loaded, nothing is parked for grad_value (whose passes drop its samples).
+        [[maybe_unused]] unsigned long long qlive = ~0ull;
+        if constexpr (kQueryHook) {
+            if (has_qm) {
+                const bool real = unit_ok && qm[q] != 0;
+                if (unit_ok && !real) {
+                    const size_t u0 = plane_s0 + (size_t)imul24(q, HLP);  // the unit's first sample
+                    if constexpr (FUSED) {
+                        TS *gp = static_cast<TS *>(p.grad_loc) + 3 * u0;
+                        for (int e = j; e < 3 * p.LP; e += G) gp[e] = SR::from_acc((A)0);
+                        const int npart = kLevelRef<PP> ? p.L * p.ref_dim : p.ref_dim;  // the unit's reference-point partials
+                        T *gr = static_cast<T *>(p.grad_attn) + ((size_t)(b * (size_t)p.Q + q) * p.H + h) * npart;
+                        for (int e = j; e < npart; e += G) gr[e] = TR::from_acc((A)0);
+                    } else {
+                        T *ga = static_cast<T *>(p.grad_attn) + u0, *gl = static_cast<T *>(p.grad_loc) + 2 * u0;
+                        for (int e = j; e < p.LP; e += G) ga[e] = TR::from_acc((A)0);
+                        for (int e = j; e < 2 * p.LP; e += G) gl[e] = TR::from_acc((A)0);
+                    }
+                }
+                unit_ok = real;
+                qlive = __ballot(real);
+            }
+        }
+        auto unit_live = [&](int fu) -> bool {  // (unit fu of the wave: its first lane's bit)
+            if constexpr (kQueryHook) return ((qlive >> (fu * G)) & 1ull) != 0;
+            else return true;
+        };
         const bool use_pre = pre && it == 0;
         for (int s0 = 0; s0 < p.LP; s0 += p.sc) {
             const int sc = min(p.sc, p.LP - s0);
@@ -1231,7 +1309,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     const int fu = div_small(f, sc, inv_sc);
                     const int sl = f - imul24(fu, sc);
                     const int fq = wq0 + fu;
-                    if (fq < q_end_) {
+                    if (fq < q_end_ && unit_live(fu)) {
                         [[maybe_unused]] int npts = p.P;  // per-level point counts: the count of the sample's own level
                         int l;
                         if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
@@ -1311,7 +1389,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                 const int fu = div_small(f, sc, inv_sc);
                 const int sl = s0 + (f - imul24(fu, sc));
                 const int fq = wq0 + fu;
-                if (fq < q_end_) {
+                if (fq < q_end_ && unit_live(fu)) {
                     int l;
                     if constexpr (FUSED && kRagged<PP>) l = (int)w_rec[imul24(fu, scp) + (sl - s0)].v[3];  // (parked by phase 0)
                     else l = lvl_of(p, sl, inv_P);
@@ -1724,7 +1802,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                 const int fu = div_small(f, sc, inv_sc);
                 const int sl = s0 + (f - imul24(fu, sc));
                 const int fq = wq0 + fu;
-                if (fq < q_end_) {
+                if (fq < q_end_ && unit_live(fu)) {
                     const int sidx = imul24(fq, HLP) + sl;
                     const Rec4<A> res = w_rec[imul24(fu, scp) + (sl - s0)];
                     if constexpr (FUSED) {

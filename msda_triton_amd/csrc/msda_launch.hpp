@@ -412,6 +412,10 @@ template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T, ty
     return (int)hipGetLastError();
 }
 
+// does this call carry a query mask (MaskedParams::qmask)?
+inline bool has_query_mask(const MaskedParams &p) { return p.qmask != nullptr; }
+inline bool has_query_mask(const Params &) { return false; }
+
 template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T, typename PP = Params> inline int launch_gather(PP &p, hipStream_t stream)
 {
     using A = typename Traits<T>::acc;
@@ -470,7 +474,10 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         // (fp32 arithmetic; the rows may be 16-bit — the mixed-storage and module-storage kernels: 8-byte pieces, half the LDS)
         const LdsLevelsPlan pl = lds_levels_plan_rt(p, G, sizeof(A), sizeof(TV), MODE == 3, MODE == 1, /*two planes*/ MODE != 1);
         // (not the plain sample-gradient kernel: it would give up its LDS-DMA prefetch for them — 92.9 against 92.7 us, a draw)
-        if (pl.use && (MODE < 2 || pl.sc == p.LP)) return launch_gather_lds<T, VEC, G, MODE, TV, TS, PP>(p, pl, stream);
+        // (a query mask: the fused sample-gradient kernel with LDS-served levels has no hook for it — at its register cap,
+        // msda_kernels.hpp — so such a call takes the 256-thread kernel below)
+        if (pl.use && (MODE < 2 || pl.sc == p.LP) && !(MODE == 3 && has_query_mask(p)))
+            return launch_gather_lds<T, VEC, G, MODE, TV, TS, PP>(p, pl, stream);
     }
     size_t lds;
     plan_gather(NU, p.LP, sizeof(A), p.sc, lds, MODE == 3);
@@ -629,11 +636,10 @@ template <typename T> inline bool value_vec_ok(const Params &p)
     return aligned_to(p.grad_out, 16) && aligned_to(p.grad_value, 16) && (p.D % VECF) == 0;
 }
 
-template <typename T, typename TV = T, typename TS = T, typename PP = Params> inline int run_value_sorted(PP &p, const Dims &d, void *workspace, hipStream_t stream)
+// KP: the kernarg type the count and place passes are instantiated on (run_value_sorted below picks it)
+template <typename T, typename TV, typename TS, typename PP, typename KP> inline int run_value_sorted_on(PP &p, const Dims &d, void *workspace, hipStream_t stream)
 {
     using A = typename Traits<T>::acc;
-    // the count / scan / place / gather passes know no mask: a value-mask call runs the unmasked kernels on its Params part
-    using KP = std::conditional_t<kValueMask<PP>, Params, PP>;
     const bool vec_ok = value_vec_ok<T>(p);
     const SortedWsLayout w = sorted_ws_layout(d.B, d.I, d.H, d.D, d.Q, d.L, samples(d), sizeof(A), sizeof(T), vec_ok, p.ent_alt0 != nullptr, sizeof(TV));
     unsigned char *ws = static_cast<unsigned char *>(workspace);
@@ -768,6 +774,19 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     return 0;
 }
 
+// The scan / gather passes know no mask, and neither do the count / place passes of a value-mask call: it runs the unmasked
+// kernels on its Params part.  A QUERY mask (MaskedParams::qmask, msda_*_qmasked_*) is the count and place passes' business —
+// they drop the masked queries' samples — so such a call, and only such a call, launches their MaskedParams instantiations.
+template <typename T, typename TV = T, typename TS = T, typename PP = Params> inline int run_value_sorted(PP &p, const Dims &d, void *workspace, hipStream_t stream)
+{
+    if constexpr (kValueMask<PP>) {
+        if (p.qmask != nullptr) return run_value_sorted_on<T, TV, TS, PP, MaskedParams>(p, d, workspace, stream);
+        return run_value_sorted_on<T, TV, TS, PP, Params>(p, d, workspace, stream);
+    } else {
+        return run_value_sorted_on<T, TV, TS, PP, PP>(p, d, workspace, stream);
+    }
+}
+
 // Params::v_row: bytes between consecutive pixels' rows of `value` — the caller's `value_row_stride` argument, 0 = dense
 // (H * D * sizeof).  A caller that owns the layout pads every pixel's rows by one 128-byte line (HISTORY.md 4 item 5: the vector
 // L1 picks its tag RAM from the low bits of the line index; rows exactly 1 KB apart leave one head on half of them).
@@ -861,10 +880,19 @@ inline void fill_box_scales(HfBoxParams &p, const float *lscale, double off_scal
 inline void fill_box_scales(Params &, const float *, double, int64_t) {}
 // the value padding mask (msda_*_masked_<dtype>): [B, I] bytes behind the kernarg; advanced with every other batch-indexed
 // pointer when the grad_value pipeline runs once per group of batch elements
-inline void set_value_mask(MaskedParams &p, const uint8_t *vmask) { p.vmask = vmask; }
-inline void set_value_mask(Params &, const uint8_t *) {}
-inline void advance_value_mask(MaskedParams &pg, const MaskedParams &p, size_t pixels) { pg.vmask = p.vmask + pixels; }
-inline void advance_value_mask(Params &, const Params &, size_t) {}
+// ... and the query padding mask behind it (msda_*_qmasked_<dtype>): [B, Q] bytes, NULL from the _masked_ entry points
+inline void set_value_mask(MaskedParams &p, const uint8_t *vmask, const uint8_t *qmask)
+{
+    p.vmask = vmask;
+    p.qmask = qmask;
+}
+inline void set_value_mask(Params &, const uint8_t *, const uint8_t *) {}
+inline void advance_value_mask(MaskedParams &pg, const MaskedParams &p, size_t pixels, size_t queries)
+{
+    pg.vmask = p.vmask + pixels;
+    pg.qmask = p.qmask != nullptr ? p.qmask + queries : nullptr;
+}
+inline void advance_value_mask(Params &, const Params &, size_t, size_t) {}
 
 // ---- discrete (nearest-pixel) sampling: msda_{fwd,bwd}_discrete_<dtype>, kernels in msda_discrete.hpp ----
 // MODE 0: the forward, 1: the attention-weight gradient.  G lanes per unit from D as everywhere (pick_group); the
@@ -918,6 +946,7 @@ struct Call {
     // device buffers: the sampling operators' loc / attn and their gradients, the fused operators' proj / ref and theirs
     const void *grad_out = nullptr, *value = nullptr;
     const uint8_t *value_mask = nullptr;  // the masked twins: [B, I] bytes
+    const uint8_t *query_mask = nullptr;  // ... and their query-mask entry points: [B, Q] bytes
     const int64_t *shapes = nullptr;
     const void *loc = nullptr, *attn = nullptr, *proj = nullptr, *ref = nullptr;
     void *out = nullptr, *grad_value = nullptr, *grad_loc = nullptr, *grad_attn = nullptr, *grad_proj = nullptr,
@@ -968,7 +997,7 @@ template <typename TV, typename PP> inline int fill_kernarg(PP &p, const Call &c
     fill_params(p, d, c.padding_mode, c.align_corners);
     fill_level_starts(p, c.points_per_level, d.L);
     fill_box_scales(p, c.level_scale, c.offset_scale, d.L);
-    set_value_mask(p, c.value_mask);
+    set_value_mask(p, c.value_mask, c.query_mask);
     p.ref = c.ref;
     p.ref_dim = c.ref_dim;
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
@@ -1191,7 +1220,7 @@ inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_by
             pg.attn = static_cast<const unsigned char *>(p.attn) + ns0 * sizeof(T);
             pg.grad_out = static_cast<const unsigned char *>(p.grad_out) + (size_t)(b0 * Q * H * D) * sizeof(TS);
             pg.grad_value = static_cast<unsigned char *>(p.grad_value) + (size_t)(b0 * I * H * D) * sizeof(TV);
-            advance_value_mask(pg, p, (size_t)(b0 * I));
+            advance_value_mask(pg, p, (size_t)(b0 * I), (size_t)(b0 * Q));
             if (p.ent_alt0 != nullptr) {  // this group's own share of the caller's gradient buffers (run_bwd)
                 pg.ent_alt0 = static_cast<unsigned char *>(p.ent_alt0) + ns0 * 2 * sizeof(T);
                 pg.ent_alt1 = static_cast<unsigned char *>(p.ent_alt1) + ns0 * sizeof(T);
@@ -1510,9 +1539,11 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         return msda::run_bwd<T, TV, msda::DiscreteParams>(c);                                                    \
     }                                                                                                            \
     MSDA_DEFINE_MASKED_ENTRY_POINTS(SUF, T, TV)                                                                   \
+    MSDA_DEFINE_QMASKED_ENTRY_POINTS(SUF, T, TV)                                                                  \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)                                                          \
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, T)                                                        \
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TV, T)                                                 \
+    MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TV, T)                                                \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
@@ -1539,6 +1570,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)                                                         \
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)                                                       \
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TS, TS)                                                \
+    MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TS, TS)                                               \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)
 
 // the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
@@ -1669,6 +1701,65 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     {                                                                                                            \
         MSDA_MASK_REQUIRED("msda_bwd_fused_levelref_masked")                                                     \
         MSDA_TAKE_BWD_FUSED c.P = P; c.value_mask = value_mask;                                                  \
+        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(c);                                    \
+    }
+
+// the query-mask entry points: msda_{fwd,bwd}_qmasked_<suffix> and msda_{fwd,bwd}_fused_levelref_qmasked_<suffix> — the
+// _masked_ twins' argument lists with `query_mask` ([B, Q] bytes, non-zero = real query) behind `value_mask`, on the twins'
+// kernels (MaskedParams::qmask).  Both masks are required: a null one is an argument error, refused before any other
+// argument is looked at (a caller without a value mask passes all ones).
+#define MSDA_BOTH_MASKS_REQUIRED(NAME)                                                                           \
+    if (value_mask == nullptr || query_mask == nullptr) {                                                        \
+        msda::set_error(NAME ": %s is null (both masks are required; all ones for a mask the caller does not have)", \
+                        value_mask == nullptr ? "value_mask" : "query_mask");                                    \
+        return MSDA_ERR_BAD_ARG;                                                                                 \
+    }
+#define MSDA_DEFINE_QMASKED_ENTRY_POINTS(SUF, T, TV)                                                             \
+    extern "C" int msda_fwd_qmasked_##SUF(const void *value, const uint8_t *value_mask, const uint8_t *query_mask, \
+                                          const int64_t *shapes, const void *loc, const void *attn, void *out,   \
+                                          int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,      \
+                                          int64_t P, int padding_mode, int align_corners,                        \
+                                          int64_t value_row_stride, void *stream)                                \
+    {                                                                                                            \
+        MSDA_BOTH_MASKS_REQUIRED("msda_fwd_qmasked")                                                             \
+        MSDA_TAKE_FWD MSDA_TAKE_MODES c.P = P; c.value_mask = value_mask; c.query_mask = query_mask;             \
+        return msda::run_fwd<T, TV, msda::MaskedParams>(c);                                                      \
+    }                                                                                                            \
+    extern "C" int msda_bwd_qmasked_##SUF(const void *grad_out, const void *value, const uint8_t *value_mask,   \
+                                          const uint8_t *query_mask, const int64_t *shapes, const void *loc,     \
+                                          const void *attn, void *grad_value, void *grad_loc, void *grad_attn,   \
+                                          int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,      \
+                                          int64_t P, int padding_mode, int align_corners,                        \
+                                          int64_t max_level_cells, int64_t value_row_stride, void *workspace,    \
+                                          int64_t workspace_bytes, void *stream)                                 \
+    {                                                                                                            \
+        MSDA_BOTH_MASKS_REQUIRED("msda_bwd_qmasked")                                                             \
+        MSDA_TAKE_BWD MSDA_TAKE_MODES c.grad_loc = grad_loc; c.P = P; c.value_mask = value_mask;                 \
+        c.query_mask = query_mask;                                                                               \
+        return msda::run_bwd<T, TV, msda::MaskedParams>(c);                                                      \
+    }
+#define MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TV, TS)                                           \
+    extern "C" int msda_fwd_fused_levelref_qmasked_##SUF(const void *value, const uint8_t *value_mask,          \
+                                                         const uint8_t *query_mask, const int64_t *shapes,       \
+                                                         const void *proj, const void *ref, void *out, int64_t B, \
+                                                         int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,  \
+                                                         int64_t P, int ref_dim, int padding_mode,               \
+                                                         int align_corners, int64_t value_row_stride,            \
+                                                         void *stream)                                           \
+    {                                                                                                            \
+        MSDA_BOTH_MASKS_REQUIRED("msda_fwd_fused_levelref_qmasked")                                              \
+        MSDA_TAKE_FWD_FUSED c.P = P; c.value_mask = value_mask; c.query_mask = query_mask;                       \
+        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(c);                                    \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_levelref_qmasked_##SUF(                                                        \
+        const void *grad_out, const void *value, const uint8_t *value_mask, const uint8_t *query_mask,          \
+        const int64_t *shapes, const void *proj, const void *ref, void *grad_value, void *grad_proj,             \
+        void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P,     \
+        int ref_dim, int padding_mode, int align_corners, int64_t max_level_cells, int64_t value_row_stride,     \
+        void *workspace, int64_t workspace_bytes, void *stream)                                                  \
+    {                                                                                                            \
+        MSDA_BOTH_MASKS_REQUIRED("msda_bwd_fused_levelref_qmasked")                                              \
+        MSDA_TAKE_BWD_FUSED c.P = P; c.value_mask = value_mask; c.query_mask = query_mask;                       \
         return msda::run_bwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(c);                                    \
     }
 

@@ -58,6 +58,9 @@ template <typename T, int TB, typename PP = Params> __global__ __launch_bounds__
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
     const T *attn = static_cast<const T *>(p.attn) + plane_s0;
     const int HLP = p.H * p.LP, sl = lvl_start(p, l, l * p.P) + pt;
+    // PP = MaskedParams (launched for a call with a query mask only): a masked query's samples are never loaded and never
+    // placed — the count pass dropped them by the same test
+    [[maybe_unused]] const uint8_t *const qm = query_mask_row(p, b);
 
     // ---- level geometry: scalar loads (uniform addresses), as load_level_table computes it ----
     int lh = 0, lw = 0, cs = 0, ps = 0, plane_nc = 0;
@@ -111,11 +114,19 @@ template <typename T, int TB, typename PP = Params> __global__ __launch_bounds__
                 Pack<T, 2> xy[NS];
                 T at[NS];
                 unsigned rel[NS];
+                [[maybe_unused]] unsigned live = 0;  // (query mask: bit j — sample j's query is real)
 #pragma unroll
                 for (int j = 0; j < NS; ++j) {
                     const int q = q0 + j * dq;
                     xy[j].v[0] = xy[j].v[1] = at[j] = TR::from_acc((A)0);
-                    if (active && q < qb) {
+                    if constexpr (kValueMask<PP>) {  // the query's byte first, its sample only when it is real
+                        if (active && q < qb && query_live<PP>(qm, q)) {
+                            live |= 1u << j;
+                            const int sidx = q * HLP + sl;
+                            xy[j] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx);
+                            at[j] = attn[sidx];
+                        }
+                    } else if (active && q < qb) {
                         const int sidx = q * HLP + sl;
                         xy[j] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx);
                         at[j] = attn[sidx];
@@ -128,7 +139,12 @@ template <typename T, int TB, typename PP = Params> __global__ __launch_bounds__
                     uint32_t cellw;
                     A dx, dy;
                     rel[j] = 0xFFFFFFFFu;
-                    if (active && q < qb && cell_of<A>(p, TR::to_acc(xy[j].v[0]), TR::to_acc(xy[j].v[1]), lh, lw, 0, ps, l, cell, cellw, dx, dy)) {
+                    if constexpr (kValueMask<PP>) {
+                        if (((live >> j) & 1u) != 0 && cell_of<A>(p, TR::to_acc(xy[j].v[0]), TR::to_acc(xy[j].v[1]), lh, lw, 0, ps, l, cell, cellw, dx, dy)) {
+                            const unsigned rr = (unsigned)(cell - c0);
+                            if (rr < (unsigned)n) rel[j] = rr;
+                        }
+                    } else if (active && q < qb && cell_of<A>(p, TR::to_acc(xy[j].v[0]), TR::to_acc(xy[j].v[1]), lh, lw, 0, ps, l, cell, cellw, dx, dy)) {
                         const unsigned rr = (unsigned)(cell - c0);
                         if (rr < (unsigned)n) rel[j] = rr;
                     }

@@ -74,6 +74,9 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
     const T *attn = static_cast<const T *>(p.attn) + plane_s0;
     const int HLP = p.H * p.LP;
+    // the value-mask twin with a query mask: a masked query's samples are skipped wherever they are walked — never loaded,
+    // never counted, never placed (its byte is looked up again at each walk: nothing is kept in registers for it)
+    [[maybe_unused]] const uint8_t *const qm = query_mask_row(p, b);
     // the level's points and its first sample (uniform: P and lvl * P; per-level counts: P_l and the level's start)
     const int lP = lvl_points(p, lvl), lS = lvl_start(p, lvl, lvl * p.P);
     const int dq = lP <= kSmallBlock ? kSmallBlock / lP : 1;
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
     for (int k = 0; k < kPre; ++k) {
         pre_xy[k].v[0] = pre_xy[k].v[1] = pre_a[k] = TR::from_acc((A)0);
         const int q = q0 + k * dq;
-        if (pre && q < p.Q) {
+        if (pre && q < p.Q && query_live<PP>(qm, q)) {
             const int sidx = q * HLP + lS + pt;
             pre_xy[k] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx);
             pre_a[k] = attn[sidx];
@@ -147,15 +150,17 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
         if (pre) {
 #pragma unroll
             for (int k = 0; k < kPre; ++k)
-                if (q0 + k * dq < p.Q) one(q0 + k * dq, pre_xy[k], pre_a[k]);
+                if (q0 + k * dq < p.Q && query_live<PP>(qm, q0 + k * dq)) one(q0 + k * dq, pre_xy[k], pre_a[k]);
         } else if (active) {
             for (int q = q0; q < p.Q; q += dq) {
+                if (!query_live<PP>(qm, q)) continue;
                 const int sidx = q * HLP + lS + pt;
                 one(q, *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx), attn[sidx]);
             }
         } else if (lP > kSmallBlock) {
             for (int q = 0; q < p.Q; ++q)
                 for (int pp = tid; pp < lP; pp += kSmallBlock) {
+                    if (!query_live<PP>(qm, q)) continue;
                     const int sidx = q * HLP + lS + pp;
                     one(q, *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * sidx), attn[sidx]);
                 }
@@ -233,7 +238,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
         if (lP <= kSmallBlock && (p.Q + dq - 1) / dq <= kPre) {  // (uniform) the prefetched samples: one batch
             int qs[kPre];
 #pragma unroll
-            for (int k = 0; k < kPre; ++k) qs[k] = pre && q0 + k * dq < p.Q ? q0 + k * dq : -1;
+            for (int k = 0; k < kPre; ++k) qs[k] = pre && q0 + k * dq < p.Q && query_live<PP>(qm, q0 + k * dq) ? q0 + k * dq : -1;
             batch(wid, std::integral_constant<int, kPre>{}, qs, pre_xy, pre_a);
         } else if (lP <= kSmallBlock) {
             const int rounds = (p.Q + kPre * dq - 1) / (kPre * dq);
@@ -244,7 +249,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
 #pragma unroll
                 for (int k = 0; k < kPre; ++k) {
                     const int q = q0 + (r * kPre + k) * dq;
-                    qs[k] = active && q < p.Q ? q : -1;
+                    qs[k] = active && q < p.Q && query_live<PP>(qm, q) ? q : -1;
                     xys[k].v[0] = xys[k].v[1] = ats[k] = TR::from_acc((A)0);
                     if (qs[k] >= 0) {
                         const int sidx = q * HLP + lS + pt;
@@ -259,7 +264,7 @@ __global__ __launch_bounds__(kSmallBlock) void msda_value_small_kernel(const PP 
             for (int q = 0; q < p.Q; ++q)
                 for (int pp0 = 0; pp0 < lP; pp0 += kSmallBlock, ++it) {
                     const int pp = pp0 + tid;
-                    int qs[1] = {pp < lP ? q : -1};
+                    int qs[1] = {pp < lP && query_live<PP>(qm, q) ? q : -1};
                     Pack<T, 2> xys[1];
                     T ats[1];
                     xys[0].v[0] = xys[0].v[1] = ats[0] = TR::from_acc((A)0);

@@ -220,6 +220,9 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const PP p)
     const T *attn = static_cast<const T *>(p.attn) + plane_s0;
     const int HLP = p.H * p.LP;
     const int tid = threadIdx.x;
+    // PP = MaskedParams (launched for a call with a query mask only): a masked query's samples are dropped where a "zeros"
+    // sample outside every cell is — never loaded, never visited, by the count and the place pass alike
+    [[maybe_unused]] const uint8_t *const qm = query_mask_row(p, b);
 
     // fixed slot per thread: with LPt (level, point) slots in play, threads [0, dq * LPt) are active; thread t serves
     // slot t % LPt of the queries qa + t / LPt + k * dq.  (More slots than threads: each thread strides over the
@@ -269,7 +272,44 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const PP p)
             int q = qa + tq;
             int sidx = q * HLP + sl0;
             const int d_sidx = dq * HLP;
-            if constexpr (!PLACE) {
+            if constexpr (kValueMask<PP>) {
+                // the query-mask walk, count and place alike: a query's byte first, its sample only when it is real — two
+                // queries' bytes and samples in flight per thread
+                constexpr int RING = 2;
+                Pack<T, 2> ring[RING];
+                T ring_a[RING];
+                bool live[RING];
+#pragma unroll
+                for (int k = 0; k < RING; ++k) {
+                    ring[k].v[0] = ring[k].v[1] = ring_a[k] = TR::from_acc((A)0);
+                    live[k] = q + k * dq < qb && query_live<PP>(qm, q + k * dq);
+                    if (live[k]) {
+                        ring[k] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * (sidx + k * d_sidx));
+                        if constexpr (PLACE) ring_a[k] = attn[sidx + k * d_sidx];
+                    }
+                }
+                while (q < qb) {
+#pragma unroll
+                    for (int k = 0; k < RING; ++k) {
+                        const Pack<T, 2> xy = ring[k];
+                        const T at = ring_a[k];
+                        const bool lk = live[k];
+                        const int qk = q + k * dq;
+                        live[k] = qk + RING * dq < qb && query_live<PP>(qm, qk + RING * dq);
+                        if (live[k]) {
+                            ring[k] = *reinterpret_cast<const Pack<T, 2> *>(loc + 2 * (sidx + (k + RING) * d_sidx));
+                            if constexpr (PLACE) ring_a[k] = attn[sidx + (k + RING) * d_sidx];
+                        }
+                        int cell;
+                        uint32_t cellw;
+                        A dx, dy;
+                        if (lk && cell_of<A>(p, TR::to_acc(xy.v[0]), TR::to_acc(xy.v[1]), lh, lw, cs, ps, l, cell, cellw, dx, dy))
+                            visit(qk, cell, cellw, dx, dy, PLACE ? TR::to_acc(at) : (A)0);
+                    }
+                    q += RING * dq;
+                    sidx += RING * d_sidx;
+                }
+            } else if constexpr (!PLACE) {
                 // four samples in flight per thread (static ring): the walk is latency-bound, nothing is stored here
                 constexpr int RING = 4;
                 Pack<T, 2> ring[RING];
@@ -325,6 +365,9 @@ __global__ __launch_bounds__(kCellBlock) void msda_cell_pass_kernel(const PP p)
             }
         } else if (!fixed) {
             for (int q = qa; q < qb; ++q) {
+                if constexpr (kValueMask<PP>) {
+                    if (!query_live<PP>(qm, q)) continue;  // (uniform)
+                }
                 for (int sl = tid; sl < p.LP; sl += kCellBlock) {
                     const int l = kRagged<PP> ? lvl_of(p, sl, 0.0f) : sl / p.P;
                     const int sidx = q * HLP + sl;

@@ -130,6 +130,7 @@ def sharded_multiscale_deformable_attention(
     num_queries: Optional[int] = None,
     grad_sync: Literal["slice", "reduce_scatter"] = "slice",
     value_mask: Optional[torch.Tensor] = None,
+    query_mask: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Query-sharded operator; returns the full ``[B, Q, H, D]`` output on every rank.
 
@@ -138,12 +139,17 @@ def sharded_multiscale_deformable_attention(
     ``inputs_are_sharded=True``: they already hold only this rank's slice (``num_queries`` = global
     Q is then required, and every rank's slice must have the ceil-sized shard length except that
     trailing ranks may be shorter).
-    ``img`` is the full value pyramid on every rank.  ``value_mask`` is not served here: anything but None raises.
+    ``img`` is the full value pyramid on every rank.  ``value_mask`` and ``query_mask`` are not served here: anything but
+    None raises.
     """
     if value_mask is not None:
         raise ValueError("the sharded operators take no `value_mask`: apply it to the pyramid first "
                          "(`msda_triton_amd.functional.apply_value_mask(img, value_mask)`, i.e. masked_fill) — silently "
                          "ignoring it would sample the padding pixels")
+    if query_mask is not None:
+        raise ValueError("the sharded operators take no `query_mask`: sanitise the sampling inputs and zero the result's "
+                         "rows yourself (`msda_triton_amd.functional.apply_query_mask`) — silently ignoring it would "
+                         "let the padded queries' inputs into the pyramid's gradient")
     if not (dist.is_available() and dist.is_initialized()):
         raise RuntimeError("torch.distributed is not initialised; call init_process_group first")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -491,6 +497,7 @@ def row_sharded_multiscale_deformable_attention(
     compute_only_as: Optional[Tuple[int, int]] = None,
     loopback: bool = False,
     value_mask: Optional[torch.Tensor] = None,
+    query_mask: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Row-sharded operator; returns the full ``[B, Q, H, D]`` output on every rank.
 
@@ -512,12 +519,16 @@ def row_sharded_multiscale_deformable_attention(
     replicated and each rank computes its :func:`row_shard_bounds` rows.
     ``inputs_are_sharded=True``: they hold only this rank's rows, flattened: ``[rows, H, L, P, 2]`` /
     ``[rows, H, L, P]`` (``num_queries`` = Q per batch element is then required).
-    ``value_mask`` is not served here: anything but None raises.
+    ``value_mask`` and ``query_mask`` are not served here: anything but None raises.
     """
     if value_mask is not None:
         raise ValueError("the sharded operators take no `value_mask`: apply it to the pyramid first "
                          "(`msda_triton_amd.functional.apply_value_mask(img, value_mask)`, i.e. masked_fill) — silently "
                          "ignoring it would sample the padding pixels")
+    if query_mask is not None:
+        raise ValueError("the sharded operators take no `query_mask`: sanitise the sampling inputs and zero the result's "
+                         "rows yourself (`msda_triton_amd.functional.apply_query_mask`) — silently ignoring it would "
+                         "let the padded queries' inputs into the pyramid's gradient")
     if grad_value_sync not in ("all_reduce", "owners", "none"):
         raise ValueError(f"unknown grad_value_sync {grad_value_sync!r}")
     if grad_sync not in ("slice", "reduce_scatter"):

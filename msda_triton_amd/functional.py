@@ -213,6 +213,72 @@ def apply_value_mask(img: torch.Tensor, value_mask: Optional[torch.Tensor]) -> t
     return img.masked_fill(padding[:, :, None, None], 0)
 
 
+def _validate_query_mask(query_mask: torch.Tensor, per_query: torch.Tensor) -> None:
+    """``per_query``: any tensor whose two leading dims are (batch, num_queries) — the sampling points, the projection."""
+    if not torch.is_tensor(query_mask) or query_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"`query_mask` should be a bool or uint8 tensor, but got "
+                         f"{query_mask.dtype if torch.is_tensor(query_mask) else type(query_mask).__name__}.")
+    if query_mask.dim() != 2 or per_query.dim() < 2 or tuple(query_mask.shape) != tuple(per_query.shape[:2]):
+        raise ValueError(f"`query_mask` should be [{per_query.shape[0] if per_query.dim() else '?'}, "
+                         f"{per_query.shape[1] if per_query.dim() > 1 else '?'}] (a flag per query), but got "
+                         f"{tuple(query_mask.shape)}.")
+    if query_mask.device != per_query.device:
+        raise ValueError(f"`query_mask` should be on the queries' device {per_query.device}, but got {query_mask.device}.")
+
+
+def check_query_mask(query_mask: torch.Tensor, per_query: torch.Tensor) -> torch.Tensor:
+    """``query_mask``: ``[B, Q]``, bool or uint8, on the device of ``per_query`` (a ``[B, Q, ...]`` tensor) — non-zero = the
+    query is real, the polarity and dtype handling of :func:`check_value_mask`.  Returns it as the kernels take it:
+    contiguous uint8 (a bool mask as its uint8 view, without a copy)."""
+    _validate_query_mask(query_mask, per_query)
+    query_mask = query_mask.contiguous()
+    return query_mask.view(torch.uint8) if query_mask.dtype == torch.bool else query_mask
+
+
+def apply_query_mask(per_query: torch.Tensor, query_mask: Optional[torch.Tensor], fill: float = 0.0) -> torch.Tensor:
+    """``where(query_mask, per_query, fill)`` over everything behind the two leading (batch, query) dims — the
+    composition every route without query-mask kernels uses, and the definition of ``query_mask`` on host tensors:
+
+    * the masked queries' INPUTS are sanitised: sampling points (or reference points) to ``fill=0.5``, attention weights,
+      logits and offsets to 0 — whatever bits they held (NaN, Inf) are gone before anything is computed;
+    * the masked rows of ``out`` are zeroed (``fill=0``).
+
+    ``where`` routes gradients by selection, never by multiplication, so autograd gives the masked queries' inputs zero
+    gradients and keeps a non-finite ``grad_out`` row of theirs out of ``grad_value``.  ``per_query`` itself without a
+    mask."""
+    if query_mask is None:
+        return per_query
+    _validate_query_mask(query_mask, per_query)
+    real = query_mask if query_mask.dtype == torch.bool else query_mask != 0
+    real = real.reshape(real.shape + (1,) * (per_query.dim() - 2))
+    return torch.where(real, per_query, torch.full((), fill, dtype=per_query.dtype, device=per_query.device))
+
+
+_ONES_MASKS: dict = {}  # (B, I, device) -> all-ones uint8 [B, I]: the value mask of a call that has a query mask only
+
+
+def _ones_value_mask(img: torch.Tensor) -> torch.Tensor:
+    key = (img.shape[0], img.shape[1], img.device)
+    ones = _ONES_MASKS.get(key)
+    if ones is None:
+        ones = _ONES_MASKS[key] = torch.ones(key[:2], dtype=torch.uint8, device=img.device)
+    return ones
+
+
+def _mask_args(name: str, value_mask, query_mask, img, per_query):
+    """Entry-point family and leading mask pointers of a launcher call: ``name`` itself without a mask, its ``_masked``
+    twin with a value mask, ``_qmasked`` with a query mask (both masks required there: all ones for a missing value mask).
+    The tensors are returned too — the caller keeps them alive across the launch."""
+    if query_mask is not None:
+        value_mask = check_value_mask(value_mask, img) if value_mask is not None else _ones_value_mask(img)
+        query_mask = check_query_mask(query_mask, per_query)
+        return name + "_qmasked", (value_mask.data_ptr(), query_mask.data_ptr()), (value_mask, query_mask)
+    if value_mask is not None:
+        value_mask = check_value_mask(value_mask, img)
+        return name + "_masked", (value_mask.data_ptr(),), (value_mask,)
+    return name, (), ()
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _FUSED_LP_LIMIT: dict = {}  # (D, element size) -> msda_fused_lp_limit
 _WS_BYTES: dict = {}  # (B, I, H, D, Q, L, P, elem, option epoch) -> msda_bwd_workspace_bytes
@@ -296,14 +362,14 @@ class KernelTimer:
 # launcher pair — the native seam (reference: kernels.py:351-379, 556-592)
 # ------------------------------------------------------------------------------------------
 def msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners,
-                 out: Optional[torch.Tensor] = None, value_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, value_mask: Optional[torch.Tensor] = None,
+                 query_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Allocate ``out`` (or write into the caller's contiguous ``[B, Q, H, D]`` buffer, e.g. a slice of a gather
     buffer) and enqueue the forward kernel on the current stream (no host sync).  ``value_mask``: the value-mask twin
-    (``msda_fwd_masked_<dtype>``; :func:`check_value_mask`)."""
+    (``msda_fwd_masked_<dtype>``; :func:`check_value_mask`).  ``query_mask``: ``msda_fwd_qmasked_<dtype>``
+    (:func:`check_query_mask`; without a value mask the call passes all ones)."""
     B, I, H, D, Q, L, P = _dims(img, sampling_points, attention_weights, img_shapes)
     _check_devices(img, img_shapes, sampling_points, attention_weights)
-    if value_mask is not None:
-        value_mask = check_value_mask(value_mask, img)
     pad = _padding_code(padding_mode)
     cdt = sampling_points.dtype  # dtype of everything but `img` (the same, or fp32 next to a 16-bit `img`)
     if attention_weights.dtype != cdt:
@@ -318,9 +384,8 @@ def msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mo
         raise ValueError(f"`out` should be a contiguous {(B, Q, H, D)} {cdt} tensor on {img.device}, but got "
                          f"{tuple(out.shape)} {out.dtype} on {out.device} (contiguous: {out.is_contiguous()}).")
     lib = _lib.load()
-    name = "msda_fwd" if value_mask is None else "msda_fwd_masked"
+    name, mask_arg, _masks = _mask_args("msda_fwd", value_mask, query_mask, img, sampling_points)
     fn = getattr(lib, f"{name}_{suf}")
-    mask_arg = () if value_mask is None else (value_mask.data_ptr(),)
 
     def call():
         return fn(img.data_ptr(), *mask_arg, shapes.data_ptr(), sampling_points.data_ptr(), attention_weights.data_ptr(),
@@ -366,10 +431,12 @@ def msda_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, 
                  needs: Tuple[bool, bool, bool] = (True, True, True),
                  out: Optional[Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]] = None,
                  level_cells: int = 0, value_mask: Optional[torch.Tensor] = None,
+                 query_mask: Optional[torch.Tensor] = None,
                  ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
     """Returns ``(img_grad, sampling_points_grad, attention_weights_grad)``; entries not in ``needs`` are None.
     ``level_cells``: see :func:`level_cells_of` (0: unknown).  ``value_mask``: the value-mask twin
-    (``msda_bwd_masked_<dtype>``): padding pixels count as zeros and their ``img_grad`` rows are zeros.
+    (``msda_bwd_masked_<dtype>``): padding pixels count as zeros and their ``img_grad`` rows are zeros.  ``query_mask``:
+    ``msda_bwd_qmasked_<dtype>`` — the masked queries' gradient rows are zeros and nothing of theirs reaches ``img_grad``.
 
     Gradients are allocated contiguous (the reference's ``zeros_like(...).contiguous()`` would write
     into a temporary for permuted inputs, kernels.py:570-578) and are fully written by the kernels,
@@ -378,10 +445,7 @@ def msda_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, 
     """
     B, I, H, D, Q, L, P = _dims(img, sampling_points, attention_weights, img_shapes)
     _check_devices(img, img_shapes, sampling_points, attention_weights, out_grad)
-    if value_mask is not None:
-        value_mask = check_value_mask(value_mask, img)
-    bwd_name = "msda_bwd" if value_mask is None else "msda_bwd_masked"
-    mask_arg = () if value_mask is None else (value_mask.data_ptr(),)
+    bwd_name, mask_arg, _masks = _mask_args("msda_bwd", value_mask, query_mask, img, sampling_points)
     pad = _padding_code(padding_mode)
     cdt = sampling_points.dtype
     if attention_weights.dtype != cdt:
@@ -461,7 +525,7 @@ class _HipMultiscaleDeformableAttentionFunction(Function):
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)  # under autocast the op runs in fp32 (frontend.py:111)
     def forward(ctx, img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners, level_cells=0,
-                value_mask=None):
+                value_mask=None, query_mask=None):
         if ctx.needs_input_grad[0]:
             check_backward_supported(img, sampling_points)
         ctx.save_for_backward(img, img_shapes, sampling_points, attention_weights)
@@ -469,8 +533,9 @@ class _HipMultiscaleDeformableAttentionFunction(Function):
         ctx.align_corners = align_corners
         ctx.level_cells = int(level_cells)
         ctx.value_mask = value_mask  # (uint8 [B, I] or None; takes no gradient)
+        ctx.query_mask = query_mask  # (uint8 [B, Q] or None; likewise)
         return msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners,
-                            value_mask=value_mask)
+                            value_mask=value_mask, query_mask=query_mask)
 
     @staticmethod
     @once_differentiable
@@ -480,8 +545,9 @@ class _HipMultiscaleDeformableAttentionFunction(Function):
         needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3])
         g_img, g_pts, g_att = msda_hip_bwd(
             out_grad, img, img_shapes, sampling_points, attention_weights,
-            ctx.padding_mode, ctx.align_corners, needs, level_cells=ctx.level_cells, value_mask=ctx.value_mask)
-        return g_img, None, g_pts, g_att, None, None, None, None
+            ctx.padding_mode, ctx.align_corners, needs, level_cells=ctx.level_cells, value_mask=ctx.value_mask,
+            query_mask=ctx.query_mask)
+        return g_img, None, g_pts, g_att, None, None, None, None, None
 
 
 def hip_multiscale_deformable_attention(
@@ -494,11 +560,26 @@ def hip_multiscale_deformable_attention(
     level_shapes=None,
     points_per_level=None,
     value_mask=None,
+    query_mask=None,
 ) -> torch.Tensor:
     """GPU path.  Same contract as the reference's ``triton_multiscale_deformable_attention``
     (frontend.py:71-105): ``ValueError`` on unsupported dtype or non-GPU inputs.  ``level_shapes`` (an addition): the
-    pyramid's (h, w) pairs as host numbers, see :func:`level_cells_of`.  ``points_per_level``, ``value_mask``: see
-    :func:`multiscale_deformable_attention`."""
+    pyramid's (h, w) pairs as host numbers, see :func:`level_cells_of`.  ``points_per_level``, ``value_mask``,
+    ``query_mask``: see :func:`multiscale_deformable_attention`."""
+    if query_mask is not None:
+        if img.device.type != "cuda":
+            raise ValueError(f"hip_multiscale_deformable_attention needs GPU tensors, but `img` is on {img.device}.")
+        _validate_query_mask(query_mask, sampling_points)
+        # the query-mask entry points serve the uniform call outside a trace; everything else composes apply_query_mask
+        # with its route
+        if points_per_level is not None or torch.compiler.is_compiling() or not _lib.has_query_mask():
+            out = hip_multiscale_deformable_attention(
+                img, img_shapes, apply_query_mask(sampling_points, query_mask, 0.5),
+                apply_query_mask(attention_weights, query_mask, 0.0), padding_mode, align_corners, level_shapes,
+                points_per_level, value_mask)
+            return apply_query_mask(out, query_mask, 0.0)
+        if value_mask is None:  # (both masks travel to the kernels: a cached all-ones byte per pixel)
+            value_mask = _ones_value_mask(img)
     if value_mask is not None:
         if img.device.type != "cuda":
             raise ValueError(f"hip_multiscale_deformable_attention needs GPU tensors, but `img` is on {img.device}.")
@@ -520,7 +601,8 @@ def hip_multiscale_deformable_attention(
         # (the Python Function: the C++ autograd node takes no mask)
         return _HipMultiscaleDeformableAttentionFunction.apply(
             img, img_shapes, sampling_points, attention_weights, padding_mode, bool(align_corners),
-            level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1]), check_value_mask(value_mask, img))
+            level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1]), check_value_mask(value_mask, img),
+            None if query_mask is None else check_query_mask(query_mask, sampling_points))
     if points_per_level is not None:
         if img.device.type != "cuda":
             raise ValueError(f"hip_multiscale_deformable_attention needs GPU tensors, but `img` is on {img.device}.")
@@ -594,12 +676,14 @@ def module_sampling_inputs(proj: torch.Tensor, img_shapes: torch.Tensor, referen
 
 
 def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners,
-                       levelref: bool = False, value_mask: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+                       levelref: bool = False, value_mask: Optional[torch.Tensor] = None,
+                       query_mask: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """Forward with softmax + sampling-point math done in the kernel prologue.  Returns None when the
     library declines (L*P too large for one pass): the caller then takes the unfused route.  ``levelref``: the
     reference points are per level, ``[B, Q, L, ref_dim]``, and the points follow transformers' rule
     (:func:`hf_module_sampling_inputs`; ``msda_fwd_fused_levelref_<dtype>``).  ``value_mask`` (with ``levelref`` only):
-    the value-mask twin ``msda_fwd_fused_levelref_masked_<dtype>``."""
+    the value-mask twin ``msda_fwd_fused_levelref_masked_<dtype>``; ``query_mask`` (likewise):
+    ``msda_fwd_fused_levelref_qmasked_<dtype>``."""
     B, I, H, D = img.shape
     B2, Q, H2, L, P, three = proj.shape
     if (B2, H2, three) != (B, H, 3) or tuple(reference_points.shape[:2]) != (B, Q) or \
@@ -620,13 +704,9 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
     out = torch.empty((B, Q, H, D), dtype=cdt, device=img.device)
     lib = _lib.load()
     name = "msda_fwd_fused_levelref" if levelref else "msda_fwd_fused"
-    mask_arg = ()
-    if value_mask is not None:
-        if not levelref:
-            raise ValueError("`value_mask` is served by the per-level-reference fused kernels only (levelref=True)")
-        sym, mask_arg = name + "_masked", (check_value_mask(value_mask, img).data_ptr(),)
-    else:
-        sym = name
+    if (value_mask is not None or query_mask is not None) and not levelref:
+        raise ValueError("`value_mask` / `query_mask` are served by the per-level-reference fused kernels only (levelref=True)")
+    sym, mask_arg, _masks = _mask_args(name, value_mask, query_mask, img, proj)
     # (the timer's group stays the pair's — "msda_fwd_fused_levelref" — with or without a mask: it names the launcher)
     fn = getattr(lib, f"{sym}_{suf}", None)
     if fn is None:  # (a library built before the per-level entry points: the caller composes)
@@ -647,7 +727,7 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
 
 def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners,
                        need_img: bool = True, level_cells: int = 0, need_ref: bool = True, levelref: bool = False,
-                       value_mask: Optional[torch.Tensor] = None):
+                       value_mask: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None):
     """Backward of the module core with the prologue's chain rule done in the kernel: returns
     ``(img_grad | None, proj_grad, reference_points_grad)``, or None when the library declines (L*P too large
     for one pass; nothing was launched).  ``levelref``: as in :func:`msda_hip_fwd_fused`; the kernel's partials are
@@ -672,13 +752,10 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
                              device=img.device)
     lib = _lib.load()
     name = "msda_bwd_fused_levelref" if levelref else "msda_bwd_fused"
-    mask_arg = ()
-    if value_mask is not None:  # (the value-mask twin; the workspace is the twin's)
-        if not levelref:
-            raise ValueError("`value_mask` is served by the per-level-reference fused kernels only (levelref=True)")
-        sym, mask_arg = name + "_masked", (check_value_mask(value_mask, img).data_ptr(),)
-    else:
-        sym = name
+    if (value_mask is not None or query_mask is not None) and not levelref:
+        raise ValueError("`value_mask` / `query_mask` are served by the per-level-reference fused kernels only (levelref=True)")
+    # (the masked entry points; the workspace is the twin's)
+    sym, mask_arg, _masks = _mask_args(name, value_mask, query_mask, img, proj)
     fn = getattr(lib, f"{sym}_{suf}", None)  # (the timer's group stays the pair's, as in the forward)
     if fn is None:
         return None
@@ -758,13 +835,19 @@ class _HipFusedModuleCoreFunction(Function):
 
 
 def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None,
-                      points_per_level=None, value_mask=None) -> torch.Tensor:
+                      points_per_level=None, value_mask=None, query_mask=None) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *module_sampling_inputs(proj, ...))`` — on GPU tensors
     with the prologue fused into the forward kernel; on host tensors exactly that composition.  ``level_shapes``: the
     level sizes as host numbers, optional (:func:`level_cells_of`).  ``points_per_level``: a point count per level; then
     ``proj`` is ``[B, Q, H, S, 3]`` with ``S = sum(points_per_level)``, level-major
     (:func:`msda_triton_amd.ragged.ragged_module_sampling_inputs` states the prologue).  ``value_mask``: ``[B, I]``,
-    non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels (these have no masked form)."""
+    non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels (these have no masked form).
+    ``query_mask``: ``[B, Q]``, non-zero = the query is real; composed likewise (:func:`apply_query_mask`)."""
+    if query_mask is not None:
+        out = fused_module_core(img, img_shapes, apply_query_mask(proj, query_mask, 0.0),
+                                apply_query_mask(reference_points, query_mask, 0.5), padding_mode, align_corners,
+                                level_shapes, points_per_level, value_mask)
+        return apply_query_mask(out, query_mask, 0.0)
     img = apply_value_mask(img, value_mask)
     if points_per_level is not None:
         from .ragged import fused_ragged_module_core
@@ -875,15 +958,20 @@ class _HipFusedHFModuleCoreFunction(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, level_cells=0, value_mask=None):
+    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, level_cells=0, value_mask=None,
+                query_mask=None):
         ctx.level_cells = int(level_cells)
         ctx.value_mask = value_mask  # (uint8 [B, I] or None: the value-mask twins of both kernel families; no gradient)
+        ctx.query_mask = query_mask  # (uint8 [B, Q] or None: the query-mask entry points of both families; no gradient)
         out = msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, levelref=True,
-                                 value_mask=value_mask)
+                                 value_mask=value_mask, query_mask=query_mask)
         ctx.fused = out is not None  # the backward has the same limits: do not ask twice
         if out is None:
-            pts, att = hf_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points)
-            out = msda_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners, value_mask=value_mask).to(proj.dtype)
+            # (the prologue in PyTorch sees the masked queries' inputs: sanitised first, the kernels then skip them)
+            pts, att = hf_module_sampling_inputs(apply_query_mask(proj, query_mask, 0.0).to(reference_points.dtype), img_shapes,
+                                                 apply_query_mask(reference_points, query_mask, 0.5))
+            out = msda_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners, value_mask=value_mask,
+                               query_mask=query_mask).to(proj.dtype)
         ctx.save_for_backward(img, img_shapes, proj, reference_points)
         ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
         return out
@@ -897,19 +985,22 @@ class _HipFusedHFModuleCoreFunction(Function):
         if ctx.fused and (need_proj or need_ref):
             res = msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, ctx.padding_mode,
                                      ctx.align_corners, need_img, level_cells=ctx.level_cells, need_ref=need_ref,
-                                     levelref=True, value_mask=ctx.value_mask)
+                                     levelref=True, value_mask=ctx.value_mask, query_mask=ctx.query_mask)
             if res is not None:
                 g_img, g_proj, g_ref = res
-                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None
+                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None, None
         with torch.enable_grad():
             proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
             ref_ = reference_points.detach().requires_grad_(need_ref)
-            pts, att = hf_module_sampling_inputs(proj_, img_shapes, ref_)
+            # (a query mask: the chain rule runs on the sanitised inputs, so a masked query's gradients are where's zeros)
+            pts, att = hf_module_sampling_inputs(apply_query_mask(proj_, ctx.query_mask, 0.0), img_shapes,
+                                                 apply_query_mask(ref_, ctx.query_mask, 0.5))
         out_grad = out_grad.to(pts.dtype)
         need_sample = need_proj or need_ref
         g_img, g_pts, g_att = msda_hip_bwd(out_grad, img, img_shapes, pts.detach(), att.detach(), ctx.padding_mode,
                                            ctx.align_corners, (need_img, need_sample, need_sample),
-                                           level_cells=ctx.level_cells, value_mask=ctx.value_mask)
+                                           level_cells=ctx.level_cells, value_mask=ctx.value_mask,
+                                           query_mask=ctx.query_mask)
         g_proj = g_ref = None
         if need_sample:
             wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
@@ -918,11 +1009,11 @@ class _HipFusedHFModuleCoreFunction(Function):
                 g_proj = grads.pop(0).to(proj.dtype)
             if need_ref:
                 g_ref = grads.pop(0)
-        return g_img, None, g_proj, g_ref, None, None, None, None
+        return g_img, None, g_proj, g_ref, None, None, None, None, None
 
 
 def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None,
-                         value_mask=None, mask_in_kernels: bool = True) -> torch.Tensor:
+                         value_mask=None, mask_in_kernels: bool = True, query_mask=None) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *hf_module_sampling_inputs(proj, ...))``: the core of a Hugging
     Face attention module between its projections — value pyramid ``[B, I, H, D]``, raw projection ``[B, Q, H, L, P, 3]``,
     per-level reference points ``[B, Q, L, 2 | 4]``.  On GPU tensors the prologue and its chain rule run inside the
@@ -932,7 +1023,22 @@ def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, 
     is real (transformers' ``attention_mask``; :func:`check_value_mask`) — the result is that of ``where(mask, img, 0)``
     whatever the padding pixels hold.  On GPU tensors the mask goes into the kernels
     (``msda_*_fused_levelref_masked_<dtype>``: no pass over the pyramid in either direction); ``mask_in_kernels=False``,
-    host tensors, traced calls and a library without those symbols compose ``masked_fill`` with the unmasked route."""
+    host tensors, traced calls and a library without those symbols compose ``masked_fill`` with the unmasked route.
+    ``query_mask``: ``[B, Q]`` bool / uint8, non-zero = the query is real (:func:`check_query_mask`) — a masked query's row
+    of the result is zeros, its ``proj`` and ``reference_points`` rows get zero gradients and nothing it holds (NaN
+    included) reaches any result.  On GPU tensors it goes into the kernels with the value mask
+    (``msda_*_fused_levelref_qmasked_<dtype>``: a masked query is neither gathered for nor recorded for ``grad_value``);
+    the same other routes compose :func:`apply_query_mask`."""
+    qmask = None
+    if query_mask is not None:
+        _validate_query_mask(query_mask, proj)
+        if mask_in_kernels and img.device.type == "cuda" and not torch.compiler.is_compiling() and _lib.has_query_mask():
+            qmask = check_query_mask(query_mask, proj)
+        else:
+            out = fused_hf_module_core(img, img_shapes, apply_query_mask(proj, query_mask, 0.0),
+                                       apply_query_mask(reference_points, query_mask, 0.5), padding_mode, align_corners,
+                                       level_shapes, value_mask, mask_in_kernels)
+            return apply_query_mask(out, query_mask, 0.0)
     mask = None
     if value_mask is not None:
         _validate_value_mask(value_mask, img)
@@ -953,7 +1059,7 @@ def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, 
             pad = _padding_code(padding_mode)
             ext = _ext.load()
             # (a masked call takes the Python Function: the C++ node has no mask argument)
-            if mask is None and same and not autocast and KernelTimer.active is None and ext is not None and \
+            if mask is None and qmask is None and same and not autocast and KernelTimer.active is None and ext is not None and \
                     hasattr(ext, "msda_fused_levelref") and _lib.has_fused_levelref():
                 # C++ autograd node; only when the fused kernels take this L*P (it never composes)
                 B, I, H, D = img.shape
@@ -970,9 +1076,12 @@ def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, 
                     return ext.msda_fused_levelref(img, img_shapes, proj, reference_points, pad, bool(align_corners),
                                                    level_cells)
             return _HipFusedHFModuleCoreFunction.apply(img, img_shapes, proj, reference_points, padding_mode,
-                                                       bool(align_corners), level_cells, mask)
-    return _hf_composition(apply_value_mask(img, mask), img_shapes, proj, reference_points, padding_mode, align_corners,
-                           level_shapes)
+                                                       bool(align_corners), level_cells, mask, qmask)
+    if qmask is not None:  # (dtypes the kernels do not serve: the composition, as above)
+        proj, reference_points = apply_query_mask(proj, query_mask, 0.0), apply_query_mask(reference_points, query_mask, 0.5)
+    out = _hf_composition(apply_value_mask(img, mask), img_shapes, proj, reference_points, padding_mode, align_corners,
+                          level_shapes)
+    return apply_query_mask(out, query_mask if qmask is not None else None, 0.0)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1013,13 +1122,19 @@ def hf_box_sampling_inputs(proj: torch.Tensor, reference_points: torch.Tensor, p
 
 def fused_hf_box_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale: float = 0.5,
                       padding_mode: str = "zeros", align_corners: bool = False, level_shapes=None,
-                      value_mask=None) -> torch.Tensor:
+                      value_mask=None, query_mask=None) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *hf_box_sampling_inputs(proj, ...), points_per_level=...)``: the
     core of a D-FINE / DEIMv2 / RT-DETRv2 attention module between its projections — value pyramid ``[B, I, H, D]``, raw
     projection ``[B, Q, H, S, 3]`` (level-major), boxes ``[B, Q, 4]`` or ``[B, Q, 1, 4]``.  On GPU tensors the prologue and
     its chain rule run inside the gather kernels (``msda_*_fused_hfbox_<dtype>``, equal counts included); on host tensors,
     while traced and where the library declines it is exactly that composition (:mod:`msda_triton_amd.ragged`).
-    ``value_mask``: ``[B, I]``, non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels."""
+    ``value_mask``: ``[B, I]``, non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels.
+    ``query_mask``: ``[B, Q]``, non-zero = the query is real; composed likewise (:func:`apply_query_mask`)."""
+    if query_mask is not None:
+        out = fused_hf_box_core(img, img_shapes, apply_query_mask(proj, query_mask, 0.0),
+                                apply_query_mask(reference_points, query_mask, 0.5), points_per_level, offset_scale,
+                                padding_mode, align_corners, level_shapes, value_mask)
+        return apply_query_mask(out, query_mask, 0.0)
     from .ragged import fused_hf_box_module_core
     return fused_hf_box_module_core(apply_value_mask(img, value_mask), img_shapes, proj, reference_points, points_per_level, offset_scale, padding_mode,
                                     align_corners, level_shapes)
@@ -1117,6 +1232,7 @@ def multiscale_deformable_attention(
     points_per_level=None,
     sampling_mode: Literal["bilinear", "discrete"] = "bilinear",
     value_mask: Optional[torch.Tensor] = None,
+    query_mask: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Differentiable multiscale deformable attention.
 
@@ -1149,6 +1265,16 @@ def multiscale_deformable_attention(
             a uniform point count run the value-mask kernels (no extra pass over the pyramid in either direction);
             host tensors, ``points_per_level``, ``sampling_mode="discrete"`` and traced calls compose ``masked_fill``
             with their route.
+        query_mask: optional, not in the reference — ``[batch, num_queries]`` bool or uint8 on the queries' device,
+            non-zero = the query is real (the polarity of ``value_mask``; an encoder layer over a padded batch passes one
+            mask for both).  A masked query's row of the result is zeros, its sampling points and attention weights get
+            zero gradients, and NOTHING it holds — NaN, Inf or far-off coordinates in its points, weights or ``grad_out``
+            row — reaches ``img``'s gradient or any other result.  Real queries' rows are those of the call without the
+            mask, bit for bit.  The mask takes no gradient.  GPU tensors with a uniform point count run the query-mask
+            entry points (a masked query is neither gathered for nor recorded for ``img``'s gradient); host tensors,
+            ``points_per_level``, ``sampling_mode="discrete"`` and traced calls compose :func:`apply_query_mask` with
+            their route, which is also the definition: the call on inputs whose masked queries hold points 0.5 and
+            weights 0, with the masked rows of the result zeroed.
 
     Returns:
         ``[batch, num_queries, num_heads, num_channels]``.
@@ -1156,6 +1282,17 @@ def multiscale_deformable_attention(
     Tensors on an AMD GPU ("cuda" device type on ROCm) run the hand-written gfx950 kernels and
     never fall back; host tensors run the plain-PyTorch formulation.
     """
+    if query_mask is not None:
+        _validate_query_mask(query_mask, sampling_points)
+        if sampling_mode == "bilinear" and points_per_level is None and img.device.type == "cuda":
+            return hip_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,
+                                                       align_corners, level_shapes, value_mask=value_mask,
+                                                       query_mask=query_mask)
+        out = multiscale_deformable_attention(
+            img, img_shapes, apply_query_mask(sampling_points, query_mask, 0.5),
+            apply_query_mask(attention_weights, query_mask, 0.0), padding_mode, align_corners, level_shapes,
+            points_per_level, sampling_mode, value_mask)
+        return apply_query_mask(out, query_mask, 0.0)
     if value_mask is not None:
         _validate_value_mask(value_mask, img)
         if sampling_mode == "bilinear" and points_per_level is None and img.device.type == "cuda":

@@ -147,9 +147,21 @@ class FusedHFDeformableAttention:
 
     The softmaxed attention weights are never materialised, so the second element of the returned pair is ``None``.  A
     caller that records attentions sets ``module.return_attention_weights = True`` (or passes
-    ``output_attentions=True``): the module then takes the original forward over the adapter's core."""
+    ``output_attentions=True``): the module then takes the original forward over the adapter's core.
+
+    ``skip_padded_queries`` (set per module by ``replace_hf_msda(model, fused=True, skip_padded_queries=True)``; off by
+    default): in an encoder layer — ``encoder_hidden_states is hidden_states``, so every pixel of the padded pyramid is
+    also a query and the ``[B, I]`` ``attention_mask`` covers both roles — the mask also travels as ``query_mask``: a
+    padded position is neither gathered for nor recorded for the pyramid's gradient.  Its attended row is then zeros, so
+    the layer's output there is ``output_proj``'s BIAS, not the projection of whatever the padded position sampled.  Valid
+    positions are unaffected, because every consumer masks the padded ones: the next layer and the decoder's
+    cross-attention read them as values through the same mask (a row of zeros whatever they hold), and the two-stage
+    proposals ``masked_fill`` them.  Taken only when all three hold: a mask was passed, the layer attends to its own
+    hidden states (tested on the arguments, before the position embeddings are added), and the mask's shape is
+    ``hidden_states.shape[:2]``."""
 
     return_attention_weights = False
+    skip_padded_queries = False
 
     def _proj_rows(self, device) -> torch.Tensor:
         # row (h, l, p, k) of the one projection: k < 2 the offset rows of `sampling_offsets`, k == 2 the logit row of
@@ -170,6 +182,7 @@ class FusedHFDeformableAttention:
                                    encoder_attention_mask=encoder_attention_mask, position_embeddings=position_embeddings,
                                    reference_points=reference_points, spatial_shapes=spatial_shapes,
                                    spatial_shapes_list=spatial_shapes_list, level_start_index=level_start_index, **kwargs)
+        self_attention = encoder_hidden_states is hidden_states  # (on the arguments: the sum below makes a new tensor)
         if position_embeddings is not None:
             hidden_states = hidden_states + position_embeddings
         batch_size, num_queries, _ = hidden_states.shape
@@ -181,6 +194,8 @@ class FusedHFDeformableAttention:
         mask_kw = {}
         if attention_mask is not None:
             mask_kw = dict(value_mask=attention_mask, mask_in_kernels=mask_in_kernels(value, num_queries))
+            if self.skip_padded_queries and self_attention and tuple(attention_mask.shape) == (batch_size, num_queries):
+                mask_kw["query_mask"] = attention_mask  # every pixel is a query too: the mask covers both roles
         # ONE GEMM for offsets and logits, laid out [B, Q, H, L, P, 3]; the weight is gathered from the two HF parameters
         # (autograd routes its gradient back to them)
         rows = self._proj_rows(hidden_states.device)
@@ -353,7 +368,7 @@ def _wrap_fused_box(module: nn.Module) -> bool:
     return True
 
 
-def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = False) -> int:
+def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = False, skip_padded_queries: bool = False) -> int:
     """Swap every HF ``MultiScaleDeformableAttention`` submodule of ``model`` for the adapter, and set
     :func:`ms_deformable_attn_core` on every module that carries an ``ms_deformable_attn_core`` attribute with
     ``decoder_method == "default"`` (D-FINE / DEIMv2; ``"discrete"`` modules are left alone).  With ``discrete=True``
@@ -367,7 +382,9 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
     ``"default"`` (D-FINE, DEIMv2, RT-DETRv2; by these names as well) a :class:`FusedHFBoxDeformableAttention`.  Returns
     the number of modules replaced, patched or wrapped: without ``fused`` exactly what it always returned, with it that
     number plus the modules wrapped (a D-FINE decoder layer then counts twice, once for its core and once for the
-    wrapper)."""
+    wrapper).  ``skip_padded_queries=True`` (opt-in, no effect without ``fused=True``) sets
+    :attr:`FusedHFDeformableAttention.skip_padded_queries` on every module wrapped as one: encoder layers then hand their
+    padding mask to the core as ``query_mask`` too (see the class); the count is what it is without the flag."""
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -388,4 +405,7 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
         for module in list(model.modules()):
             if _wrap_fused(module) or _wrap_fused_box(module):
                 count += 1
+            if skip_padded_queries and isinstance(module, FusedHFDeformableAttention) and \
+                    not isinstance(module, FusedHFBoxDeformableAttention):
+                module.skip_padded_queries = True  # (an instance attribute: state_dict stays the HF module's)
     return count

@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from ._linear import projection
-from .functional import apply_value_mask, fused_module_core, module_sampling_inputs
+from .functional import apply_query_mask, apply_value_mask, fused_module_core, module_sampling_inputs
 from .ragged import ragged_module_sampling_inputs
 
 
@@ -91,7 +91,7 @@ class MultiscaleDeformableAttention(nn.Module):
         return module_sampling_inputs(proj, img_shapes, reference_points)
 
     def forward(self, img: torch.Tensor, img_shapes: torch.Tensor, queries: torch.Tensor,
-                reference_points: torch.Tensor, level_shapes=None, value_mask=None) -> torch.Tensor:
+                reference_points: torch.Tensor, level_shapes=None, value_mask=None, query_mask=None) -> torch.Tensor:
         """
         Args:
             img: flattened pyramid ``[batch, num_image, emb_dim]``.
@@ -104,6 +104,10 @@ class MultiscaleDeformableAttention(nn.Module):
             value_mask: optional (not in the reference): ``[batch, num_image]`` bool or uint8, non-zero = the pixel is
                 real (transformers' ``attention_mask`` polarity).  Applied to the projected pyramid as ``masked_fill``
                 (this module's fused kernels have no masked form); see ``multiscale_deformable_attention``.
+            query_mask: optional (not in the reference): ``[batch, num_queries]`` bool or uint8, non-zero = the query is
+                real.  Composed around the core (``functional.apply_query_mask``): a masked query's attended row is
+                zeros, so its row of the result is the output projection's bias, and nothing its projection or reference
+                point holds reaches a gradient.
 
         Returns:
             ``[batch, num_queries, emb_dim]``.
@@ -126,6 +130,8 @@ class MultiscaleDeformableAttention(nn.Module):
         #  from 32 768 (b, q) rows on)
         value = projection(self.img_input_proj, img, pad_rows=B * N >= 32768).reshape(B, I, H, self.hidden_dim // H)
         value = apply_value_mask(value, value_mask)
+        if query_mask is not None:
+            proj, reference_points = apply_query_mask(proj, query_mask, 0.0), apply_query_mask(reference_points, query_mask, 0.5)
         if value.device.type == "cuda" and proj.dtype in (torch.bfloat16, torch.float16) and \
                 self.value_dtype in (None, proj.dtype) and value.dtype == proj.dtype:
             # 16-bit projections (autocast's GEMMs, or 16-bit parameters) with fp32 reference points: the kernels read
@@ -145,4 +151,5 @@ class MultiscaleDeformableAttention(nn.Module):
         else:
             attended = fused_module_core(value, img_shapes, proj, reference_points, self.padding_mode,
                                          self.align_corners, level_shapes, counts)
+        attended = apply_query_mask(attended, query_mask, 0.0)
         return projection(self.query_output_proj, attended.reshape(B, N, self.hidden_dim))
