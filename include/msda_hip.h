@@ -477,6 +477,56 @@ MSDA_QUERY_MASK_FUSED(f32_vbf16) MSDA_QUERY_MASK_FUSED(f32_vf16) MSDA_QUERY_MASK
 #undef MSDA_QUERY_MASK_FUSED
 
 /*
+ * Hugging Face's box rule in front of DISCRETE sampling (D-FINE / DEIMv2 / RT-DETRv2 with decoder_method = "discrete") —
+ * ADDITIONS WITHIN ABI 12, probed by symbol: msda_fwd_fused_hfbox_discrete_<suffix> / msda_bwd_fused_hfbox_discrete_<suffix>
+ * (the eight suffixes of the hfbox pair) and msda_bwd_fused_hfbox_discrete_workspace_bytes.  The argument lists are the
+ * hfbox pair's WITHOUT ref_dim (boxes only: `ref` [B, Q, 4]), padding_mode, align_corners (discrete sampling has neither)
+ * and grad_ref_partial (the pixel index is an integer: nothing differentiable reaches the point, hence nothing the box):
+ *
+ *   a_s   = softmax over the unit's S logits proj[..., 2]
+ *   point = ref.xy + proj[..., :2] * level_scale[l] * ref.wh * offset_scale     four roundings, as the hfbox pair's
+ *   out[b, q, head, :] = sum_s a_s * value[b, start_l + iy * w + ix, head, :]   the pixel rule of msda_fwd_discrete_<dtype>
+ *
+ * The point and the pixel are formed in fp32 from the stored values (fp64 for f64), never with a fused multiply-add, by
+ * the very helpers of the two families this one joins, so for fp32 / fp64 inputs the pixel is the one transformers'
+ * expressions pick on the same projection.  The ALL-16-BIT suffixes (f16, bf16) differ from transformers there: it forms
+ * the point in 16 bits and can land on the neighbouring pixel; the kernel's point is the fp32 one.
+ * msda_bwd_fused_hfbox_discrete_<suffix> writes EVERY element of grad_proj [B, Q, H, S, 3]: the two offset slots are stored
+ * zeros, the logit slot is a_s (g_s - sum_t a_t g_t) with g_s = <the sample's row, the unit's grad_out row>.  grad_value
+ * == NULL means a frozen pyramid: no workspace is needed and one kernel runs.  Otherwise the head of the workspace
+ * receives the sampling points [B, Q, H, S, 2] and behind them the softmaxed weights [B, Q, H, S] (float for the 16-bit
+ * operators, as the hfbox pair parks them), and msda_bwd_discrete_<dtype>'s grad_value pipeline runs on those two buffers —
+ * its limits, reproducibility and MSDA_WS_PASSES(n) carry over; msda_bwd_fused_hfbox_discrete_workspace_bytes (the
+ * arguments of msda_bwd_discrete_workspace_bytes) is the size, 0 where the call needs none or is refused.
+ * L <= 8 (the scales ride in the kernel arguments): more is MSDA_ERR_UNSUPPORTED.  S = sum of points_per_level has NO limit
+ * of its own beyond the common size guards (msda_fused_lp_limit does not apply: nothing per sample is held in LDS).  A
+ * null level_scale is MSDA_ERR_BAD_ARG; a grad_value the pipeline cannot produce for the shape is MSDA_ERR_UNSUPPORTED and a
+ * workspace that is too small MSDA_ERR_BAD_ARG; all of these are answered BEFORE anything is launched.
+ * msda_last_launch_info: "fwd_variant" 4, "sample_variant" 3.
+ */
+#define MSDA_HFBOX_DISCRETE(SUF)                                                                       \
+    MSDA_API int msda_fwd_fused_hfbox_discrete_##SUF(const void *value, const int64_t *shapes,      \
+                       const void *proj, const void *ref, void *out, int64_t B, int64_t I,          \
+                       int64_t H, int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level, \
+                       const float *level_scale, double offset_scale, int64_t value_row_stride,     \
+                       void *stream);                                                               \
+    MSDA_API int msda_bwd_fused_hfbox_discrete_##SUF(const void *grad_out, const void *value,       \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,      \
+                       int64_t L, const int32_t *points_per_level, const float *level_scale,        \
+                       double offset_scale, int64_t max_level_cells, int64_t value_row_stride,      \
+                       void *workspace, int64_t workspace_bytes, void *stream);
+#define MSDA_HFBOX_DISCRETE_QUERY(WHAT)                                                                \
+    MSDA_API int64_t msda_bwd_fused_hfbox_discrete_##WHAT(int64_t B, int64_t I, int64_t H,          \
+                       int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level,            \
+                       int elem_size, int value_elem_size, int64_t max_level_cells, int flags);
+MSDA_HFBOX_DISCRETE(f32) MSDA_HFBOX_DISCRETE(f16) MSDA_HFBOX_DISCRETE(bf16) MSDA_HFBOX_DISCRETE(f64)
+MSDA_HFBOX_DISCRETE(f32_vbf16) MSDA_HFBOX_DISCRETE(f32_vf16) MSDA_HFBOX_DISCRETE(f32_sbf16) MSDA_HFBOX_DISCRETE(f32_sf16)
+MSDA_HFBOX_DISCRETE_QUERY(workspace_bytes)
+#undef MSDA_HFBOX_DISCRETE
+#undef MSDA_HFBOX_DISCRETE_QUERY
+
+/*
  * Bytes of device workspace msda_bwd_<dtype> wants for these sizes.  elem_size: of everything but `value`;
  * value_elem_size: of `value` / `grad_value` (0: the same — 2 next to elem_size 4 for the mixed-storage entry points);
  * max_level_cells: as for the call (0: unknown).
@@ -621,7 +671,8 @@ MSDA_API int msda_profile_read(char *buf, int cap);
 MSDA_API int msda_get_option(const char *key);
 /* Measurement only (ABI 11): which variants the most recent launches took (process-wide; bench.py reads it to say how many
  * of the forward's rows came from LDS).  Keys: "fwd_variant" 0 = 256-thread kernel, 1 = LDS-served coarse levels, 2 = one
- * wave per unit, 3 = the discrete-sampling forward (msda_fwd_discrete_<dtype>);  "fwd_lds_level_bytes" LDS bytes per plane set aside for level rows (the kernel keeps the longest suffix
+ * wave per unit, 3 = the discrete-sampling forward (msda_fwd_discrete_<dtype>), 4 = the box rule's discrete forward
+ * (msda_fwd_fused_hfbox_discrete_<suffix>; its backward kernel: "sample_variant" 3);  "fwd_lds_level_bytes" LDS bytes per plane set aside for level rows (the kernel keeps the longest suffix
  * of the level list that fits);  "fwd_lds_planes";  "fwd_workgroups";  "sample_variant", "sample_lds_level_bytes" the same
  * for the sample-gradient kernel (2 = the discrete attention-weight gradient);  "value_path" 1 = single-launch kernel, 2 = sorted pipeline;  "value_passes" its passes
  * over the batch.

@@ -55,6 +55,12 @@ QUERY_MASK_SYMBOLS = tuple(
     + [f"msda_{d}_fused_levelref_qmasked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
 )
 
+# ... and Hugging Face's box rule in front of discrete sampling (has_fused_hfbox_discrete): the hfbox pair's suffixes
+HFBOX_DISCRETE_SYMBOLS = tuple(
+    [f"msda_{d}_fused_hfbox_discrete_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+    + ["msda_bwd_fused_hfbox_discrete_workspace_bytes"]
+)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -215,6 +221,22 @@ def load():
                 glq = getattr(lib, f"msda_bwd_fused_levelref_qmasked_{suf}")
                 glq.restype = ci
                 glq.argtypes = [vp] * 10 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
+        # the box rule in front of discrete sampling: additions within ABI 12 (has_fused_hfbox_discrete); the hfbox pair's
+        # lists without ref_dim, padding_mode, align_corners and grad_ref_partial
+        if hasattr(lib, "msda_bwd_fused_hfbox_discrete_workspace_bytes"):
+            cd = ctypes.c_double
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                fhd = getattr(lib, f"msda_fwd_fused_hfbox_discrete_{suf}")
+                fhd.restype = ci
+                # (value, shapes, proj, ref, out, B ... L, points_per_level, level_scale, offset_scale, value_row_stride, stream)
+                fhd.argtypes = [vp] * 5 + [i64] * 6 + [vp, vp, cd, i64, vp]
+                ghd = getattr(lib, f"msda_bwd_fused_hfbox_discrete_{suf}")
+                ghd.restype = ci
+                # (grad_out, value, shapes, proj, ref, grad_value, grad_proj, B ... L, points_per_level, level_scale,
+                #  offset_scale, max_level_cells, value_row_stride, workspace, workspace_bytes, stream)
+                ghd.argtypes = [vp] * 7 + [i64] * 6 + [vp, vp, cd, i64, i64, vp, i64, vp]
+            lib.msda_bwd_fused_hfbox_discrete_workspace_bytes.restype = i64
+            lib.msda_bwd_fused_hfbox_discrete_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -262,6 +284,13 @@ def has_fused_hfbox() -> bool:
     (msda_fwd_fused_hfbox_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller composes
     transformers' prologue around the ragged operator."""
     return hasattr(load(), "msda_bwd_fused_hfbox_f32")
+
+
+def has_fused_hfbox_discrete() -> bool:
+    """Does the loaded library have the box rule's pair for discrete sampling (msda_fwd_fused_hfbox_discrete_<dtype> ...,
+    additions within ABI 12, found by symbol)?  Without them the caller composes transformers' prologue around the
+    discrete operator."""
+    return hasattr(load(), "msda_bwd_fused_hfbox_discrete_workspace_bytes")
 
 
 def has_value_mask() -> bool:

@@ -157,6 +157,23 @@ extern "C" int64_t msda_bwd_discrete_workspace_bytes(int64_t B, int64_t I, int64
                                            flags & ~MSDA_WS_RECORDS_IN_GRADS);
 }
 
+// the box rule in front of discrete sampling: the parked points and weights (3 elements per sample, float for the 16-bit
+// operators), then the discrete pipeline's workspace; 0 where the call is refused or needs none
+extern "C" int64_t msda_bwd_fused_hfbox_discrete_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,
+                                                                 int64_t L, const int32_t *points_per_level, int elem_size,
+                                                                 int value_elem_size, int64_t max_level_cells, int flags)
+{
+    (void)value_elem_size;
+    msda::Dims d;
+    if (elem_size <= 0 || L > msda::kFusedRaggedMaxLevels || !msda::ragged_dims(d, B, I, H, D, Q, L, points_per_level, max_level_cells))
+        return 0;
+    if (msda::common_limits_exceeded(d, elem_size)) return 0;
+    if (elem_size == 2) elem_size = 4;  // (ParkType: the float grad_value passes)
+    if (msda::common_limits_exceeded(d, elem_size) || !msda::bwd_supported(d, elem_size)) return 0;
+    return (int64_t)msda::fused_mat_bytes(d.B, d.H, d.Q, msda::samples(d), (size_t)elem_size) +
+           msda::sorted_ws_bytes(d, elem_size, false, 0, msda::passes_of(flags));
+}
+
 extern "C" int msda_bwd_discrete_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                            const int32_t *points_per_level, int elem_size)
 {

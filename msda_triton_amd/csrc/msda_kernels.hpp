@@ -278,7 +278,15 @@ struct HfBoxParams : RaggedParams {
     float lscale[kFusedRaggedMaxLevels];  // s_l; entries beyond L are 0
     double off_scale;
 };
-template <typename PP> constexpr bool kHfBox = std::is_base_of<HfBoxParams, PP>::value;
+// ... and the same rule in front of DISCRETE sampling (msda_*_fused_hfbox_discrete_<dtype>, msda_hfbox_discrete.hpp): the
+// discrete kernarg with the same two additions behind it, so that its grad_value passes are the discrete pipeline's
+// (value_pass_params, msda_launch.hpp) and hfbox_scale reads the scales where it reads HfBoxParams'.
+struct HfBoxDiscreteParams : DiscreteParams {
+    float lscale[kFusedRaggedMaxLevels];
+    double off_scale;
+};
+template <typename PP> constexpr bool kHfBoxDiscrete = std::is_base_of<HfBoxDiscreteParams, PP>::value;
+template <typename PP> constexpr bool kHfBox = std::is_base_of<HfBoxParams, PP>::value || kHfBoxDiscrete<PP>;
 
 // s_l of the sample's level, converted to the arithmetic type: a select per level on scalars at constant kernarg offsets
 // (as lvl_of's scan; the level itself comes from that scan, the host bounds L by kFusedRaggedMaxLevels).

@@ -11,6 +11,7 @@
 #include "msda_value_place.hpp"
 #include "msda_value_small.hpp"
 #include "msda_discrete.hpp"
+#include "msda_hfbox_discrete.hpp"
 #include "msda_options.hpp"
 
 namespace msda {
@@ -877,6 +878,11 @@ inline void fill_box_scales(HfBoxParams &p, const float *lscale, double off_scal
     for (int64_t l = 0; l < kFusedRaggedMaxLevels; ++l) p.lscale[l] = l < L ? lscale[l] : 0.0f;
     p.off_scale = off_scale;
 }
+inline void fill_box_scales(HfBoxDiscreteParams &p, const float *lscale, double off_scale, int64_t L)
+{
+    for (int64_t l = 0; l < kFusedRaggedMaxLevels; ++l) p.lscale[l] = l < L ? lscale[l] : 0.0f;
+    p.off_scale = off_scale;
+}
 inline void fill_box_scales(Params &, const float *, double, int64_t) {}
 // the value padding mask (msda_*_masked_<dtype>): [B, I] bytes behind the kernarg; advanced with every other batch-indexed
 // pointer when the grad_value pipeline runs once per group of batch elements
@@ -938,6 +944,61 @@ template <typename T, int MODE, typename TV> inline int dispatch_discrete(Discre
     constexpr int VECF = 16 / sizeof(T);
     if (vec_ok && (p.D % VECF) == 0) return dispatch_discrete_group<T, VECF, MODE, TV>(p, stream);
     return dispatch_discrete_group<T, 1, MODE, TV>(p, stream);
+}
+
+// ---- the box rule in front of discrete sampling: msda_{fwd,bwd}_fused_hfbox_discrete_<suffix>, kernels in
+//      msda_hfbox_discrete.hpp ----
+// MODE 0: the forward, 1: the backward (grad_proj; the points and weights for the grad_value passes).  The geometry is
+// launch_discrete's; the kernels' level scan is the fused kernels' (at most kFusedRaggedMaxLevels scales in the kernarg),
+// refused here, before anything is launched.
+template <typename T, int VEC, int G, int MODE, typename TV, typename TS>
+inline int launch_hfbox_discrete(HfBoxDiscreteParams &p, hipStream_t stream)
+{
+    constexpr int NU = kBlock / G;
+    p.nqc = (p.Q + NU - 1) / NU;
+    dim3 grid;
+    if (!plane_grid(p, p.B * p.H, p.nqc, grid)) {
+        set_error("grid too large");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    if (MODE == 0) {
+        note_launch(0, 4);
+        note_launch(1, 0);
+        note_launch(2, 1);
+        note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, G, p.D);
+        const ProfileScope prof("msda_fwd_hfbox_discrete_kernel", stream);
+        hipLaunchKernelGGL((msda_fwd_hfbox_discrete_kernel<T, VEC, G, TV, TS>), grid, dim3(kBlock), 0, stream, p);
+    } else {
+        note_launch(4, 3);
+        note_launch(5, 0);
+        note_instance(11, VEC, G, p.D);
+        const ProfileScope prof("msda_bwd_hfbox_discrete_kernel", stream);
+        hipLaunchKernelGGL((msda_bwd_hfbox_discrete_kernel<T, VEC, G, TV, TS>), grid, dim3(kBlock), 0, stream, p);
+    }
+    return (int)hipGetLastError();
+}
+template <typename T, int VEC, int MODE, typename TV, typename TS>
+inline int dispatch_hfbox_discrete_group(HfBoxDiscreteParams &p, hipStream_t stream)
+{
+    switch (pick_group((p.D + VEC - 1) / VEC)) {
+    case 4: return launch_hfbox_discrete<T, VEC, 4, MODE, TV, TS>(p, stream);
+    case 8: return launch_hfbox_discrete<T, VEC, 8, MODE, TV, TS>(p, stream);
+    case 16: return launch_hfbox_discrete<T, VEC, 16, MODE, TV, TS>(p, stream);
+    case 32: return launch_hfbox_discrete<T, VEC, 32, MODE, TV, TS>(p, stream);
+    default: return launch_hfbox_discrete<T, VEC, 64, MODE, TV, TS>(p, stream);
+    }
+}
+template <typename T, int MODE, typename TV, typename TS>
+inline int dispatch_hfbox_discrete(HfBoxDiscreteParams &p, bool vec_ok, hipStream_t stream)
+{
+    constexpr int VECF = 16 / sizeof(T);
+    if (p.L > kFusedRaggedMaxLevels) {
+        set_error("the fused box prologue serves at most %d levels, got %d", kFusedRaggedMaxLevels, p.L);
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    if (vec_ok && (p.D % VECF) == 0) return dispatch_hfbox_discrete_group<T, VECF, MODE, TV, TS>(p, stream);
+    return dispatch_hfbox_discrete_group<T, 1, MODE, TV, TS>(p, stream);
 }
 
 // ---- one call of an entry point, by name.  The extern "C" functions (MSDA_DEFINE_* below) fill one and hand it to their
@@ -1045,6 +1106,8 @@ template <typename T, typename TV = T, typename PP = Params> int run_fwd(const C
 // rule (msda_kernels.hpp)
 // PP = HfBoxParams (msda_fwd_fused_hfbox_<dtype>): the per-level-count layout with transformers' box rule — `level_scale`
 // holds L fp32 scales on the host, `offset_scale` the config's (the entry point checked ref_dim == 4)
+// PP = HfBoxDiscreteParams (msda_fwd_fused_hfbox_discrete_<dtype>): the same rule in front of discrete sampling, on the
+// kernels of msda_hfbox_discrete.hpp (no padding mode — border —, no 32-bit limit on the projection)
 template <typename T, typename TV = T, typename TS = T, typename PP = Params> int run_fwd_fused(const Call &c)
 {
     const Dims d = make_dims(c);
@@ -1057,7 +1120,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     if (rc) return rc;
     if (samples(d) == 0 || d.I == 0) return zero_outputs({{c.out, out_bytes}}, stream);
     if ((rc = require_buffers({c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
-    if (fused_limit_exceeded(d)) {
+    if (!kHfBoxDiscrete<PP> && fused_limit_exceeded(d)) {  // (the discrete kernels index the projection in 64 bits)
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
@@ -1066,7 +1129,10 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     PP p{};
     if ((rc = fill_kernarg<TV>(p, c, d)) != 0) return rc;
     p.loc = c.proj;
-    return launched(dispatch_gather<T, 2, TV, TS>(p, rows_vec_ok(p, c.out), stream), "fused forward");
+    if constexpr (kHfBoxDiscrete<PP>)
+        return launched(dispatch_hfbox_discrete<T, 0, TV, TS>(p, rows_vec_ok(p, c.out), stream), "fused discrete forward");
+    else
+        return launched(dispatch_gather<T, 2, TV, TS>(p, rows_vec_ok(p, c.out), stream), "fused forward");
 }
 
 // ---- single-launch grad_value for small problems (msda_value_small.hpp) ----
@@ -1190,6 +1256,23 @@ inline const char *ws_query_name(const Params &) { return "msda_bwd_workspace_by
 inline const char *ws_query_name(const RaggedParams &) { return "msda_bwd_ragged_workspace_bytes"; }
 inline const char *ws_query_name(const DiscreteParams &) { return "msda_bwd_discrete_workspace_bytes"; }
 
+// Would run_value find a route for this call?  0, or the status it would return — for a caller that must refuse before
+// its own first launch (run_bwd_fused on the box rule's discrete kernels); nothing is launched or written here.
+template <typename T, typename TV> inline int value_route_status(const Params &p, const Dims &d, const void *workspace, int64_t workspace_bytes)
+{
+    if (small_path_chosen<T>(d)) return 0;
+    const bool fits = sorted_fits<T>(d);
+    if (fits && value_batch_per_pass<T, TV>(p, d, workspace, workspace_bytes) > 0) return 0;
+    if (option_value_path() != 2 && small_fits<T>(d)) return 0;
+    if (!fits) {
+        set_error("grad_value: this shape is beyond the sorted pipeline's record format and too large for the single-launch kernel");
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    set_error("grad_value needs a larger 256-byte aligned workspace (got %lld bytes behind the parked points): see the "
+              "family's workspace query", (long long)(workspace ? workspace_bytes : 0));
+    return MSDA_ERR_BAD_ARG;
+}
+
 template <typename T, typename TV = T, typename TS = T, typename PP = Params>
 inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_bytes, hipStream_t stream)
 {
@@ -1258,10 +1341,12 @@ int run_value_float(PP &p, const Dims &d, void *workspace, int64_t workspace_byt
 }
 #define MSDA_RUN_VALUE_FLOAT_(KW, TS, PP) \
     KW template int msda::run_value_float<TS, TS, msda::PP>(msda::PP &, const msda::Dims &, void *, int64_t, hipStream_t);
-#define MSDA_DECLARE_RUN_VALUE_FLOAT(TS) \
-    MSDA_RUN_VALUE_FLOAT_(extern, TS, Params) MSDA_RUN_VALUE_FLOAT_(extern, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(extern, TS, MaskedParams)
-#define MSDA_DEFINE_RUN_VALUE_FLOAT(TS) \
-    MSDA_RUN_VALUE_FLOAT_(, TS, Params) MSDA_RUN_VALUE_FLOAT_(, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(, TS, MaskedParams)
+#define MSDA_DECLARE_RUN_VALUE_FLOAT(TS)                                                                                                       \
+    MSDA_RUN_VALUE_FLOAT_(extern, TS, Params) MSDA_RUN_VALUE_FLOAT_(extern, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(extern, TS, MaskedParams) \
+    MSDA_RUN_VALUE_FLOAT_(extern, TS, DiscreteParams)
+#define MSDA_DEFINE_RUN_VALUE_FLOAT(TS)                                                                                     \
+    MSDA_RUN_VALUE_FLOAT_(, TS, Params) MSDA_RUN_VALUE_FLOAT_(, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(, TS, MaskedParams) \
+    MSDA_RUN_VALUE_FLOAT_(, TS, DiscreteParams)
 
 // PP as run_fwd's.  DiscreteParams (msda_bwd_discrete_<dtype>): grad_value and / or grad_attn — the sampling points have no
 // gradient in this mode, so there is no grad_loc buffer, the records always stay in the workspace
@@ -1373,12 +1458,16 @@ inline Params &value_pass_params(LevelRefParams &p) { return p; }
 inline MaskedParams &value_pass_params(LevelRefMaskedParams &p) { return p; }  // (... the plain value-mask pipeline)
 // ... and so does Hugging Face's box rule: grad_value is the PER-LEVEL-COUNT pipeline on the parked points.
 inline RaggedParams &value_pass_params(HfBoxParams &p) { return p; }
+// ... and in front of discrete sampling the DISCRETE pipeline (cell_of's one-corner records)
+inline DiscreteParams &value_pass_params(HfBoxDiscreteParams &p) { return p; }
 
 // PP = RaggedParams (msda_bwd_fused_ragged_<dtype>): per-level point counts, proj / grad_proj [B, Q, H, S, 3]; the
 // derived points and weights go to the workspace in the ragged operator's layout and its grad_value pipeline reads them
 // PP = LevelRefParams (msda_bwd_fused_levelref_<dtype>): `ref` [B, Q, L, ref_dim], partials [B, Q, H, L, ref_dim]
 // PP = HfBoxParams (msda_bwd_fused_hfbox_<dtype>): the per-level-count layout and workspace, transformers' box rule with
 // the host's `level_scale` [L] and `offset_scale`
+// PP = HfBoxDiscreteParams (msda_bwd_fused_hfbox_discrete_<dtype>): that rule in front of discrete sampling — grad_proj only
+// (no partials: c.grad_ref_partial stays null), the same head of the workspace, then the DISCRETE grad_value pipeline
 template <typename T, typename TV = T, typename TS = T, typename PP = Params> int run_bwd_fused(const Call &c)
 {
     const Dims d = make_dims(c);
@@ -1389,7 +1478,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     if (rc == 0) rc = check_ref_dim(c.ref_dim);
     if (rc) return rc;
     const size_t ns = (size_t)(d.B * d.Q * d.H * samples(d));
-    const size_t nref = (size_t)(d.B * d.Q * d.H) * (kLevelRef<PP> ? (size_t)d.L : 1) * c.ref_dim;
+    // (discrete sampling: nothing differentiable reaches the box, there are no partials)
+    const size_t nref = kHfBoxDiscrete<PP> ? 0 : (size_t)(d.B * d.Q * d.H) * (kLevelRef<PP> ? (size_t)d.L : 1) * c.ref_dim;
     // (a buffer of no elements may be null: PyTorch's empty tensors are — a call with Q = 0 has nothing to produce there)
     if ((ns && c.grad_proj == nullptr) || (nref && c.grad_ref_partial == nullptr)) {
         set_error("the fused backward always produces grad_proj and the grad_reference_points partials");
@@ -1399,7 +1489,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         return zero_outputs({{grad_value, (size_t)(d.B * d.I * d.H * d.D) * sizeof(TV)}, {c.grad_proj, ns * 3 * sizeof(TS)},
                              {c.grad_ref_partial, nref * sizeof(T)}}, stream);
     if ((rc = require_buffers({c.grad_out, c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
-    if (fused_limit_exceeded(d)) {
+    if (!kHfBoxDiscrete<PP> && fused_limit_exceeded(d)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
@@ -1429,7 +1519,15 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         p.mat_loc = ws;
         p.mat_attn = ws + ns * 2 * sizeof(MT);
     }
-    if ((rc = launched(dispatch_gather<T, 3, TV, TS>(p, rows_vec_ok(p, c.grad_out), stream), "fused backward")) != 0) return rc;
+    if constexpr (kHfBoxDiscrete<PP>) {
+        // this family refuses a grad_value call it cannot finish BEFORE its first kernel (run_value would say the same
+        // behind it)
+        if (want_value && (rc = value_route_status<MT, TV>(p, d, ws + mat, workspace_bytes - (int64_t)mat)) != 0) return rc;
+        rc = launched(dispatch_hfbox_discrete<T, 1, TV, TS>(p, rows_vec_ok(p, c.grad_out), stream), "fused discrete backward");
+    } else {
+        rc = launched(dispatch_gather<T, 3, TV, TS>(p, rows_vec_ok(p, c.grad_out), stream), "fused backward");
+    }
+    if (rc != 0) return rc;
     if (want_value) {
         p.loc = p.mat_loc;
         p.attn = p.mat_attn;
@@ -1544,7 +1642,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, T)                                                        \
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TV, T)                                                 \
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TV, T)                                                \
-    MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)
+    MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)                                                           \
+    MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
 // fp32 reference points and fp32 arithmetic (msda_fwd_fused_f32_sbf16 / _sf16): fused entry points only
@@ -1571,7 +1670,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)                                                       \
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TS, TS)                                                \
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TS, TS)                                               \
-    MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)
+    MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)                                                          \
+    MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TS, TS)
 
 // the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
 // points, TV value rows, TS projection / out / their gradients)
@@ -1649,6 +1749,38 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     {                                                                                                            \
         MSDA_TAKE_BWD_FUSED MSDA_TAKE_COUNTS MSDA_TAKE_BOX_RULE                                                  \
         return msda::run_bwd_fused<T, TV, TS, msda::HfBoxParams>(c);                                             \
+    }
+
+// the box rule in front of DISCRETE sampling (decoder_method = "discrete"): msda_{fwd,bwd}_fused_hfbox_discrete_<suffix>, the
+// hfbox pair's lists without ref_dim, padding_mode, align_corners (discrete sampling has none) and grad_ref_partial (nothing
+// differentiable reaches the box)
+#define MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TV, TS)                                             \
+    extern "C" int msda_fwd_fused_hfbox_discrete_##SUF(const void *value, const int64_t *shapes, const void *proj, \
+                                                       const void *ref, void *out, int64_t B, int64_t I,          \
+                                                       int64_t H, int64_t D, int64_t Q, int64_t L,                \
+                                                       const int32_t *points_per_level, const float *level_scale, \
+                                                       double offset_scale, int64_t value_row_stride,             \
+                                                       void *stream)                                              \
+    {                                                                                                            \
+        const int ref_dim = 4;                                                                                   \
+        msda::Call c; c.value = value; c.shapes = shapes; c.proj = proj; c.ref = ref; c.out = out;               \
+        c.ref_dim = ref_dim; MSDA_TAKE_SIZES MSDA_TAKE_COUNTS MSDA_TAKE_BOX_RULE                                 \
+        return msda::run_fwd_fused<T, TV, TS, msda::HfBoxDiscreteParams>(c);                                     \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_hfbox_discrete_##SUF(const void *grad_out, const void *value,                  \
+                                                       const int64_t *shapes, const void *proj, const void *ref,  \
+                                                       void *grad_value, void *grad_proj, int64_t B, int64_t I,   \
+                                                       int64_t H, int64_t D, int64_t Q, int64_t L,                \
+                                                       const int32_t *points_per_level, const float *level_scale, \
+                                                       double offset_scale, int64_t max_level_cells,              \
+                                                       int64_t value_row_stride, void *workspace,                 \
+                                                       int64_t workspace_bytes, void *stream)                     \
+    {                                                                                                            \
+        const int ref_dim = 4;                                                                                   \
+        msda::Call c; c.grad_out = grad_out; c.value = value; c.shapes = shapes; c.proj = proj; c.ref = ref;     \
+        c.grad_value = grad_value; c.grad_proj = grad_proj; c.ref_dim = ref_dim;                                 \
+        MSDA_TAKE_SIZES MSDA_TAKE_WORKSPACE MSDA_TAKE_COUNTS MSDA_TAKE_BOX_RULE                                  \
+        return msda::run_bwd_fused<T, TV, TS, msda::HfBoxDiscreteParams>(c);                                     \
     }
 
 // the value-mask twins: msda_{fwd,bwd}_masked_<suffix> and msda_{fwd,bwd}_fused_levelref_masked_<suffix> — the twins'

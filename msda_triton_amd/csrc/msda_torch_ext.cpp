@@ -9,9 +9,10 @@
 // Layout: every family of entry points (msda_fwd<family>_<dtype> / msda_bwd<family>_<dtype>) is one MSDA_FAMILY table
 // line — the dtype rule is written once, in suffix_of — and one thin torch::autograd::Function class, which names its
 // table, its workspace query and the arguments its entry points take between the problem's dimensions and
-// value_row_stride.  The bodies are shared: node_forward for all seven, sampling_backward for the nodes over sampling
+// value_row_stride.  The bodies are shared: node_forward for all eight, sampling_backward for the nodes over sampling
 // points and weights (MSDAFunction, MSDARaggedFunction, MSDADiscreteFunction), fused_backward for the module cores with
-// the prologue fused in (MSDAFused*Function).  Behind them, the row-range launches of the row-sharded operator.
+// the prologue fused in (MSDAFused*Function; the box rule's discrete node has no reference-point partials and a backward
+// of its own).  Behind them, the row-range launches of the row-sharded operator.
 // Reference counterpart: _TritonMultiscaleDeformableAttentionFunction, src/msda_triton/frontend.py:108-142.
 #include <torch/extension.h>
 #include <torch/csrc/autograd/functions/basic_ops.h>
@@ -70,6 +71,7 @@ MSDA_FAMILY(kDiscrete, _discrete)
 MSDA_FAMILY(kFused, _fused)
 MSDA_FAMILY(kFusedRagged, _fused_ragged)
 MSDA_FAMILY(kFusedHfBox, _fused_hfbox)
+MSDA_FAMILY(kFusedHfBoxDiscrete, _fused_hfbox_discrete)
 MSDA_FAMILY(kFusedLevelRef, _fused_levelref)
 #undef MSDA_FAMILY
 #undef MSDA_PAIR
@@ -127,7 +129,7 @@ int64_t value_batch_bytes(const at::Tensor &img, int64_t vrow)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The seven autograd nodes.  Each takes (img, shapes, a, b, ...): `a`, `b` are the sampling points and attention
+// The eight autograd nodes.  Each takes (img, shapes, a, b, ...): `a`, `b` are the sampling points and attention
 // weights, or — the fused module cores — the raw projection and the reference points.
 // ------------------------------------------------------------------------------------------------------------------
 using torch::autograd::AutogradContext;
@@ -449,6 +451,36 @@ public:
     }
 };
 
+// ... and the same rule in front of discrete sampling (msda_fwd_fused_hfbox_discrete_ / msda_bwd_fused_hfbox_discrete_<dtype>,
+// additions within ABI 12): no padding mode, and no gradient for the boxes — nothing differentiable reaches them, so the
+// backward has no partials to allocate or sum.
+class MSDAFusedHfBoxDiscreteFunction : public torch::autograd::Function<MSDAFusedHfBoxDiscreteFunction> {
+public:
+    static constexpr auto &family = kFusedHfBoxDiscrete;
+    static constexpr auto workspace_bytes = &msda_bwd_fused_hfbox_discrete_workspace_bytes;
+    static constexpr size_t arguments = 8;
+    static auto samples(const Call &c) { return c.per_level(); }
+    static auto mode(const Call &c) { return std::make_tuple(c.scale.data(), c.offset_scale); }
+    static at::Tensor forward(AutogradContext *ctx, const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj,
+                              const at::Tensor &ref, int64_t level_cells, const std::vector<int64_t> &counts,
+                              const std::vector<double> &level_scale, double offset_scale)
+    {
+        TORCH_CHECK_VALUE(level_scale.size() == counts.size(), "level_scale and points_per_level differ in length");
+        return node_forward<MSDAFusedHfBoxDiscreteFunction>(ctx, img, shapes, proj, ref,
+                                                            {0, false, level_cells, counts, level_scale, offset_scale});
+    }
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
+    {
+        const Call c = saved_call(ctx);
+        const at::Tensor gout = grad_out_as(grads[0], c.a.scalar_type());
+        at::Tensor g_proj = at::empty_like(c.a);
+        ValueGrad v;
+        if (ctx->needs_input_grad(0)) v = value_grad<MSDAFusedHfBoxDiscreteFunction>(c, false);
+        launch_backward<MSDAFusedHfBoxDiscreteFunction>(c, gout, v, std::make_tuple(ptr_or_null(v.g_img), g_proj.data_ptr()));
+        return node_grads<MSDAFusedHfBoxDiscreteFunction>(ctx, grads, v.g_img, g_proj, at::Tensor());
+    }
+};
+
 // ... for per-level reference points and transformers' point rule (msda_fwd_fused_levelref_ / msda_bwd_fused_levelref_<dtype>,
 // additions within ABI 12): ref [B, Q, L, ref_dim].  The workspace is the uniform fused pair's.
 class MSDAFusedLevelRefFunction : public torch::autograd::Function<MSDAFusedLevelRefFunction> {
@@ -720,6 +752,13 @@ at::Tensor msda_fused_hfbox(const at::Tensor &img, const at::Tensor &shapes, con
                                          level_scale, offset_scale);
 }
 
+at::Tensor msda_fused_hfbox_discrete(const at::Tensor &img, const at::Tensor &shapes, const at::Tensor &proj,
+                                     const at::Tensor &ref, int64_t level_cells, const std::vector<int64_t> &counts,
+                                     const std::vector<double> &level_scale, double offset_scale)
+{
+    return MSDAFusedHfBoxDiscreteFunction::apply(img, shapes, proj, ref, level_cells, counts, level_scale, offset_scale);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -753,6 +792,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
           pybind11::arg("padding_mode"), pybind11::arg("align_corners"), pybind11::arg("level_cells"),
           pybind11::arg("points_per_level"), pybind11::arg("level_scale"), pybind11::arg("offset_scale"));
+    // (in a submodule: the top-level callables are a recorded list that callers and tests compare against exactly)
+    auto box_discrete = m.def_submodule("box_discrete", "Hugging Face's box rule in front of discrete sampling");
+    box_discrete.def(
+        "msda_fused_hfbox_discrete", &msda_fused_hfbox_discrete,
+        "Hugging Face's box prologue fused in front of discrete sampling: boxes [B,Q,4] (differentiable in img and proj)",
+        pybind11::arg("img"), pybind11::arg("shapes"), pybind11::arg("proj"), pybind11::arg("reference_points"),
+        pybind11::arg("level_cells"), pybind11::arg("points_per_level"), pybind11::arg("level_scale"),
+        pybind11::arg("offset_scale"));
     m.def("msda_rows", &msda_rows,
           "rows [r0, r1) of the flattened (b, q) row space computed in `chunks` pieces into a full [B,Q,H,D] result "
           "(differentiable; the row-sharded operator without its exchange)",

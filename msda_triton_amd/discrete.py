@@ -33,6 +33,7 @@ from . import functional as F
 from .ragged import _counts_array, _prepare, check_points_per_level
 
 SAMPLING_MODES = ("bilinear", "discrete")
+FUSED_BOX_MAX_LEVELS = 8  # msda_*_fused_hfbox_discrete_<dtype>: the level scales ride in the kernel arguments
 
 
 def check_discrete_mode(padding_mode, align_corners) -> None:
@@ -152,6 +153,181 @@ class _HipDiscreteFunction(Function):
         g_img, g_att = discrete_hip_bwd(out_grad, img, img_shapes, sampling_points, attention_weights, ctx.counts,
                                         (ctx.needs_input_grad[0], ctx.needs_input_grad[3]), ctx.level_cells)
         return g_img, None, None, g_att, None, None  # (the sampling points: no gradient in this mode)
+
+
+# ------------------------------------------------------------------------------------------
+# Hugging Face's box rule in front of discrete sampling (D-FINE / DEIMv2 / RT-DETRv2, decoder_method="discrete"):
+# functional.fused_hf_box_core(..., sampling_mode="discrete") on msda_*_fused_hfbox_discrete_<suffix>
+# ------------------------------------------------------------------------------------------
+def hf_box_discrete_hip_fwd_fused(img, img_shapes, proj, reference_points, counts, offset_scale: float = 0.5):
+    """Forward with the softmax, transformers' box rule and the pixel choice done in the kernel
+    (``msda_fwd_fused_hfbox_discrete_<suffix>``; ``reference_points`` ``[B, Q, 4]``).  None when the library declines (more
+    than 8 levels) or predates these entry points: the caller then composes the prologue around the discrete operator."""
+    from .ragged import _scale_array
+    if not _lib.has_fused_hfbox_discrete() or len(counts) > FUSED_BOX_MAX_LEVELS:  # (declined without a call)
+        return None
+    B, I, H, D = img.shape
+    B2, Q, H2, S, _ = proj.shape
+    if (B2, H2) != (B, H) or tuple(reference_points.shape) != (B, Q, 4):
+        raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
+                         f"reference_points {tuple(reference_points.shape)}")
+    F._check_devices(img, img_shapes, proj, reference_points)
+    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    shapes = F._shapes_i64(img_shapes)
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    fn = getattr(_lib.load(), f"msda_fwd_fused_hfbox_discrete_{suf}")
+
+    def call():
+        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+                  B, I, H, D, Q, len(counts), _counts_array(counts), _scale_array(counts), float(offset_scale), vrow,
+                  F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_fwd_fused_hfbox_discrete", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_fwd_fused_hfbox_discrete_{suf}")
+    return out
+
+
+def hf_box_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, counts, offset_scale: float = 0.5,
+                                  need_img: bool = True, level_cells: int = 0, parked_points: bool = False):
+    """Backward of the discrete box core (``msda_bwd_fused_hfbox_discrete_<suffix>``): ``(img_grad | None, proj_grad)`` —
+    the offset slots of ``proj_grad`` are stored zeros and the boxes have no gradient —, or None when the library declines
+    (nothing was launched).  ``parked_points`` (with ``need_img``): two more elements, the sampling points
+    ``[B, Q, H, S, 2]`` and the softmaxed weights ``[B, Q, H, S]`` the kernel left at the head of its workspace for the
+    grad_value passes, in the arithmetic dtype (float32 for the 16-bit operators)."""
+    from .ragged import _scale_array
+    if not _lib.has_fused_hfbox_discrete() or len(counts) > FUSED_BOX_MAX_LEVELS:  # (declined without a call)
+        return None
+    B, I, H, D = img.shape
+    _, Q, _, S, _ = proj.shape
+    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
+    cdt = proj.dtype
+    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
+    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and boxes fp32)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    out_grad = out_grad.contiguous()
+    if out_grad.dtype != cdt:
+        out_grad = out_grad.to(cdt)
+    shapes = F._shapes_i64(img_shapes)
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
+    lib = _lib.load()
+    fn = getattr(lib, f"msda_bwd_fused_hfbox_discrete_{suf}")
+    arr, scale = _counts_array(counts), _scale_array(counts)
+    ws, ws_bytes = None, 0
+    level_cells = int(level_cells)
+    if need_img:  # (a frozen value pyramid needs no workspace at all)
+        ws_bytes = int(lib.msda_bwd_fused_hfbox_discrete_workspace_bytes(
+            B, I, H, D, Q, len(counts), arr, 4 if storage else proj.element_size(), img.element_size(), level_cells, 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
+
+    def call():
+        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), B, I, H, D, Q, len(counts), arr, scale,
+                  float(offset_scale), level_cells, vrow, ws.data_ptr() if ws is not None else None, ws_bytes,
+                  F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_bwd_fused_hfbox_discrete", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_bwd_fused_hfbox_discrete_{suf}")
+    res = (g_img, g_proj)
+    if parked_points and ws is not None:
+        pdt = torch.float32 if reference_points.element_size() == 2 else reference_points.dtype
+        ns = B * Q * H * S
+        res += (ws[:ns * 2 * pdt.itemsize].view(pdt).view(B, Q, H, S, 2).clone(),
+                ws[ns * 2 * pdt.itemsize:ns * 3 * pdt.itemsize].view(pdt).view(B, Q, H, S).clone())
+    return res
+
+
+def _hf_box_discrete_composition(img, img_shapes, proj, reference_points, counts, offset_scale, level_shapes):
+    """transformers' box prologue as PyTorch ops around the discrete operator (host tensors, traced calls, whatever the
+    fused kernels do not take).  16-bit value / projection next to fp32 boxes: the prologue in fp32, the mixed-storage
+    operator, the result back in the projection's dtype."""
+    if img.device.type == "cuda" and F.fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype):
+        pts, att = F.hf_box_sampling_inputs(proj.to(reference_points.dtype), reference_points, counts, offset_scale)
+        return discrete_multiscale_deformable_attention(img, img_shapes, pts, att, "border", False, counts,
+                                                        level_shapes).to(proj.dtype)
+    pts, att = F.hf_box_sampling_inputs(proj, reference_points, counts, offset_scale)
+    return discrete_multiscale_deformable_attention(img, img_shapes, pts, att, "border", False, counts, level_shapes)
+
+
+class _HipFusedHfBoxDiscreteFunction(Function):
+    """The discrete box core on ``msda_*_fused_hfbox_discrete_<dtype>`` (autocast: in fp32; the storage suffixes).  When
+    the library declines, the prologue runs in PyTorch around the discrete operator's kernels."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, img, img_shapes, proj, reference_points, counts, offset_scale, level_cells=0):
+        ctx.level_cells, ctx.counts, ctx.offset_scale = int(level_cells), counts, float(offset_scale)
+        out = hf_box_discrete_hip_fwd_fused(img, img_shapes, proj, reference_points, counts, offset_scale)
+        ctx.fused = out is not None  # the backward has the same limits: do not ask twice
+        if out is None:
+            pts, att = F.hf_box_sampling_inputs(proj.to(reference_points.dtype), reference_points, counts, offset_scale)
+            out = discrete_hip_fwd(img, img_shapes, pts, att, counts).to(proj.dtype)
+        ctx.save_for_backward(img, img_shapes, proj, reference_points)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, out_grad):
+        img, img_shapes, proj, reference_points = ctx.saved_tensors
+        need_img, _, need_proj = ctx.needs_input_grad[:3]
+        counts = ctx.counts
+        if ctx.fused and need_proj:
+            res = hf_box_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, counts, ctx.offset_scale,
+                                                need_img, level_cells=ctx.level_cells)
+            if res is not None:
+                return res[0], None, res[1], None, None, None, None
+        with torch.enable_grad():
+            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
+            pts, att = F.hf_box_sampling_inputs(proj_, reference_points.detach(), counts, ctx.offset_scale)
+        g_img, g_att = discrete_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(), counts,
+                                        (need_img, need_proj), ctx.level_cells)
+        g_proj = None
+        if need_proj:
+            g_proj = torch.autograd.grad([att], [proj_], [g_att])[0].to(proj.dtype)
+        return g_img, None, g_proj, None, None, None, None
+
+
+def fused_hf_box_discrete_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale=0.5,
+                               level_shapes=None) -> torch.Tensor:
+    """:func:`msda_triton_amd.functional.fused_hf_box_core` with ``sampling_mode="discrete"``.  Routing mirrors the
+    bilinear core's: host tensors -> the composition; GPU -> the fused kernels (the C++ node, else the Python
+    ``Function``); traced -> the composition over the registered discrete custom ops."""
+    from .ragged import _box_ref, check_hf_box_args
+    counts = check_hf_box_args(img_shapes, proj, reference_points, points_per_level)
+    offset_scale = float(offset_scale)
+    B, Q, H, S, _ = proj.shape
+    on_gpu = img.device.type == "cuda"
+    if on_gpu and img_shapes.device != img.device:
+        img_shapes = img_shapes.to(img.device)  # (a handful of integers: follow `img`, as the other cores do)
+    floating = img.is_floating_point() and proj.is_floating_point() and reference_points.is_floating_point()
+    if on_gpu and floating and not torch.compiler.is_compiling() and _lib.has_fused_hfbox_discrete() \
+            and len(counts) <= FUSED_BOX_MAX_LEVELS:
+        F._check_devices(img, proj, reference_points)
+        same = F.dtypes_supported(img.dtype, proj.dtype) and reference_points.dtype == proj.dtype
+        if F._autocast_on() or F.fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype) or same:
+            level_cells = F.level_cells_of(level_shapes, len(counts), img.shape[1])
+            ref = _box_ref(reference_points)
+            if img.requires_grad and torch.is_grad_enabled():
+                check_backward_supported(img, proj, counts)
+            node = getattr(getattr(_ext.load(), "box_discrete", None), "msda_fused_hfbox_discrete", None)
+            if same and node is not None and F.KernelTimer.active is None \
+                    and not F._autocast_on() and img.dim() == 4 and (img.shape[0], img.shape[2]) == (B, H):
+                # the C++ autograd node: decoder-sized calls spend more host time than device time
+                return node(img, F._shapes_i64(img_shapes), proj, ref, level_cells, list(counts),
+                            list(F.hf_box_level_scale(counts)), offset_scale)
+            return _HipFusedHfBoxDiscreteFunction.apply(img, img_shapes, proj, ref, counts, offset_scale, level_cells)
+    # host tensors, tracing (the discrete operator's registered custom ops) and everything the checks above did not take
+    return _hf_box_discrete_composition(img, img_shapes, proj, reference_points, counts, offset_scale, level_shapes)
 
 
 def discrete_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,

@@ -1121,20 +1121,42 @@ def hf_box_sampling_inputs(proj: torch.Tensor, reference_points: torch.Tensor, p
 
 
 def fused_hf_box_core(img, img_shapes, proj, reference_points, points_per_level, offset_scale: float = 0.5,
-                      padding_mode: str = "zeros", align_corners: bool = False, level_shapes=None,
-                      value_mask=None, query_mask=None) -> torch.Tensor:
+                      padding_mode: Optional[str] = None, align_corners: Optional[bool] = None, level_shapes=None,
+                      value_mask=None, query_mask=None, sampling_mode: str = "bilinear") -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *hf_box_sampling_inputs(proj, ...), points_per_level=...)``: the
     core of a D-FINE / DEIMv2 / RT-DETRv2 attention module between its projections — value pyramid ``[B, I, H, D]``, raw
     projection ``[B, Q, H, S, 3]`` (level-major), boxes ``[B, Q, 4]`` or ``[B, Q, 1, 4]``.  On GPU tensors the prologue and
     its chain rule run inside the gather kernels (``msda_*_fused_hfbox_<dtype>``, equal counts included); on host tensors,
     while traced and where the library declines it is exactly that composition (:mod:`msda_triton_amd.ragged`).
     ``value_mask``: ``[B, I]``, non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels.
-    ``query_mask``: ``[B, Q]``, non-zero = the query is real; composed likewise (:func:`apply_query_mask`)."""
+    ``query_mask``: ``[B, Q]``, non-zero = the query is real; composed likewise (:func:`apply_query_mask`).
+    ``padding_mode`` / ``align_corners`` default to ``"zeros"`` / ``False``, what these modules sample with.
+
+    ``sampling_mode="discrete"`` (the modules' ``decoder_method="discrete"``): the same prologue in front of
+    :mod:`msda_triton_amd.discrete` — ``multiscale_deformable_attention(img, img_shapes, *hf_box_sampling_inputs(proj, ...),
+    "border", False, points_per_level=..., sampling_mode="discrete")``, on GPU tensors inside
+    ``msda_*_fused_hfbox_discrete_<dtype>``.  ``padding_mode`` / ``align_corners`` have no meaning there: leave them out, or
+    pass ``"border"`` / ``False``.  ``reference_points`` gets no gradient (``None``) and the offset slots of ``proj`` exact
+    zeros: the pixel index is an integer.  The kernels form the point in fp32 from the stored values; for all-16-bit
+    tensors transformers forms it in 16 bits and can land on the neighbouring pixel."""
+    if sampling_mode not in ("bilinear", "discrete"):
+        raise ValueError(f'`sampling_mode` should be "bilinear" or "discrete", but got {sampling_mode!r}.')
+    if sampling_mode == "discrete":
+        from .discrete import check_discrete_mode
+        check_discrete_mode("border" if padding_mode is None else padding_mode, bool(align_corners))
+        padding_mode, align_corners = "border", False
+    else:
+        padding_mode = "zeros" if padding_mode is None else padding_mode
+        align_corners = False if align_corners is None else align_corners
     if query_mask is not None:
         out = fused_hf_box_core(img, img_shapes, apply_query_mask(proj, query_mask, 0.0),
                                 apply_query_mask(reference_points, query_mask, 0.5), points_per_level, offset_scale,
-                                padding_mode, align_corners, level_shapes, value_mask)
+                                padding_mode, align_corners, level_shapes, value_mask, sampling_mode=sampling_mode)
         return apply_query_mask(out, query_mask, 0.0)
+    if sampling_mode == "discrete":
+        from .discrete import fused_hf_box_discrete_core
+        return fused_hf_box_discrete_core(apply_value_mask(img, value_mask), img_shapes, proj, reference_points,
+                                          points_per_level, offset_scale, level_shapes)
     from .ragged import fused_hf_box_module_core
     return fused_hf_box_module_core(apply_value_mask(img, value_mask), img_shapes, proj, reference_points, points_per_level, offset_scale, padding_mode,
                                     align_corners, level_shapes)

@@ -262,7 +262,11 @@ class FusedHFBoxDeformableAttention(FusedHFDeformableAttention):
 
     The second element of the returned pair is ``None``.  The original forward (over the adapter's core, where the module
     carries one) runs when attention weights are asked for (``return_attention_weights`` / ``output_attentions=True``),
-    for 2-d reference points, for a reference-point axis of length other than 1 and for ``method="discrete"``."""
+    for 2-d reference points, for a reference-point axis of length other than 1 and for ``method="discrete"`` — unless
+    the module was wrapped FOR that method (``replace_hf_msda(model, fused=True, fuse_discrete=True)``): it then runs
+    ``fused_hf_box_core(..., sampling_mode="discrete")``, and takes the ``sampling_offsets`` rows of its one GEMM from
+    detached parameters, because transformers gives ``sampling_offsets`` no gradient in this mode (the pixel index is an
+    integer): their ``.grad`` stays ``None`` and ``hidden_states`` receives exact zeros from those slots."""
 
     def _proj_rows(self, device) -> torch.Tensor:
         # row (h, s, k) of the one projection: k < 2 the offset rows of `sampling_offsets`, k == 2 the logit row of
@@ -283,8 +287,10 @@ class FusedHFBoxDeformableAttention(FusedHFDeformableAttention):
                 type(self)._msda_arg_names = names
             kwargs.update(zip(names, args))
         reference_points = kwargs.get("reference_points")
+        method = _first_attr(self, "decoder_method", "method")
+        discrete = method == "discrete" and self.__dict__.get("_msda_fused_discrete", False)
         if self.return_attention_weights or kwargs.get("output_attentions") or \
-                _first_attr(self, "decoder_method", "method") != "default" or \
+                (method != "default" and not discrete) or \
                 not torch.is_tensor(reference_points) or reference_points.dim() != 4 or \
                 reference_points.shape[2] != 1 or reference_points.shape[-1] != 4:
             return super(FusedHFDeformableAttention, self).forward(hidden_states, attention_mask, **kwargs)
@@ -308,8 +314,10 @@ class FusedHFBoxDeformableAttention(FusedHFDeformableAttention):
         so, aw = self.sampling_offsets, self.attention_weights
         if (so.bias is None) != (aw.bias is None):
             raise ValueError("`sampling_offsets` and `attention_weights` should both have a bias or neither")
-        weight = torch.cat([so.weight, aw.weight], 0).index_select(0, rows)
-        bias = torch.cat([so.bias, aw.bias], 0).index_select(0, rows) if so.bias is not None else None
+        so_weight, so_bias = (so.weight.detach(), so.bias.detach() if so.bias is not None else None) if discrete \
+            else (so.weight, so.bias)  # (discrete: no gradient reaches the offsets, so none is formed for their parameters)
+        weight = torch.cat([so_weight, aw.weight], 0).index_select(0, rows)
+        bias = torch.cat([so_bias, aw.bias], 0).index_select(0, rows) if so.bias is not None else None
         counts = [int(p) for p in _first_attr(self, "num_points_list", "n_points_list")]
         proj = nn.functional.linear(hidden_states, weight, bias).view(batch_size, num_queries, self.n_heads, sum(counts), 3)
         level_shapes = spatial_shapes_list if isinstance(spatial_shapes_list, (list, tuple)) else None
@@ -317,20 +325,21 @@ class FusedHFBoxDeformableAttention(FusedHFDeformableAttention):
         if not torch.is_tensor(shapes):
             shapes = _shapes_tensor(shapes if shapes is not None else spatial_shapes_list, value.device)
         offset_scale = float(self.offset_scale)
+        mode = ("border", False, "discrete") if discrete else ("zeros", False, "bilinear")
         if value.device.type == "cuda" and value.dtype in (torch.bfloat16, torch.float16) and proj.dtype == value.dtype \
                 and reference_points.dtype == torch.float32:
             # what autocast hands the core: 16-bit value and projection next to fp32 boxes — the module-storage kernels
             # (fp32 arithmetic, 16-bit result), called outside autocast so that nothing is cast to fp32
             with torch.autocast("cuda", enabled=False):
-                out = fused_hf_box_core(value, shapes, proj, reference_points, counts, offset_scale, "zeros", False,
-                                        level_shapes=level_shapes)
+                out = fused_hf_box_core(value, shapes, proj, reference_points, counts, offset_scale, *mode[:2],
+                                        level_shapes=level_shapes, sampling_mode=mode[2])
         else:
             if proj.dtype != value.dtype:
                 proj = proj.to(value.dtype)
             if reference_points.dtype != value.dtype:
                 reference_points = reference_points.to(value.dtype)
-            out = fused_hf_box_core(value, shapes, proj, reference_points, counts, offset_scale, "zeros", False,
-                                    level_shapes=level_shapes)
+            out = fused_hf_box_core(value, shapes, proj, reference_points, counts, offset_scale, *mode[:2],
+                                    level_shapes=level_shapes, sampling_mode=mode[2])
         out = out.flatten(2)
         return (output_proj(out) if output_proj is not None else out), None
 
@@ -338,15 +347,16 @@ class FusedHFBoxDeformableAttention(FusedHFDeformableAttention):
 _FUSED_BOX_ATTRS = ("sampling_offsets", "attention_weights", "n_heads", "offset_scale")
 
 
-def _wrap_fused_box(module: nn.Module) -> bool:
+def _wrap_fused_box(module: nn.Module, discrete: bool = False) -> bool:
     """Wrap a module with per-level point counts and the box rule, matched by attribute names.  The scale buffer is
     compared ONCE, here, with float32(1 / P_l) repeated P_l times — a loaded checkpoint could carry other values, and the
-    kernels take the scale from the counts."""
+    kernels take the scale from the counts.  ``discrete``: modules whose method is ``"discrete"`` are wrapped too."""
     if isinstance(module, FusedHFDeformableAttention) or not all(hasattr(module, a) for a in _FUSED_BOX_ATTRS):
         return False
     counts, scale = _first_attr(module, "num_points_list", "n_points_list"), _first_attr(module, "num_points_scale", "n_points_scale")
+    method = _first_attr(module, "decoder_method", "method")
     if not isinstance(counts, (list, tuple)) or not torch.is_tensor(scale) or not isinstance(module.offset_scale, (int, float)) \
-            or _first_attr(module, "decoder_method", "method") != "default":
+            or not (method == "default" or (discrete and method == "discrete")):
         return False
     counts = [int(p) for p in counts]
     if not counts or any(p < 1 for p in counts):
@@ -365,10 +375,13 @@ def _wrap_fused_box(module: nn.Module) -> bool:
     if fused is None:
         fused = _FUSED_CLASSES[cls] = type("Fused" + cls.__name__, (FusedHFBoxDeformableAttention, cls), {})
     module.__class__ = fused
+    if method == "discrete":
+        module.__dict__["_msda_fused_discrete"] = True  # (an instance attribute: state_dict stays the HF module's)
     return True
 
 
-def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = False, skip_padded_queries: bool = False) -> int:
+def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = False, skip_padded_queries: bool = False,
+                    fuse_discrete: bool = False) -> int:
     """Swap every HF ``MultiScaleDeformableAttention`` submodule of ``model`` for the adapter, and set
     :func:`ms_deformable_attn_core` on every module that carries an ``ms_deformable_attn_core`` attribute with
     ``decoder_method == "default"`` (D-FINE / DEIMv2; ``"discrete"`` modules are left alone).  With ``discrete=True``
@@ -379,7 +392,11 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
     class) additionally becomes a :class:`FusedHFDeformableAttention`, and every module that has ``sampling_offsets``,
     ``attention_weights``, ``n_heads``, ``offset_scale``, a point list (``num_points_list`` / ``n_points_list``), a scale
     buffer (``num_points_scale`` / ``n_points_scale``) equal to ``float32(1 / P_l)`` repeated ``P_l`` times and method
-    ``"default"`` (D-FINE, DEIMv2, RT-DETRv2; by these names as well) a :class:`FusedHFBoxDeformableAttention`.  Returns
+    ``"default"`` (D-FINE, DEIMv2, RT-DETRv2; by these names as well) a :class:`FusedHFBoxDeformableAttention` — with
+    ``fused=True, fuse_discrete=True`` (opt-in, no effect without ``fused=True``) also those whose method is
+    ``"discrete"``, which then run the box rule's discrete kernels.  ``fused=True`` leaves them unwrapped, with or without
+    ``discrete=True``, as it always did; ``discrete=True`` stays the switch for their cores, which a wrapped module still
+    uses when it runs its original forward, so a discrete D-FINE model takes all three flags.  Returns
     the number of modules replaced, patched or wrapped: without ``fused`` exactly what it always returned, with it that
     number plus the modules wrapped (a D-FINE decoder layer then counts twice, once for its core and once for the
     wrapper).  ``skip_padded_queries=True`` (opt-in, no effect without ``fused=True``) sets
@@ -403,7 +420,7 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
             count += 1
     if fused:
         for module in list(model.modules()):
-            if _wrap_fused(module) or _wrap_fused_box(module):
+            if _wrap_fused(module) or _wrap_fused_box(module, fuse_discrete):
                 count += 1
             if skip_padded_queries and isinstance(module, FusedHFDeformableAttention) and \
                     not isinstance(module, FusedHFBoxDeformableAttention):
