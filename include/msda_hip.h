@@ -477,6 +477,60 @@ MSDA_QUERY_MASK_FUSED(f32_vbf16) MSDA_QUERY_MASK_FUSED(f32_vf16) MSDA_QUERY_MASK
 #undef MSDA_QUERY_MASK_FUSED
 
 /*
+ * Both padding masks inside the MODULE's own fused kernels — ADDITIONS WITHIN ABI 12, probed by symbol:
+ * msda_fwd_fused_masked_<suffix> / msda_bwd_fused_masked_<suffix> (one reference point per query, uniform point count) and
+ * msda_fwd_fused_ragged_masked_<suffix> / msda_bwd_fused_ragged_masked_<suffix> (per-level point counts), the eight suffixes
+ * of the fused pairs.  Each list is its unmasked twin's (msda_*_fused_<suffix>, msda_*_fused_ragged_<suffix>) with two
+ * arguments directly behind `value`:
+ *
+ *   value_mask   [B, I] bytes, non-zero = the pixel is real.  NULL is MSDA_ERR_BAD_ARG, refused before any other argument
+ *                is looked at (a caller with a query mask only passes all ones)
+ *   query_mask   [B, Q] bytes, non-zero = the query is real.  NULL = every query is real: the call keeps what a query mask
+ *                costs it (below)
+ *
+ * The contracts are the ones stated above for the value mask (out, grad_proj, grad_ref_partial: the twin's on
+ * where(mask, value, 0), bit for bit; grad_value: where(mask, the twin's, +0)) and for the query mask (real queries' rows
+ * unchanged bit for bit, masked queries' rows of out / grad_proj / grad_ref_partial stored as zeros with no bit of their
+ * inputs read, grad_value the sum over the real queries' samples).  The hooks are those of the per-level-reference pair:
+ * mask_taps behind make_taps in phase 1, the per-slice ballot of live units before phase 0, the masked finish pass / the
+ * single-launch kernel's zero rows and skipped walks, and — with a query mask only — the count and place passes on the
+ * masked kernarg.  With a query mask the fused backward takes the 256-thread sample-gradient kernel (the 1024-thread one
+ * with LDS-served levels has no room for the hook: "sample_variant" says 0); the forward may still serve levels from LDS.
+ * The one-wave-per-unit forward is never chosen.  Size guards, alignment, ref_dim, msda_fused_lp_limit, L <= 8 for the
+ * per-level pair (MSDA_ERR_UNSUPPORTED), their order of precedence and the workspaces are the twins':
+ * msda_bwd_fused_workspace_bytes / msda_bwd_fused_ragged_workspace_bytes answer for these calls, MSDA_WS_PASSES(n) included
+ * (both mask pointers advance with the batch groups).  Everything is answered before anything is launched.
+ */
+#define MSDA_MODULE_MASK(SUF)                                                                          \
+    MSDA_API int msda_fwd_fused_masked_##SUF(const void *value, const uint8_t *value_mask,          \
+                       const uint8_t *query_mask, const int64_t *shapes, const void *proj,          \
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
+                       int align_corners, int64_t value_row_stride, void *stream);                  \
+    MSDA_API int msda_bwd_fused_masked_##SUF(const void *grad_out, const void *value,               \
+                       const uint8_t *value_mask, const uint8_t *query_mask, const int64_t *shapes, \
+                       const void *proj, const void *ref, void *grad_value, void *grad_proj,        \
+                       void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D,          \
+                       int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);                     \
+    MSDA_API int msda_fwd_fused_ragged_masked_##SUF(const void *value, const uint8_t *value_mask,   \
+                       const uint8_t *query_mask, const int64_t *shapes, const void *proj,          \
+                       const void *ref, void *out, int64_t B, int64_t I, int64_t H, int64_t D,      \
+                       int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,          \
+                       int padding_mode, int align_corners, int64_t value_row_stride, void *stream);\
+    MSDA_API int msda_bwd_fused_ragged_masked_##SUF(const void *grad_out, const void *value,        \
+                       const uint8_t *value_mask, const uint8_t *query_mask, const int64_t *shapes, \
+                       const void *proj, const void *ref, void *grad_value, void *grad_proj,        \
+                       void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D,          \
+                       int64_t Q, int64_t L, const int32_t *points_per_level, int ref_dim,          \
+                       int padding_mode, int align_corners, int64_t max_level_cells,                \
+                       int64_t value_row_stride, void *workspace, int64_t workspace_bytes, void *stream);
+MSDA_MODULE_MASK(f32) MSDA_MODULE_MASK(f16) MSDA_MODULE_MASK(bf16) MSDA_MODULE_MASK(f64)
+MSDA_MODULE_MASK(f32_vbf16) MSDA_MODULE_MASK(f32_vf16) MSDA_MODULE_MASK(f32_sbf16) MSDA_MODULE_MASK(f32_sf16)
+#undef MSDA_MODULE_MASK
+
+/*
  * Hugging Face's box rule in front of DISCRETE sampling (D-FINE / DEIMv2 / RT-DETRv2 with decoder_method = "discrete") —
  * ADDITIONS WITHIN ABI 12, probed by symbol: msda_fwd_fused_hfbox_discrete_<suffix> / msda_bwd_fused_hfbox_discrete_<suffix>
  * (the eight suffixes of the hfbox pair) and msda_bwd_fused_hfbox_discrete_workspace_bytes.  The argument lists are the

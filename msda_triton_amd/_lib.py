@@ -61,6 +61,13 @@ HFBOX_DISCRETE_SYMBOLS = tuple(
     + ["msda_bwd_fused_hfbox_discrete_workspace_bytes"]
 )
 
+# ... and both padding masks inside the module's own fused pairs (has_module_masks): the fused and the fused ragged pairs'
+# lists with `value_mask`, `query_mask` behind `value`
+MODULE_MASK_SYMBOLS = tuple(
+    [f"msda_{d}_fused_masked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+    + [f"msda_{d}_fused_ragged_masked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -237,6 +244,22 @@ def load():
                 ghd.argtypes = [vp] * 7 + [i64] * 6 + [vp, vp, cd, i64, i64, vp, i64, vp]
             lib.msda_bwd_fused_hfbox_discrete_workspace_bytes.restype = i64
             lib.msda_bwd_fused_hfbox_discrete_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
+        # both masks inside the module's own fused pairs: additions within ABI 12 (has_module_masks); the fused / fused
+        # ragged pairs' lists with `value_mask`, `query_mask` behind `value`
+        if hasattr(lib, "msda_bwd_fused_ragged_masked_f32"):
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                fmm = getattr(lib, f"msda_fwd_fused_masked_{suf}")
+                fmm.restype = ci
+                fmm.argtypes = [vp] * 7 + [i64] * 7 + [ci, ci, ci, i64, vp]
+                gmm = getattr(lib, f"msda_bwd_fused_masked_{suf}")
+                gmm.restype = ci
+                gmm.argtypes = [vp] * 10 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
+                frm = getattr(lib, f"msda_fwd_fused_ragged_masked_{suf}")
+                frm.restype = ci
+                frm.argtypes = [vp] * 7 + [i64] * 6 + [vp, ci, ci, ci, i64, vp]
+                grm = getattr(lib, f"msda_bwd_fused_ragged_masked_{suf}")
+                grm.restype = ci
+                grm.argtypes = [vp] * 10 + [i64] * 6 + [vp, ci, ci, ci, i64, i64, vp, i64, vp]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -305,6 +328,13 @@ def has_query_mask() -> bool:
     msda_fwd_fused_levelref_qmasked_<dtype> ..., additions within ABI 12, found by symbol)?  Without them a call with a
     query mask composes ``functional.apply_query_mask`` with its route."""
     return hasattr(load(), "msda_bwd_qmasked_f32")
+
+
+def has_module_masks() -> bool:
+    """Does the loaded library have the module's own fused pairs with both padding masks (msda_fwd_fused_masked_<dtype> ...,
+    msda_fwd_fused_ragged_masked_<dtype> ..., additions within ABI 12, found by symbol)?  Without them a masked module call
+    composes ``apply_value_mask`` / ``apply_query_mask`` with the unmasked fused route."""
+    return hasattr(load(), "msda_bwd_fused_ragged_masked_f32")
 
 
 def check(rc: int, what: str) -> None:

@@ -209,7 +209,15 @@ struct MaskedParams : Params {
     const uint8_t *qmask;
 };
 struct LevelRefMaskedParams : MaskedParams {};
-template <typename PP> constexpr bool kValueMask = std::is_base_of<MaskedParams, PP>::value;
+// ... and for per-level point counts (msda_*_fused_ragged_masked_<dtype>): the two pointers at the very END, behind the level
+// starts, so that the preloaded front is RaggedParams' and the level scans read their starts where they always did.  The
+// module's uniform fused pair (msda_*_fused_masked_<dtype>) runs on plain MaskedParams: one reference point per query.
+struct RaggedMaskedParams : RaggedParams {
+    const uint8_t *vmask;
+    const uint8_t *qmask;
+};
+template <typename PP>
+constexpr bool kValueMask = std::is_base_of<MaskedParams, PP>::value || std::is_base_of<RaggedMaskedParams, PP>::value;
 // the batch element's query mask bytes (uniform), or NULL: no query mask, or a kernarg without one
 template <typename PP> __device__ __forceinline__ const uint8_t *query_mask_row(const PP &p, int b)
 {

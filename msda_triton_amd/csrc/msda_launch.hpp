@@ -414,8 +414,11 @@ template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T, ty
 }
 
 // does this call carry a query mask (MaskedParams::qmask)?
-inline bool has_query_mask(const MaskedParams &p) { return p.qmask != nullptr; }
-inline bool has_query_mask(const Params &) { return false; }
+template <typename PP> inline bool has_query_mask(const PP &p)
+{
+    if constexpr (kValueMask<PP>) return p.qmask != nullptr;
+    else return false;
+}
 
 template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T, typename PP = Params> inline int launch_gather(PP &p, hipStream_t stream)
 {
@@ -470,7 +473,13 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
     // ... and the module's kernels (fused prologue).  (An early version of the variant had lost over a bf16 pyramid — the
     // module's step 1.09 -> 1.31 ms; with the waves' dynamic slices it wins there as well: fused forward 116-126 -> 75-79 us,
     // fused sample gradients 124-135 -> 115-123 at the c2 shape.)
-    if constexpr (VEC == 4 && sizeof(A) == 4 && (sizeof(T) == 4 || MODE == 0) &&
+    // (the module's uniform masked pair, msda_bwd_fused_masked_<suffix>, with fp32 rows and 8-lane units: the fused
+    // sample-gradient kernel with LDS-served levels sits at the 128-VGPR cap of its 1024-thread workgroup, and mask_taps'
+    // four pixel indices and mask bytes cost that one instantiation 2 vector registers of scratch — it is not instantiated,
+    // and such a call takes the 256-thread kernel below, which has the hook; "sample_variant" says 0.  The 4-lane units, the
+    // 16-bit rows and the per-level-count / per-level-reference kernargs fit.)
+    constexpr bool kNoLdsMaskHook = MODE == 3 && G == 8 && sizeof(TV) == 4 && std::is_same<PP, MaskedParams>::value;
+    if constexpr (VEC == 4 && sizeof(A) == 4 && (sizeof(T) == 4 || MODE == 0) && !kNoLdsMaskHook &&
                   (((MODE == 0 || MODE == 2) && G <= 16) || ((MODE == 1 || MODE == 3) && (G == 4 || G == 8)))) {
         // (fp32 arithmetic; the rows may be 16-bit — the mixed-storage and module-storage kernels: 8-byte pieces, half the LDS)
         const LdsLevelsPlan pl = lds_levels_plan_rt(p, G, sizeof(A), sizeof(TV), MODE == 3, MODE == 1, /*two planes*/ MODE != 1);
@@ -570,6 +579,17 @@ template <typename T, int MODE, typename TV = T, typename TS = T, typename PP = 
 
 // ---- sorted (gather-formulated) grad_value: K1..K5 of msda_value_sorted.hpp ----
 // PP = MaskedParams: the finish pass is the value-mask twin (the gather itself knows no mask)
+// PP = RaggedMaskedParams: the same twin — the finish pass works per pixel and reads no level start, so it takes the call's
+// Params part and its two mask pointers as a MaskedParams (no finish kernels of its own for per-level counts)
+inline const MaskedParams &finish_kernarg(const MaskedParams &p) { return p; }
+inline MaskedParams finish_kernarg(const RaggedMaskedParams &p)
+{
+    MaskedParams m{};
+    static_cast<Params &>(m) = p;
+    m.vmask = p.vmask;
+    m.qmask = p.qmask;
+    return m;
+}
 template <typename T, int VEC, int G, int GB, typename TV = T, typename TS = T, typename PP = Params> inline int launch_value_gather_block(PP &p, hipStream_t stream)
 {
     constexpr int NUG = GB / G;
@@ -600,9 +620,9 @@ template <typename T, int VEC, int G, int GB, typename TV = T, typename TS = T, 
     const ProfileScope prof("msda_value_finish_kernel", stream);
     if constexpr (kValueMask<PP>) {
         if (fp == 64)
-            hipLaunchKernelGGL((msda_value_finish_masked_kernel<T, VEC, G, GB, TV, 64>), g5, dim3(kBlock), 0, stream, static_cast<const MaskedParams &>(p));
+            hipLaunchKernelGGL((msda_value_finish_masked_kernel<T, VEC, G, GB, TV, 64>), g5, dim3(kBlock), 0, stream, finish_kernarg(p));
         else
-            hipLaunchKernelGGL((msda_value_finish_masked_kernel<T, VEC, G, GB, TV, 32>), g5, dim3(kBlock), 0, stream, static_cast<const MaskedParams &>(p));
+            hipLaunchKernelGGL((msda_value_finish_masked_kernel<T, VEC, G, GB, TV, 32>), g5, dim3(kBlock), 0, stream, finish_kernarg(p));
     } else {
         if (fp == 64)
             hipLaunchKernelGGL((msda_value_finish_kernel<T, VEC, G, GB, TV, 64>), g5, dim3(kBlock), 0, stream, static_cast<const Params &>(p));
@@ -781,8 +801,11 @@ template <typename T, typename TV, typename TS, typename PP, typename KP> inline
 template <typename T, typename TV = T, typename TS = T, typename PP = Params> inline int run_value_sorted(PP &p, const Dims &d, void *workspace, hipStream_t stream)
 {
     if constexpr (kValueMask<PP>) {
-        if (p.qmask != nullptr) return run_value_sorted_on<T, TV, TS, PP, MaskedParams>(p, d, workspace, stream);
-        return run_value_sorted_on<T, TV, TS, PP, Params>(p, d, workspace, stream);
+        // (per-level counts: the ragged masked kernarg, else the ragged passes on its RaggedParams part)
+        using Plain = std::conditional_t<kRagged<PP>, RaggedParams, Params>;
+        using Masked = std::conditional_t<kRagged<PP>, RaggedMaskedParams, MaskedParams>;
+        if (p.qmask != nullptr) return run_value_sorted_on<T, TV, TS, PP, Masked>(p, d, workspace, stream);
+        return run_value_sorted_on<T, TV, TS, PP, Plain>(p, d, workspace, stream);
     } else {
         return run_value_sorted_on<T, TV, TS, PP, PP>(p, d, workspace, stream);
     }
@@ -887,18 +910,21 @@ inline void fill_box_scales(Params &, const float *, double, int64_t) {}
 // the value padding mask (msda_*_masked_<dtype>): [B, I] bytes behind the kernarg; advanced with every other batch-indexed
 // pointer when the grad_value pipeline runs once per group of batch elements
 // ... and the query padding mask behind it (msda_*_qmasked_<dtype>): [B, Q] bytes, NULL from the _masked_ entry points
-inline void set_value_mask(MaskedParams &p, const uint8_t *vmask, const uint8_t *qmask)
+// (one definition for every kernarg that carries the pair — kValueMask — and a no-op for the others)
+template <typename PP> inline void set_value_mask(PP &p, const uint8_t *vmask, const uint8_t *qmask)
 {
-    p.vmask = vmask;
-    p.qmask = qmask;
+    if constexpr (kValueMask<PP>) {
+        p.vmask = vmask;
+        p.qmask = qmask;
+    }
 }
-inline void set_value_mask(Params &, const uint8_t *, const uint8_t *) {}
-inline void advance_value_mask(MaskedParams &pg, const MaskedParams &p, size_t pixels, size_t queries)
+template <typename PP> inline void advance_value_mask(PP &pg, const PP &p, size_t pixels, size_t queries)
 {
-    pg.vmask = p.vmask + pixels;
-    pg.qmask = p.qmask != nullptr ? p.qmask + queries : nullptr;
+    if constexpr (kValueMask<PP>) {
+        pg.vmask = p.vmask + pixels;
+        pg.qmask = p.qmask != nullptr ? p.qmask + queries : nullptr;
+    }
 }
-inline void advance_value_mask(Params &, const Params &, size_t, size_t) {}
 
 // ---- discrete (nearest-pixel) sampling: msda_{fwd,bwd}_discrete_<dtype>, kernels in msda_discrete.hpp ----
 // MODE 0: the forward, 1: the attention-weight gradient.  G lanes per unit from D as everywhere (pick_group); the
@@ -1108,6 +1134,8 @@ template <typename T, typename TV = T, typename PP = Params> int run_fwd(const C
 // holds L fp32 scales on the host, `offset_scale` the config's (the entry point checked ref_dim == 4)
 // PP = HfBoxDiscreteParams (msda_fwd_fused_hfbox_discrete_<dtype>): the same rule in front of discrete sampling, on the
 // kernels of msda_hfbox_discrete.hpp (no padding mode — border —, no 32-bit limit on the projection)
+// PP = MaskedParams (msda_fwd_fused_masked_<dtype>) / RaggedMaskedParams (msda_fwd_fused_ragged_masked_<dtype>): the module's
+// own rule, uniform / per-level counts, with the value mask and (unless NULL) the query mask in the kernels
 template <typename T, typename TV = T, typename TS = T, typename PP = Params> int run_fwd_fused(const Call &c)
 {
     const Dims d = make_dims(c);
@@ -1343,10 +1371,10 @@ int run_value_float(PP &p, const Dims &d, void *workspace, int64_t workspace_byt
     KW template int msda::run_value_float<TS, TS, msda::PP>(msda::PP &, const msda::Dims &, void *, int64_t, hipStream_t);
 #define MSDA_DECLARE_RUN_VALUE_FLOAT(TS)                                                                                                       \
     MSDA_RUN_VALUE_FLOAT_(extern, TS, Params) MSDA_RUN_VALUE_FLOAT_(extern, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(extern, TS, MaskedParams) \
-    MSDA_RUN_VALUE_FLOAT_(extern, TS, DiscreteParams)
+    MSDA_RUN_VALUE_FLOAT_(extern, TS, DiscreteParams) MSDA_RUN_VALUE_FLOAT_(extern, TS, RaggedMaskedParams)
 #define MSDA_DEFINE_RUN_VALUE_FLOAT(TS)                                                                                     \
     MSDA_RUN_VALUE_FLOAT_(, TS, Params) MSDA_RUN_VALUE_FLOAT_(, TS, RaggedParams) MSDA_RUN_VALUE_FLOAT_(, TS, MaskedParams) \
-    MSDA_RUN_VALUE_FLOAT_(, TS, DiscreteParams)
+    MSDA_RUN_VALUE_FLOAT_(, TS, DiscreteParams) MSDA_RUN_VALUE_FLOAT_(, TS, RaggedMaskedParams)
 
 // PP as run_fwd's.  DiscreteParams (msda_bwd_discrete_<dtype>): grad_value and / or grad_attn — the sampling points have no
 // gradient in this mode, so there is no grad_loc buffer, the records always stay in the workspace
@@ -1643,7 +1671,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TV, T)                                                 \
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TV, T)                                                \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)                                                           \
-    MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TV, T)
+    MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TV, T)                                                  \
+    MSDA_DEFINE_MODULE_MASK_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
 // fp32 reference points and fp32 arithmetic (msda_fwd_fused_f32_sbf16 / _sf16): fused entry points only
@@ -1671,7 +1700,8 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TS, TS)                                                \
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TS, TS)                                               \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)                                                          \
-    MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TS, TS)
+    MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TS, TS)                                                 \
+    MSDA_DEFINE_MODULE_MASK_ENTRY_POINTS(SUF, T, TS, TS)
 
 // the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
 // points, TV value rows, TS projection / out / their gradients)
@@ -1893,6 +1923,59 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         MSDA_BOTH_MASKS_REQUIRED("msda_bwd_fused_levelref_qmasked")                                              \
         MSDA_TAKE_BWD_FUSED c.P = P; c.value_mask = value_mask; c.query_mask = query_mask;                       \
         return msda::run_bwd_fused<T, TV, TS, msda::LevelRefMaskedParams>(c);                                    \
+    }
+
+// the module's own fused pairs with both padding masks: msda_{fwd,bwd}_fused_masked_<suffix> (one reference point per query,
+// uniform point count: MaskedParams) and msda_{fwd,bwd}_fused_ragged_masked_<suffix> (per-level counts: RaggedMaskedParams) —
+// the unmasked twins' argument lists with `value_mask`, `query_mask` behind `value`.  A null value_mask is an argument
+// error, refused before any other argument is looked at; a null query_mask means "every query is real" (what the kernarg
+// means by it: a call that only masks values keeps its prefetches and the LDS-level sample-gradient kernel).
+#define MSDA_DEFINE_MODULE_MASK_ENTRY_POINTS(SUF, T, TV, TS)                                                     \
+    extern "C" int msda_fwd_fused_masked_##SUF(const void *value, const uint8_t *value_mask,                    \
+                                               const uint8_t *query_mask, const int64_t *shapes,                 \
+                                               const void *proj, const void *ref, void *out, int64_t B,          \
+                                               int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                                               int ref_dim, int padding_mode, int align_corners,                 \
+                                               int64_t value_row_stride, void *stream)                           \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_fwd_fused_masked")                                                              \
+        MSDA_TAKE_FWD_FUSED c.P = P; c.value_mask = value_mask; c.query_mask = query_mask;                       \
+        return msda::run_fwd_fused<T, TV, TS, msda::MaskedParams>(c);                                            \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_masked_##SUF(                                                                  \
+        const void *grad_out, const void *value, const uint8_t *value_mask, const uint8_t *query_mask,          \
+        const int64_t *shapes, const void *proj, const void *ref, void *grad_value, void *grad_proj,             \
+        void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P,     \
+        int ref_dim, int padding_mode, int align_corners, int64_t max_level_cells, int64_t value_row_stride,     \
+        void *workspace, int64_t workspace_bytes, void *stream)                                                  \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_bwd_fused_masked")                                                              \
+        MSDA_TAKE_BWD_FUSED c.P = P; c.value_mask = value_mask; c.query_mask = query_mask;                       \
+        return msda::run_bwd_fused<T, TV, TS, msda::MaskedParams>(c);                                            \
+    }                                                                                                            \
+    extern "C" int msda_fwd_fused_ragged_masked_##SUF(const void *value, const uint8_t *value_mask,             \
+                                                      const uint8_t *query_mask, const int64_t *shapes,          \
+                                                      const void *proj, const void *ref, void *out, int64_t B,   \
+                                                      int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,     \
+                                                      const int32_t *points_per_level, int ref_dim,              \
+                                                      int padding_mode, int align_corners,                       \
+                                                      int64_t value_row_stride, void *stream)                    \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_fwd_fused_ragged_masked")                                                       \
+        MSDA_TAKE_FWD_FUSED MSDA_TAKE_COUNTS c.value_mask = value_mask; c.query_mask = query_mask;               \
+        return msda::run_fwd_fused<T, TV, TS, msda::RaggedMaskedParams>(c);                                      \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_ragged_masked_##SUF(                                                           \
+        const void *grad_out, const void *value, const uint8_t *value_mask, const uint8_t *query_mask,          \
+        const int64_t *shapes, const void *proj, const void *ref, void *grad_value, void *grad_proj,             \
+        void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,                \
+        const int32_t *points_per_level, int ref_dim, int padding_mode, int align_corners,                       \
+        int64_t max_level_cells, int64_t value_row_stride, void *workspace, int64_t workspace_bytes,             \
+        void *stream)                                                                                            \
+    {                                                                                                            \
+        MSDA_MASK_REQUIRED("msda_bwd_fused_ragged_masked")                                                       \
+        MSDA_TAKE_BWD_FUSED MSDA_TAKE_COUNTS c.value_mask = value_mask; c.query_mask = query_mask;               \
+        return msda::run_bwd_fused<T, TV, TS, msda::RaggedMaskedParams>(c);                                      \
     }
 
 // one storage type for every tensor

@@ -279,6 +279,64 @@ def _mask_args(name: str, value_mask, query_mask, img, per_query):
     return name, (), ()
 
 
+class MaskedCallDeclined(Exception):
+    """Raised by the forward of a masked module ``Function`` when the library declines the call (``MSDA_ERR_UNSUPPORTED``;
+    nothing was launched): :func:`fused_module_core` / ``fused_ragged_module_core`` catch it and compose the masks."""
+
+
+def _mask_bytes(mask: torch.Tensor) -> torch.Tensor:
+    """a validated mask as the kernels take it: contiguous uint8 (bool is viewed, not copied)"""
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _module_mask_args(name: str, value_mask, query_mask, img, per_query, checked: bool = False):
+    """:func:`_mask_args` for the module's own fused pairs (``msda_*_fused_masked_<suffix>``,
+    ``msda_*_fused_ragged_masked_<suffix>``): one ``_masked`` family takes both pointers behind ``value``; a call with a
+    query mask only passes the cached all-ones value mask, a call with a value mask only a NULL query mask ("every query is
+    real": it keeps what a query mask costs the kernels).  ``checked``: the masks are what :func:`check_value_mask` /
+    :func:`check_query_mask` return already (the ``Function``s: the cores validated and converted them once)."""
+    if value_mask is None and query_mask is None:
+        return name, (), ()
+    if value_mask is None:
+        value_mask = _ones_value_mask(img)
+    elif not checked:
+        value_mask = check_value_mask(value_mask, img)
+    if query_mask is not None and not checked:
+        query_mask = check_query_mask(query_mask, per_query)
+    return (name + "_masked", (value_mask.data_ptr(), None if query_mask is None else query_mask.data_ptr()),
+            (value_mask, query_mask))
+
+
+def fused_lp_limit(D: int, elem_size: int) -> int:
+    """``msda_fused_lp_limit``: the most samples per (b, q, h) unit the fused kernels take at this head dimension and
+    arithmetic element size (cached)."""
+    key = (int(D), int(elem_size))
+    limit = _FUSED_LP_LIMIT.get(key)
+    if limit is None:
+        limit = _FUSED_LP_LIMIT[key] = int(_lib.load().msda_fused_lp_limit(*key))
+    return limit
+
+
+def module_masks_in_kernels(img, proj, reference_points, samples: int, levels: Optional[int] = None) -> bool:
+    """Do the module's masked fused kernels take this call — GPU tensors of the dtypes the fused kernels serve, outside a
+    trace, a library that has the symbols, and a shape the kernels do not decline (all ``samples`` of a unit in one LDS
+    pass; ``levels``, given for per-level counts, at most 8)?  Everything else composes :func:`apply_value_mask` /
+    :func:`apply_query_mask` with the unmasked route."""
+    if img.device.type != "cuda" or torch.compiler.is_compiling() or img.dim() != 4:
+        return False
+    if not (img.is_floating_point() and proj.is_floating_point() and reference_points.is_floating_point()):
+        return False
+    autocast = _autocast_on()
+    storage = fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype)
+    same = dtypes_supported(img.dtype, proj.dtype) and reference_points.dtype == proj.dtype
+    if not (autocast or storage or same) or not _lib.has_module_masks():
+        return False
+    if levels is not None and levels > 8:
+        return False
+    return samples <= fused_lp_limit(img.shape[3], 4 if (autocast or storage) else proj.element_size())
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _FUSED_LP_LIMIT: dict = {}  # (D, element size) -> msda_fused_lp_limit
 _WS_BYTES: dict = {}  # (B, I, H, D, Q, L, P, elem, option epoch) -> msda_bwd_workspace_bytes
@@ -677,13 +735,13 @@ def module_sampling_inputs(proj: torch.Tensor, img_shapes: torch.Tensor, referen
 
 def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners,
                        levelref: bool = False, value_mask: Optional[torch.Tensor] = None,
-                       query_mask: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+                       query_mask: Optional[torch.Tensor] = None, masks_checked: bool = False) -> Optional[torch.Tensor]:
     """Forward with softmax + sampling-point math done in the kernel prologue.  Returns None when the
     library declines (L*P too large for one pass): the caller then takes the unfused route.  ``levelref``: the
     reference points are per level, ``[B, Q, L, ref_dim]``, and the points follow transformers' rule
-    (:func:`hf_module_sampling_inputs`; ``msda_fwd_fused_levelref_<dtype>``).  ``value_mask`` (with ``levelref`` only):
-    the value-mask twin ``msda_fwd_fused_levelref_masked_<dtype>``; ``query_mask`` (likewise):
-    ``msda_fwd_fused_levelref_qmasked_<dtype>``."""
+    (:func:`hf_module_sampling_inputs`; ``msda_fwd_fused_levelref_<dtype>``).  ``value_mask`` / ``query_mask``: with
+    ``levelref`` the twins ``msda_fwd_fused_levelref_masked_<dtype>`` / ``..._qmasked_<dtype>``; without it the module's own
+    masked pair ``msda_fwd_fused_masked_<dtype>``, which takes both pointers (:func:`_module_mask_args`)."""
     B, I, H, D = img.shape
     B2, Q, H2, L, P, three = proj.shape
     if (B2, H2, three) != (B, H, 3) or tuple(reference_points.shape[:2]) != (B, Q) or \
@@ -704,9 +762,8 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
     out = torch.empty((B, Q, H, D), dtype=cdt, device=img.device)
     lib = _lib.load()
     name = "msda_fwd_fused_levelref" if levelref else "msda_fwd_fused"
-    if (value_mask is not None or query_mask is not None) and not levelref:
-        raise ValueError("`value_mask` / `query_mask` are served by the per-level-reference fused kernels only (levelref=True)")
-    sym, mask_arg, _masks = _mask_args(name, value_mask, query_mask, img, proj)
+    sym, mask_arg, _masks = _mask_args(name, value_mask, query_mask, img, proj) if levelref else \
+        _module_mask_args(name, value_mask, query_mask, img, proj, masks_checked)
     # (the timer's group stays the pair's — "msda_fwd_fused_levelref" — with or without a mask: it names the launcher)
     fn = getattr(lib, f"{sym}_{suf}", None)
     if fn is None:  # (a library built before the per-level entry points: the caller composes)
@@ -727,7 +784,8 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
 
 def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners,
                        need_img: bool = True, level_cells: int = 0, need_ref: bool = True, levelref: bool = False,
-                       value_mask: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None):
+                       value_mask: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None,
+                       masks_checked: bool = False):
     """Backward of the module core with the prologue's chain rule done in the kernel: returns
     ``(img_grad | None, proj_grad, reference_points_grad)``, or None when the library declines (L*P too large
     for one pass; nothing was launched).  ``levelref``: as in :func:`msda_hip_fwd_fused`; the kernel's partials are
@@ -752,10 +810,9 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
                              device=img.device)
     lib = _lib.load()
     name = "msda_bwd_fused_levelref" if levelref else "msda_bwd_fused"
-    if (value_mask is not None or query_mask is not None) and not levelref:
-        raise ValueError("`value_mask` / `query_mask` are served by the per-level-reference fused kernels only (levelref=True)")
     # (the masked entry points; the workspace is the twin's)
-    sym, mask_arg, _masks = _mask_args(name, value_mask, query_mask, img, proj)
+    sym, mask_arg, _masks = _mask_args(name, value_mask, query_mask, img, proj) if levelref else \
+        _module_mask_args(name, value_mask, query_mask, img, proj, masks_checked)
     fn = getattr(lib, f"{sym}_{suf}", None)  # (the timer's group stays the pair's, as in the forward)
     if fn is None:
         return None
@@ -790,15 +847,21 @@ class _HipFusedModuleCoreFunction(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, level_cells=0):
+    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, level_cells=0, value_mask=None,
+                query_mask=None):
         ctx.level_cells = int(level_cells)
-        out = msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners)
+        # (value_mask, query_mask: uint8 [B, I] / [B, Q] as check_*_mask returns them, or None: msda_*_fused_masked_<dtype>;
+        # no gradient.  A masked call the library declines is handed back to fused_module_core, which composes it)
+        out = msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners,
+                                 value_mask=value_mask, query_mask=query_mask, masks_checked=True)
         ctx.fused = out is not None  # the backward has the same L*P limit: do not ask twice
+        if out is None and (value_mask is not None or query_mask is not None):
+            raise MaskedCallDeclined()
         if out is None:
             # (16-bit storage next to fp32 reference points: the prologue in fp32, the mixed-storage operator)
             pts, att = module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points)
             out = msda_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners).to(proj.dtype)
-        ctx.save_for_backward(img, img_shapes, proj, reference_points)
+        ctx.save_for_backward(img, img_shapes, proj, reference_points, value_mask, query_mask)
         ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
         return out
 
@@ -806,14 +869,21 @@ class _HipFusedModuleCoreFunction(Function):
     @once_differentiable
     @custom_bwd(device_type="cuda")
     def backward(ctx, out_grad):
-        img, img_shapes, proj, reference_points = ctx.saved_tensors
+        img, img_shapes, proj, reference_points, value_mask, query_mask = ctx.saved_tensors
         need_img, _, need_proj, need_ref = ctx.needs_input_grad[:4]
-        if ctx.fused and (need_proj or need_ref):
+        # (a masked call stays on the fused backward even when only the pyramid wants a gradient — its grad_proj is then
+        # discarded: the composition below would have to sanitise the masked queries' inputs)
+        masked = value_mask is not None or query_mask is not None
+        if ctx.fused and (need_proj or need_ref or masked):
             res = msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, ctx.padding_mode,
-                                     ctx.align_corners, need_img, level_cells=ctx.level_cells, need_ref=need_ref)
+                                     ctx.align_corners, need_img, level_cells=ctx.level_cells, need_ref=need_ref,
+                                     value_mask=value_mask, query_mask=query_mask, masks_checked=True)
             if res is not None:
                 g_img, g_proj, g_ref = res
-                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None
+                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None, None
+        if masked:  # (the forward ran masked; only the grad_value pipeline can decline here, and the message says why)
+            raise _lib.MSDALibraryError("the masked fused backward was declined after its forward ran: "
+                                        + _lib.load().msda_last_error().decode(errors="replace"))
         with torch.enable_grad():
             proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
             ref_ = reference_points.detach().requires_grad_(need_ref)
@@ -831,22 +901,54 @@ class _HipFusedModuleCoreFunction(Function):
                 g_proj = grads.pop(0).to(proj.dtype)
             if need_ref:
                 g_ref = grads.pop(0)
-        return g_img, None, g_proj, g_ref, None, None, None
+        return g_img, None, g_proj, g_ref, None, None, None, None, None
 
 
 def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None,
-                      points_per_level=None, value_mask=None, query_mask=None) -> torch.Tensor:
+                      points_per_level=None, value_mask=None, query_mask=None, mask_in_kernels: bool = True) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *module_sampling_inputs(proj, ...))`` — on GPU tensors
     with the prologue fused into the forward kernel; on host tensors exactly that composition.  ``level_shapes``: the
     level sizes as host numbers, optional (:func:`level_cells_of`).  ``points_per_level``: a point count per level; then
     ``proj`` is ``[B, Q, H, S, 3]`` with ``S = sum(points_per_level)``, level-major
     (:func:`msda_triton_amd.ragged.ragged_module_sampling_inputs` states the prologue).  ``value_mask``: ``[B, I]``,
-    non-zero = the pixel is real; composed as ``masked_fill`` in front of the kernels (these have no masked form).
-    ``query_mask``: ``[B, Q]``, non-zero = the query is real; composed likewise (:func:`apply_query_mask`)."""
+    non-zero = the pixel is real — the result is that of ``where(mask, img, 0)`` whatever the padding pixels hold.
+    ``query_mask``: ``[B, Q]``, non-zero = the query is real — a masked query's row of the result is zeros, its ``proj`` and
+    ``reference_points`` rows get zero gradients and nothing they hold reaches any result.  On GPU tensors both go into the
+    fused kernels (``msda_*_fused_masked_<dtype>``, with ``points_per_level`` ``msda_*_fused_ragged_masked_<dtype>``; a
+    call with a query mask only passes a cached all-ones value mask) through the Python ``Function`` — the C++ autograd
+    nodes and the compile ops take no mask.  Host tensors, traced calls, ``mask_in_kernels=False``, a library without
+    those symbols, a shape beyond the fused kernels' limits (:func:`module_masks_in_kernels`) and a forward the library
+    declines (``MSDA_ERR_UNSUPPORTED``) compose :func:`apply_value_mask` / :func:`apply_query_mask` with the unmasked route.
+    A BACKWARD the library declines after its forward ran masked — the grad_value pipeline's own limits: 2^22 pixels per
+    plane and more, option "strict" with the plane-major place pass — raises ``MSDALibraryError`` with the library's
+    message; ``mask_in_kernels=False`` serves such a call."""
+    if points_per_level is not None and (value_mask is not None or query_mask is not None):
+        from .ragged import fused_ragged_module_core
+        return fused_ragged_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners,
+                                        points_per_level, level_shapes, value_mask, query_mask, mask_in_kernels)
+    if value_mask is not None or query_mask is not None:
+        if value_mask is not None:
+            _validate_value_mask(value_mask, img)
+        if query_mask is not None:
+            _validate_query_mask(query_mask, proj)
+        if mask_in_kernels and proj.dim() == 6 and \
+                module_masks_in_kernels(img, proj, reference_points, proj.shape[3] * proj.shape[4]):
+            if img_shapes.device != img.device:
+                img_shapes = img_shapes.to(img.device)
+            _check_devices(img, proj, reference_points)
+            _padding_code(padding_mode)
+            try:  # (the masks were validated above: converted once, here)
+                return _HipFusedModuleCoreFunction.apply(
+                    img, img_shapes, proj, reference_points, padding_mode, bool(align_corners),
+                    level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1]),
+                    _mask_bytes(value_mask) if value_mask is not None else _ones_value_mask(img),
+                    None if query_mask is None else _mask_bytes(query_mask))
+            except MaskedCallDeclined:
+                pass  # nothing was launched: the composition below
     if query_mask is not None:
         out = fused_module_core(img, img_shapes, apply_query_mask(proj, query_mask, 0.0),
                                 apply_query_mask(reference_points, query_mask, 0.5), padding_mode, align_corners,
-                                level_shapes, points_per_level, value_mask)
+                                level_shapes, points_per_level, value_mask, None, mask_in_kernels)
         return apply_query_mask(out, query_mask, 0.0)
     img = apply_value_mask(img, value_mask)
     if points_per_level is not None:

@@ -14,8 +14,23 @@ import torch
 from torch import nn
 
 from ._linear import projection
-from .functional import apply_query_mask, apply_value_mask, fused_module_core, module_sampling_inputs
+from .functional import fused_module_core, module_sampling_inputs
 from .ragged import ragged_module_sampling_inputs
+
+# Both padding masks inside the fused kernels (msda_*_fused_masked_<dtype>, msda_*_fused_ragged_masked_<dtype>) instead of
+# masked_fill / where passes around them.  The per-dtype default follows the project's rule: a storage
+# dtype goes to the kernels only where the masked leg's slowest measured repeat was below the composition's fastest,
+# forward plus backward (tools/module_mask_bench.py).  False: every call composes (A/B runs, and the parent's behaviour).
+MASK_IN_KERNELS = True
+MASK_IN_KERNELS_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def mask_in_kernels(value: torch.Tensor) -> bool:
+    """Does ``MultiscaleDeformableAttention.forward`` ask the core to take ``value_mask`` / ``query_mask`` into its fused
+    kernels for this projected pyramid (``fused_module_core(mask_in_kernels=True)``), or compose them?  ``value`` is the
+    pyramid as the kernels will read it — after the cast to the module's ``value_dtype``, so ``value_dtype=torch.float16``
+    composes like every fp16 pyramid."""
+    return bool(MASK_IN_KERNELS) and value.device.type == "cuda" and value.dtype in MASK_IN_KERNELS_DTYPES
 
 
 class MultiscaleDeformableAttention(nn.Module):
@@ -102,12 +117,13 @@ class MultiscaleDeformableAttention(nn.Module):
             level_shapes: optional (not in the reference): the same (height, width) pairs as host numbers; see
                 ``msda_triton_amd.functional.level_cells_of``.
             value_mask: optional (not in the reference): ``[batch, num_image]`` bool or uint8, non-zero = the pixel is
-                real (transformers' ``attention_mask`` polarity).  Applied to the projected pyramid as ``masked_fill``
-                (this module's fused kernels have no masked form); see ``multiscale_deformable_attention``.
+                real (transformers' ``attention_mask`` polarity): the projected pyramid counts as
+                ``where(mask, value, 0)``.  On the GPU the mask goes into the fused kernels (``mask_in_kernels``); elsewhere
+                it is applied as ``masked_fill``; see ``functional.fused_module_core``.
             query_mask: optional (not in the reference): ``[batch, num_queries]`` bool or uint8, non-zero = the query is
-                real.  Composed around the core (``functional.apply_query_mask``): a masked query's attended row is
-                zeros, so its row of the result is the output projection's bias, and nothing its projection or reference
-                point holds reaches a gradient.
+                real.  A masked query's attended row is zeros, so its row of the result is the output projection's bias,
+                and nothing its projection or reference point holds reaches a gradient.  Handed to the core with
+                ``value_mask`` (on the GPU the fused kernels skip the query; elsewhere ``functional.apply_query_mask``).
 
         Returns:
             ``[batch, num_queries, emb_dim]``.
@@ -129,27 +145,30 @@ class MultiscaleDeformableAttention(nn.Module):
         #  no gain at 2 500, and a LOSS at 900 — a host-bound step that the two extra small launches lengthen — so only
         #  from 32 768 (b, q) rows on)
         value = projection(self.img_input_proj, img, pad_rows=B * N >= 32768).reshape(B, I, H, self.hidden_dim // H)
-        value = apply_value_mask(value, value_mask)
-        if query_mask is not None:
-            proj, reference_points = apply_query_mask(proj, query_mask, 0.0), apply_query_mask(reference_points, query_mask, 0.5)
-        if value.device.type == "cuda" and proj.dtype in (torch.bfloat16, torch.float16) and \
-                self.value_dtype in (None, proj.dtype) and value.dtype == proj.dtype:
+        # both masks travel to the core, which takes them into its kernels or composes them (module-level MASK_IN_KERNELS,
+        # decided on the dtype the kernels will read the pyramid in: below, after any cast to `value_dtype`)
+        storage16 = value.device.type == "cuda" and proj.dtype in (torch.bfloat16, torch.float16) and \
+            self.value_dtype in (None, proj.dtype) and value.dtype == proj.dtype
+        if not storage16 and self.value_dtype is not None and value.device.type == "cuda":
+            value = value.to(self.value_dtype)  # nothing to do when autocast already produced this dtype
+        masks = dict(value_mask=value_mask, query_mask=query_mask, mask_in_kernels=mask_in_kernels(value))
+        if storage16:
             # 16-bit projections (autocast's GEMMs, or 16-bit parameters) with fp32 reference points: the kernels read
             # and write the 16-bit tensors as they are and compute in fp32 — what the reference's core does under
             # autocast (it casts every input to fp32, frontend.py:111) without the fp32 copies of value, projection,
             # result and their gradients; rounding happens at the same places (the GEMMs' outputs / inputs)
             with torch.autocast("cuda", enabled=False):
                 attended = fused_module_core(value, img_shapes, proj, reference_points.float(), self.padding_mode,
-                                             self.align_corners, level_shapes, counts)
+                                             self.align_corners, level_shapes, counts, **masks)
         elif self.value_dtype is not None and value.device.type == "cuda":
             # 16-bit value pyramid next to fp32 sampling inputs: the mixed-storage kernels read it as it is (no fp32
             # copy, which is what autocast's cast_inputs would make), so the call sits outside autocast
-            value = value.to(self.value_dtype)  # nothing to do when autocast already produced this dtype
+            # (cast above, in front of the masks' routing decision)
             with torch.autocast("cuda", enabled=False):
                 attended = fused_module_core(value, img_shapes, proj.float(), reference_points.float(),
-                                             self.padding_mode, self.align_corners, level_shapes, counts).to(proj.dtype)
+                                             self.padding_mode, self.align_corners, level_shapes, counts,
+                                             **masks).to(proj.dtype)
         else:
             attended = fused_module_core(value, img_shapes, proj, reference_points, self.padding_mode,
-                                         self.align_corners, level_shapes, counts)
-        attended = apply_query_mask(attended, query_mask, 0.0)
+                                         self.align_corners, level_shapes, counts, **masks)
         return projection(self.query_output_proj, attended.reshape(B, N, self.hidden_dim))

@@ -278,10 +278,12 @@ def fused_ragged_limits_ok(D: int, elem_size: int, counts) -> bool:
     return sum(counts) <= limit and len(counts) <= 8
 
 
-def ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts) -> Optional[torch.Tensor]:
+def ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
+                         value_mask=None, query_mask=None, masks_checked: bool = False) -> Optional[torch.Tensor]:
     """Forward with the softmax and the sampling-point arithmetic done in the kernel prologue
     (``msda_fwd_fused_ragged_<suffix>``).  None when the library declines (S too large for one pass, more than 8 levels)
-    or predates these entry points: the caller then takes the unfused route."""
+    or predates these entry points: the caller then takes the unfused route.  ``value_mask`` / ``query_mask``: the masked
+    pair ``msda_fwd_fused_ragged_masked_<suffix>`` (:func:`msda_triton_amd.functional._module_mask_args`)."""
     if not _lib.has_fused_ragged():
         return None
     B, I, H, D = img.shape
@@ -295,10 +297,13 @@ def ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, 
     (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
     shapes = F._shapes_i64(img_shapes)
     out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
-    fn = getattr(_lib.load(), f"msda_fwd_fused_ragged_{suf}")
+    sym, mask_arg, _masks = F._module_mask_args("msda_fwd_fused_ragged", value_mask, query_mask, img, proj, masks_checked)
+    fn = getattr(_lib.load(), f"{sym}_{suf}", None)
+    if fn is None:
+        return None
 
     def call():
-        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+        return fn(img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
                   B, I, H, D, Q, len(counts), _counts_array(counts), reference_points.shape[-1], pad,
                   int(bool(align_corners)), vrow, F._stream_ptr(img.device))
 
@@ -307,12 +312,13 @@ def ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, 
         rc = timer.launch("msda_fwd_fused_ragged", img.device, call) if timer else call()
     if rc == -5:  # MSDA_ERR_UNSUPPORTED
         return None
-    _lib.check(rc, f"msda_fwd_fused_ragged_{suf}")
+    _lib.check(rc, f"{sym}_{suf}")
     return out
 
 
 def ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
-                         need_img: bool = True, level_cells: int = 0, need_ref: bool = True):
+                         need_img: bool = True, level_cells: int = 0, need_ref: bool = True, value_mask=None,
+                         query_mask=None, masks_checked: bool = False):
     """Backward of the module core with the prologue's chain rule done in the kernel
     (``msda_bwd_fused_ragged_<suffix>``): ``(img_grad | None, proj_grad, reference_points_grad | None)``, or None when
     the library declines (nothing was launched)."""
@@ -335,7 +341,11 @@ def ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padd
     g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
     g_ref_part = torch.empty((B, Q, H, ref_dim), dtype=reference_points.dtype, device=img.device)
     lib = _lib.load()
-    fn = getattr(lib, f"msda_bwd_fused_ragged_{suf}")
+    # (the masked pair msda_bwd_fused_ragged_masked_<suffix>; the workspace is the twin's)
+    sym, mask_arg, _masks = F._module_mask_args("msda_bwd_fused_ragged", value_mask, query_mask, img, proj, masks_checked)
+    fn = getattr(lib, f"{sym}_{suf}", None)
+    if fn is None:
+        return None
     arr = _counts_array(counts)
     ws, ws_bytes = None, 0
     level_cells = int(level_cells)
@@ -346,7 +356,7 @@ def ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padd
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
 
     def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+        return fn(out_grad.data_ptr(), img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
                   g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
                   B, I, H, D, Q, len(counts), arr, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
                   ws.data_ptr() if ws is not None else None, ws_bytes, F._stream_ptr(img.device))
@@ -356,7 +366,7 @@ def ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padd
         rc = timer.launch("msda_bwd_fused_ragged", img.device, call) if timer else call()
     if rc == -5:  # MSDA_ERR_UNSUPPORTED
         return None
-    _lib.check(rc, f"msda_bwd_fused_ragged_{suf}")
+    _lib.check(rc, f"{sym}_{suf}")
     return g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None)
 
 
@@ -367,14 +377,21 @@ class _HipFusedRaggedModuleCoreFunction(Function):
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts, level_cells=0):
+    def forward(ctx, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts, level_cells=0,
+                value_mask=None, query_mask=None):
         ctx.level_cells, ctx.counts = int(level_cells), counts
-        out = ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts)
+        # (value_mask, query_mask: uint8 [B, I] / [B, Q] as check_*_mask returns them, or None:
+        # msda_*_fused_ragged_masked_<dtype>; no gradient.  A masked call the library declines is handed back to
+        # fused_ragged_module_core, which composes it — the ragged operator has no masked kernels to do that here)
+        out = ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
+                                   value_mask, query_mask, masks_checked=True)
         ctx.fused = out is not None  # the backward has the same limits: do not ask twice
+        if out is None and (value_mask is not None or query_mask is not None):
+            raise F.MaskedCallDeclined()
         if out is None:
             pts, att = ragged_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points, counts)
             out = ragged_hip_fwd(img, img_shapes, pts, att, padding_mode, align_corners, counts).to(proj.dtype)
-        ctx.save_for_backward(img, img_shapes, proj, reference_points)
+        ctx.save_for_backward(img, img_shapes, proj, reference_points, value_mask, query_mask)
         ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
         return out
 
@@ -382,15 +399,23 @@ class _HipFusedRaggedModuleCoreFunction(Function):
     @once_differentiable
     @custom_bwd(device_type="cuda")
     def backward(ctx, out_grad):
-        img, img_shapes, proj, reference_points = ctx.saved_tensors
+        img, img_shapes, proj, reference_points, value_mask, query_mask = ctx.saved_tensors
         need_img, _, need_proj, need_ref = ctx.needs_input_grad[:4]
         counts = ctx.counts
-        if ctx.fused and (need_proj or need_ref):
+        # (a masked call stays on the fused backward even when only the pyramid wants a gradient — its grad_proj is then
+        # discarded: there is no masked ragged operator to compose from)
+        masked = value_mask is not None or query_mask is not None
+        if ctx.fused and (need_proj or need_ref or masked):
             res = ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, ctx.padding_mode,
-                                       ctx.align_corners, counts, need_img, level_cells=ctx.level_cells, need_ref=need_ref)
+                                       ctx.align_corners, counts, need_img, level_cells=ctx.level_cells, need_ref=need_ref,
+                                       value_mask=value_mask, query_mask=query_mask, masks_checked=True)
             if res is not None:
                 g_img, g_proj, g_ref = res
-                return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None
+                return (g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None,
+                        None, None)
+        if masked:  # (the forward ran masked; only the grad_value pipeline can decline here, and the message says why)
+            raise _lib.MSDALibraryError("the masked fused ragged backward was declined after its forward ran: "
+                                        + _lib.load().msda_last_error().decode(errors="replace"))
         with torch.enable_grad():
             proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
             ref_ = reference_points.detach().requires_grad_(need_ref)
@@ -407,19 +432,47 @@ class _HipFusedRaggedModuleCoreFunction(Function):
                 g_proj = grads.pop(0).to(proj.dtype)
             if need_ref:
                 g_ref = grads.pop(0)
-        return g_img, None, g_proj, g_ref, None, None, None, None
+        return g_img, None, g_proj, g_ref, None, None, None, None, None, None
 
 
 def fused_ragged_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, points_per_level,
-                             level_shapes=None) -> torch.Tensor:
+                             level_shapes=None, value_mask=None, query_mask=None, mask_in_kernels: bool = True) -> torch.Tensor:
     """``fused_module_core(..., points_per_level=...)``: ``proj`` is ``[B, Q, H, S, 3]``.  Routing mirrors the uniform
-    function: equal counts -> the uniform call on a view; host tensors -> the composition; GPU -> the fused kernels."""
+    function: equal counts -> the uniform call on a view; host tensors -> the composition; GPU -> the fused kernels.
+    ``value_mask`` / ``query_mask`` / ``mask_in_kernels``: as :func:`msda_triton_amd.functional.fused_module_core` — on GPU
+    tensors the masks go into ``msda_*_fused_ragged_masked_<dtype>`` through the Python ``Function``; every other route
+    composes ``apply_value_mask`` / ``apply_query_mask``."""
     counts = check_proj_points_per_level(img_shapes, proj, reference_points, points_per_level)
     B, Q, H, S, _ = proj.shape
     L = len(counts)
     if all(p == counts[0] for p in counts):
         return F.fused_module_core(img, img_shapes, proj.reshape(B, Q, H, L, counts[0], 3), reference_points, padding_mode,
-                                   align_corners, level_shapes)
+                                   align_corners, level_shapes, None, value_mask, query_mask, mask_in_kernels)
+    if value_mask is not None or query_mask is not None:
+        if value_mask is not None:
+            F._validate_value_mask(value_mask, img)
+        if query_mask is not None:
+            F._validate_query_mask(query_mask, proj)
+        if mask_in_kernels and F.module_masks_in_kernels(img, proj, reference_points, S, L):
+            if img_shapes.device != img.device:
+                img_shapes = img_shapes.to(img.device)
+            F._check_devices(img, proj, reference_points)
+            F._padding_code(padding_mode)
+            try:  # (the masks were validated above: converted once, here)
+                return _HipFusedRaggedModuleCoreFunction.apply(
+                    img, img_shapes, proj, reference_points, padding_mode, bool(align_corners), counts,
+                    F.level_cells_of(level_shapes, L, img.shape[1]),
+                    F._mask_bytes(value_mask) if value_mask is not None else F._ones_value_mask(img),
+                    None if query_mask is None else F._mask_bytes(query_mask))
+            except F.MaskedCallDeclined:
+                pass  # nothing was launched: the composition below
+        # the composition, as the uniform function states it
+        if query_mask is not None:
+            out = fused_ragged_module_core(img, img_shapes, F.apply_query_mask(proj, query_mask, 0.0),
+                                           F.apply_query_mask(reference_points, query_mask, 0.5), padding_mode,
+                                           align_corners, counts, level_shapes, value_mask, None, mask_in_kernels)
+            return F.apply_query_mask(out, query_mask, 0.0)
+        img = F.apply_value_mask(img, value_mask)
     level_cells = F.level_cells_of(level_shapes, L, img.shape[1])
     on_gpu = img.device.type == "cuda"
     if on_gpu and img_shapes.device != img.device:
