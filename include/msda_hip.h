@@ -738,6 +738,13 @@ MSDA_API int msda_get_option(const char *key);
  * arithmetic type, or 1 when D is no multiple of that or a row pointer is not 16-byte aligned;  group: lanes per (b, q, h)
  * unit, the smallest of 4, 8, 16, 32, 64 that holds ceil(D / vec) — 64 beyond;  chunks: ceil(D / (group * vec)) trips
  * of the kernels' channel loop.  0 before the first launch of that kind.
+ * THE SORTED PIPELINE'S TABLES (last values, added within ABI 12 by name; all 0 after a single-launch grad_value):
+ * "value_cell_cap" cells of the LDS table of the count pass (and of the plane-major place pass) — a plane with more cells is
+ * walked in ceil(cells / value_cell_cap) trips, a plane's cells being sum_l (h_l + 1) * (w_l + 1);  "value_place_cells" cells of
+ * the level-major place pass's table (a level with more cells takes several trips), 0 when the plane-major pass ran;
+ * "value_place_variant" 0 = plane-major place pass, 1 = level-major with 1024 threads, 2 = level-major with 256 threads;
+ * "value_slices" query slices per plane of the count and place passes;  "value_rounds" rounds over the queries;
+ * "value_win" records per gather window.  With several passes over the batch: the last pass's values.
  * "grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches" are COUNTERS, not last values: launches so far in this
  * process whose (plane, slot) grid took the XCD-aware 3-D form dim3(8, slots, ceil(planes / 8)), the linear 2-D form
  * dim3(slots, planes), or the flat 1-D form that decodes its block index with a division (more than 65535 slots, plane

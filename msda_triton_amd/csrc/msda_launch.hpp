@@ -758,6 +758,13 @@ template <typename T, typename TV, typename TS, typename PP, typename KP> inline
         allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlock, KP>, big_lds_lm);
         allow_big_lds(msda_cell_place_lm_kernel<T, kPlaceBlockSmall, KP>, big_lds_lm_small);
     }
+    // measurement only: the table sizes, slices, rounds, window and place-pass variant of this launch
+    note_launch(17, cell_cap_pm);
+    note_launch(18, place_lm ? place_cells : 0);
+    note_launch(19, !place_lm ? 0 : place_small ? 2 : 1);
+    note_launch(20, p.nsplit);
+    note_launch(21, w.rounds);
+    note_launch(22, p.win);
     for (int r = 0; r < w.rounds; ++r) {  // one round unless Q is so large that a plane's grad_out rows leave L2
         p.q_begin = r * w.q_round;
         p.q_end = p.q_begin + w.q_round < p.Q ? p.q_begin + w.q_round : p.Q;
@@ -1316,6 +1323,7 @@ inline int run_value(PP &p, const Dims &d, void *workspace, int64_t workspace_by
     if (small_path) {
         note_launch(6, 1);
         note_launch(7, 1);
+        for (int slot = 17; slot <= 22; ++slot) note_launch(slot, 0);  // (the sorted pipeline's counters: none of it ran)
         rc = run_value_small<T, TV, TS>(p, d, stream);
     } else if (sorted) {
         note_launch(6, 2);

@@ -217,12 +217,19 @@ for _d in (68, 132):
 SHAPE_MATRIX = ["d32_vec_g8", "d64_vec_g16", "d8_vec_g4", "d5_scalar", "d1", "one_query", "many_levels"]
 
 
+# name: f(case, rng) -> case, applied after the draw by a helper module that registers cases of its own here
+# (tests/large_pyramid_cases.py re-draws the sampling points and plants samples at its trip cuts)
+FINISH = {}
+
+
 @functools.lru_cache(maxsize=None)
 def get_case(name):
     """The case's fp64 inputs (cached; treat as read-only)."""
     kind, dims, kw, _ = CASES[name]
     rng = np.random.default_rng(zlib.crc32(name.encode()))
     c = {"flood": flood_case, "lattice": lattice_case}.get(kind, exact_case)(rng, *dims, **kw)
+    if name in FINISH:
+        c = FINISH[name](c, rng)
     for v in c.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
