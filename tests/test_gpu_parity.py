@@ -18,7 +18,9 @@ from conftest import MODES, case_id, digest_cases, golden_cases, kink_mask, mode
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-FWD_TOL = {torch.float32: dict(atol=1e-4, rtol=1e-3), torch.float64: dict(atol=1e-8, rtol=1e-8)}
+# Smoke tolerances: 10 to 13 bits wider than float32 arithmetic delivers.  The tight, derived per-element bound on generic
+# inputs lives in tests/error_bound_cases.py and is held by tests/test_gpu_error_bounds.py.
+FWD_TOL ={torch.float32: dict(atol=1e-4, rtol=1e-3), torch.float64: dict(atol=1e-8, rtol=1e-8)}
 BWD_TOL = {torch.float32: dict(atol=1e-3, rtol=1e-2), torch.float64: dict(atol=1e-8, rtol=1e-8)}
 
 
