@@ -738,6 +738,12 @@ MSDA_API int msda_get_option(const char *key);
  * arithmetic type, or 1 when D is no multiple of that or a row pointer is not 16-byte aligned;  group: lanes per (b, q, h)
  * unit, the smallest of 4, 8, 16, 32, 64 that holds ceil(D / vec) — 64 beyond;  chunks: ceil(D / (group * vec)) trips
  * of the kernels' channel loop.  0 before the first launch of that kind.
+ * PASSES OVER A UNIT'S SAMPLES (last values, added within ABI 12): "fwd_trips" of the last forward launch and "sample_trips"
+ * of the last sample-gradient launch — ceil(S / sc) for a unit of S samples (L * P, or the sum of points_per_level), sc being
+ * the samples the kernel parks in LDS per trip (the 256-thread kernels: 48 KiB of records for the workgroup's 256 / group
+ * units, less one; the LDS-served-level kernels: 72 KiB, or 100 KiB for the fused backward, for 1024 / group units, a
+ * multi-trip sc rounded down to a multiple of group) or, in the one-wave-per-unit forward, the 64 / U samples a wave's
+ * U units take per trip.  1 for the discrete kernels, which park nothing.
  * THE SORTED PIPELINE'S TABLES (last values, added within ABI 12 by name; all 0 after a single-launch grad_value):
  * "value_cell_cap" cells of the LDS table of the count pass (and of the plane-major place pass) — a plane with more cells is
  * walked in ceil(cells / value_cell_cap) trips, a plane's cells being sum_l (h_l + 1) * (w_l + 1);  "value_place_cells" cells of

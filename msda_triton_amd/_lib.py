@@ -361,6 +361,7 @@ def get_option(key: str) -> int:
 LAUNCH_INFO_KEYS = ("fwd_variant", "fwd_lds_level_bytes", "fwd_lds_planes", "fwd_workgroups", "sample_variant",
                     "sample_lds_level_bytes", "value_path", "value_passes", "fwd_vec", "fwd_group", "fwd_chunks",
                     "sample_vec", "sample_group", "sample_chunks", "value_vec", "value_group", "value_chunks",
+                    "fwd_trips", "sample_trips",
                     "value_cell_cap", "value_place_cells", "value_place_variant", "value_slices", "value_rounds", "value_win",
                     "grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches")
 # the last three are counters (launches per grid form since the process started): callers take differences around a call

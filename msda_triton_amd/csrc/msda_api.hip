@@ -145,7 +145,7 @@ void profile_end(void *token, hipStream_t stream)
 
 // ---- measurement only: what the last launches were (msda_last_launch_info) — process-wide, like the profile records:
 //      autograd issues the backward from its own thread ----
-constexpr int kLaunchInfoSlots = 23;  // (msda_launch.hpp, note_launch: 0-7 as before, 8-16 the instantiations, 17-22 the sorted pipeline)
+constexpr int kLaunchInfoSlots = 25;  // (msda_launch.hpp, note_launch: 0-7 as before, 8-16 the instantiations, 17-22 the sorted pipeline, 23-24 the trips)
 static std::atomic<int> g_info[kLaunchInfoSlots];
 void note_launch(int slot, int value)
 {
@@ -182,7 +182,9 @@ extern "C" int msda_last_launch_info(const char *key)
         "fwd_vec", "fwd_group", "fwd_chunks", "sample_vec", "sample_group", "sample_chunks", "value_vec", "value_group",
         "value_chunks",
         // the sorted grad_value pipeline's table sizes, place-pass variant, query slices, rounds and gather window
-        "value_cell_cap", "value_place_cells", "value_place_variant", "value_slices", "value_rounds", "value_win"};
+        "value_cell_cap", "value_place_cells", "value_place_variant", "value_slices", "value_rounds", "value_win",
+        // passes over a unit's samples of the last forward / sample-gradient launch (note_trips)
+        "fwd_trips", "sample_trips"};
     for (int i = 0; key != nullptr && i < msda::kLaunchInfoSlots; ++i)
         if (strcmp(key, kKeys[i]) == 0) return msda::g_info[i].load(std::memory_order_relaxed);
     static const char *const kGridKeys[3] = {"grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches"};

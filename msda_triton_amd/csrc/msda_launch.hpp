@@ -34,6 +34,11 @@ inline void note_instance(int first_slot, int vec, int group, int D)
     note_launch(first_slot + 1, group);
     note_launch(first_slot + 2, (D + group * vec - 1) / (group * vec));
 }
+// ... and how many passes the launch makes over a unit's S samples: ceil(S / sc), sc samples parked per trip (plan_gather, the
+// LDS-served-level plan) or taken per trip by a wave's 64 / U lanes (the one-wave-per-unit forward) — slot 23 the forward
+// ("fwd_trips"), 24 the sample gradients ("sample_trips"); 1 for the discrete kernels, which park nothing.  For tests: a moved
+// cap must not turn a three-trip case into a one-trip one.
+inline void note_trips(int slot, int S, int sc) { note_launch(slot, sc > 0 ? (S + sc - 1) / sc : 0); }
 // ... and which grid form plane_grid gave a launch: 0 XCD-aware 3-D, 1 linear 2-D, 2 flat 1-D — one process-wide counter per
 // form that only ever rises ("grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches"; callers take differences)
 void note_grid(int form);
@@ -395,10 +400,12 @@ template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T, ty
         note_launch(2, pl.planes);
         note_launch(3, (int)(grid.x * grid.y * grid.z));
         note_instance(8, VEC, G, p.D);
+        note_trips(23, p.LP, pl.sc);
     } else {
         note_launch(4, 1);
         note_launch(5, pl.lev_bytes);
         note_instance(11, VEC, G, p.D);
+        note_trips(24, p.LP, pl.sc);
     }
     const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
     if constexpr (MODE == 0 || MODE == 2) {
@@ -454,7 +461,9 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
             // units per wave: rows in the Infinity Cache Q = 100 7.96 / 8.32 us, 200 9.60 / 9.68, 300 11.28 / 11.92; rows in
             // HBM 100 10.4 / 10.4, 200 13.5 / 12.6, 300 16.7 / 15.4 (tools/small_q_cold.py --flush 256 / 1024).
             const bool pairs_ok = gl <= kWave / 2 && (size_t)p.B * p.I * (size_t)p.v_row < ((size_t)1 << 31);
-            if (pairs_ok && option_unit_waves() == 2) {
+            const bool pairs = pairs_ok && option_unit_waves() == 2;
+            note_trips(23, p.LP, kWave / (pairs ? 2 : 1));  // (a unit's 64 / U lanes take one sample each per trip)
+            if (pairs) {
                 p.div_win = make_fast_div((uint32_t)p.Q);  // (the forward has no other use for this field)
                 auto kernel = msda_fwd_unit_kernel<T, VEC, TV, 2, PP>;
                 allow_big_lds(kernel, big_lds_unit2);
@@ -517,10 +526,12 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         note_launch(2, 1);
         note_launch(3, (int)(grid.x * grid.y * grid.z));
         note_instance(8, VEC, G, p.D);
+        note_trips(23, p.LP, p.sc);
     } else {
         note_launch(4, 0);
         note_launch(5, 0);
         note_instance(11, VEC, G, p.D);
+        note_trips(24, p.LP, p.sc);
     }
     static std::atomic<uint64_t> big_lds_done{0};  // one per template instantiation
     const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
@@ -951,12 +962,14 @@ template <typename T, int VEC, int G, int MODE, typename TV> inline int launch_d
         note_launch(2, 1);
         note_launch(3, (int)(grid.x * grid.y * grid.z));
         note_instance(8, VEC, G, p.D);
+        note_launch(23, 1);
         const ProfileScope prof("msda_fwd_discrete_kernel", stream);
         hipLaunchKernelGGL((msda_fwd_discrete_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
     } else {
         note_launch(4, 2);
         note_launch(5, 0);
         note_instance(11, VEC, G, p.D);
+        note_launch(24, 1);
         const ProfileScope prof("msda_bwd_discrete_attn_kernel", stream);
         hipLaunchKernelGGL((msda_bwd_discrete_attn_kernel<T, VEC, G, TV>), grid, dim3(kBlock), 0, stream, p);
     }
@@ -1000,12 +1013,14 @@ inline int launch_hfbox_discrete(HfBoxDiscreteParams &p, hipStream_t stream)
         note_launch(2, 1);
         note_launch(3, (int)(grid.x * grid.y * grid.z));
         note_instance(8, VEC, G, p.D);
+        note_launch(23, 1);
         const ProfileScope prof("msda_fwd_hfbox_discrete_kernel", stream);
         hipLaunchKernelGGL((msda_fwd_hfbox_discrete_kernel<T, VEC, G, TV, TS>), grid, dim3(kBlock), 0, stream, p);
     } else {
         note_launch(4, 3);
         note_launch(5, 0);
         note_instance(11, VEC, G, p.D);
+        note_launch(24, 1);
         const ProfileScope prof("msda_bwd_hfbox_discrete_kernel", stream);
         hipLaunchKernelGGL((msda_bwd_hfbox_discrete_kernel<T, VEC, G, TV, TS>), grid, dim3(kBlock), 0, stream, p);
     }

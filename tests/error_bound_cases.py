@@ -520,6 +520,16 @@ FUSED = {
     "hfbox": ("hfbox", 4, [3, 1, 2]), "hfbox_discrete": ("hfbox", 4, [3, 1, 2]),
 }
 FUSED_DIMS = dict(B=2, Q=37, H=3, D=32)
+# ... and the names a helper module registers (tests/sample_level_cases.py), in tables of their own so that what iterates
+# FUSED sees the same names whatever was imported before: name -> FUSED's tuple, name -> (dims as FUSED_DIMS, levels)
+FUSED_MORE = {}
+FUSED_SHAPES = {}
+FUSED_DISCRETE = {"hfbox_discrete"}  # the names whose operator behind the prologue is discrete sampling
+
+
+def fused_entry(name):
+    """(rule, ref_dim, P or counts) of a name of FUSED or FUSED_MORE"""
+    return FUSED[name] if name in FUSED else FUSED_MORE[name]
 
 
 def ev_exp(z):
@@ -548,14 +558,15 @@ def _sample_levels(proj, counts):
 
 @functools.lru_cache(maxsize=None)
 def fused_raw_case(name):
-    rule, ref_dim, P = FUSED[name]
+    rule, ref_dim, P = fused_entry(name)
     rng = np.random.default_rng(zlib.crc32(("error_bound_fused_" + name).encode()) + SEEDS.get(name, 0))
-    B, Q, H, D = (FUSED_DIMS[k] for k in "BQHD")
+    dims, levels = FUSED_SHAPES.get(name, (FUSED_DIMS, LEVELS))
+    B, Q, H, D = (dims[k] for k in "BQHD")
     counts = None if isinstance(P, int) else list(P)
-    shapes = np.asarray(LEVELS, dtype=np.int64)
-    pts = (len(LEVELS), P) if counts is None else (sum(counts),)
+    shapes = np.asarray(levels, dtype=np.int64)
+    pts = (len(levels), P) if counts is None else (sum(counts),)
     lvl, npts, _, _ = _sample_levels(np.zeros((B, Q, H) + pts + (3,)), counts)
-    ref_shape = (B, Q, len(LEVELS), ref_dim) if rule == "levelref" else (B, Q, ref_dim)
+    ref_shape = (B, Q, len(levels), ref_dim) if rule == "levelref" else (B, Q, ref_dim)
     ref = rng.uniform(0.1, 0.9, size=ref_shape)
     if ref_dim == 4:
         ref[..., 2:] = rng.uniform(0.2, 0.6, size=ref_shape[:-1] + (2,))
@@ -609,7 +620,7 @@ def prologue(fc, name, scale_fn=None):
     """The sampling points (x, y), the attention weights, d point / d offset (kx, ky), the parked offsets the box-size
     gradient multiplies and the factor applied behind its sum — each an Ev in the layout of proj[..., 0].  scale_fn: a
     mutant's rounding of the box rule's float32(1 / P_l)."""
-    rule, ref_dim, _ = FUSED[name]
+    rule, ref_dim, _ = fused_entry(name)
     proj, counts = fc["proj"], fc.get("counts")
     lvl, npts, _, S = _sample_levels(proj, counts)
     hs, ws = fc["shapes"][lvl, 0].astype(np.float64), fc["shapes"][lvl, 1].astype(np.float64)
@@ -669,14 +680,14 @@ def fused_operator_case(fc, pro):
 
 def fused_formulas(fc, name, pm, ac, records="float", pro=None):
     """out, grad_value, grad_proj and grad_ref of a fused family as Ev, and what to keep of them."""
-    rule, ref_dim, _ = FUSED[name]
+    rule, ref_dim, _ = fused_entry(name)
     pro = prologue(fc, name) if pro is None else pro
     c = fused_operator_case(fc, pro)
     loc_err = np.stack([pro["x"].err, pro["y"].err], -1)
     _, _, saxes, S = _sample_levels(fc["proj"], fc.get("counts"))
     H = fc["value"].shape[2]
     a = pro["a"]
-    if name == "hfbox_discrete":
+    if name in FUSED_DISCRETE:
         base, keep0, near = discrete_formulas(c, loc_err, a.err)
         gA = base["grad_attn"]
         dot = (a * gA).sum(3, n=S)                                                # msda_hfbox_discrete.hpp:251-255
@@ -725,7 +736,7 @@ def fused_torch(fc, name, pm, ac, dtype):
     of the host operator (as tests/test_gpu_hf_box_fused.py and tests/test_gpu_hf_box_discrete.py build their references)."""
     from msda_triton_amd import functional as F, ragged
     from msda_triton_amd.functional import multiscale_deformable_attention
-    rule, _, _ = FUSED[name]
+    rule, _, _ = fused_entry(name)
     t = {k: torch.from_numpy(np.array(fc[k])).to(dtype).requires_grad_(True) for k in ("value", "proj", "ref")}
     shapes, counts = torch.from_numpy(np.array(fc["shapes"])), fc.get("counts")
     if rule == "hfbox":
@@ -737,13 +748,13 @@ def fused_torch(fc, name, pm, ac, dtype):
     else:
         pts, att = F.module_sampling_inputs(t["proj"], shapes, t["ref"])
     kw = dict(points_per_level=counts) if counts is not None else {}
-    if name == "hfbox_discrete":
+    if name in FUSED_DISCRETE:
         out = multiscale_deformable_attention(t["value"], shapes, pts, att, "border", False, sampling_mode="discrete", **kw)
     else:
         out = multiscale_deformable_attention(t["value"], shapes, pts, att, pm, ac, **kw)
     out.backward(torch.from_numpy(np.array(fc["grad_out"])).to(dtype))
     res = dict(out=out.detach(), grad_value=t["value"].grad, grad_proj=t["proj"].grad)
-    if name != "hfbox_discrete":
+    if name not in FUSED_DISCRETE:
         res["grad_ref"] = t["ref"].grad
     return res
 

@@ -29,7 +29,8 @@ def test_the_library_knows_the_sorted_pipelines_counters():
     six counters of the sorted pipeline sit in front of the three grid-form counters, which stay the last three"""
     from msda_triton_amd import _lib
     assert _lib.GRID_FORM_KEYS == ("grid_xcd3d_launches", "grid_linear2d_launches", "grid_flat_launches")
-    assert _lib.LAUNCH_INFO_KEYS[-9:-3] == SORTED_KEYS and len(set(_lib.LAUNCH_INFO_KEYS)) == len(_lib.LAUNCH_INFO_KEYS) == 26
+    assert _lib.LAUNCH_INFO_KEYS[-9:-3] == SORTED_KEYS and len(set(_lib.LAUNCH_INFO_KEYS)) == len(_lib.LAUNCH_INFO_KEYS) == 28
+    assert _lib.LAUNCH_INFO_KEYS[-11:-9] == ("fwd_trips", "sample_trips")  # (the passes over a unit's samples, in front of those)
     lib = _lib.load()
     for k in _lib.LAUNCH_INFO_KEYS:
         assert int(lib.msda_last_launch_info(k.encode())) >= 0, k
