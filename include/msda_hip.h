@@ -581,6 +581,50 @@ MSDA_HFBOX_DISCRETE_QUERY(workspace_bytes)
 #undef MSDA_HFBOX_DISCRETE_QUERY
 
 /*
+ * The REFERENCE MODULE's rule in front of DISCRETE sampling (MultiscaleDeformableAttention(sampling_mode="discrete"),
+ * functional.fused_module_core(..., sampling_mode="discrete")) — ADDITIONS WITHIN ABI 12, probed by symbol:
+ * msda_fwd_fused_discrete_<suffix> / msda_bwd_fused_discrete_<suffix> (the same eight suffixes) and
+ * msda_bwd_fused_discrete_workspace_bytes.  The argument lists are the hfbox-discrete pair's with `int ref_dim` in place of
+ * `level_scale, offset_scale`; `proj` is [B, Q, H, S, 3] level-major (a uniform point count is the same call with equal
+ * counts), `ref` [B, Q, ref_dim]:
+ *
+ *   a_s   = softmax over the unit's S logits proj[..., 2]
+ *   point, ref_dim 2:  x = ref_x + ox / shapes[l][0]           y = ref_y + oy / shapes[l][1]     (the stored (h, w) order,
+ *                                                                                                as msda_fwd_fused_<dtype>)
+ *   point, ref_dim 4:  x = ref_x + ox * ref_w / (2 P_l)        y = ref_y + oy * ref_h / (2 P_l)  (P_l: the sample's level)
+ *   out[b, q, head, :] = sum_s a_s * value[b, start_l + iy * w + ix, head, :]   the pixel rule of msda_fwd_discrete_<dtype>
+ *
+ * Every operation is rounded once in fp32 (fp64 for f64; the 16-bit operators form the point in fp32 from the stored
+ * values): a multiply, a correctly rounded TRUE division — not a multiplication by a reciprocal —, an add, then the
+ * discrete operator's multiply and add, none of them fused.  The kernel bodies, grad_proj (offset slots stored zeros, no
+ * gradient for `ref`), the parked points and weights, the discrete grad_value pipeline behind them, the frozen-pyramid
+ * call, the workspace (msda_bwd_fused_discrete_workspace_bytes answers what the hfbox-discrete query answers) and the
+ * limits are the hfbox-discrete pair's: L <= 8 (more: MSDA_ERR_UNSUPPORTED), S unbounded.  ref_dim other than 2 / 4 is
+ * MSDA_ERR_BAD_ARG.  Everything is answered BEFORE anything is launched.  No padding masks (the caller composes them).
+ * msda_last_launch_info: "fwd_variant" 4, "sample_variant" 3 — the box-rule discrete pair's, the bodies are the same.
+ */
+#define MSDA_MODULE_DISCRETE(SUF)                                                                      \
+    MSDA_API int msda_fwd_fused_discrete_##SUF(const void *value, const int64_t *shapes,            \
+                       const void *proj, const void *ref, void *out, int64_t B, int64_t I,          \
+                       int64_t H, int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level, \
+                       int ref_dim, int64_t value_row_stride, void *stream);                        \
+    MSDA_API int msda_bwd_fused_discrete_##SUF(const void *grad_out, const void *value,             \
+                       const int64_t *shapes, const void *proj, const void *ref, void *grad_value,  \
+                       void *grad_proj, int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q,      \
+                       int64_t L, const int32_t *points_per_level, int ref_dim,                     \
+                       int64_t max_level_cells, int64_t value_row_stride, void *workspace,          \
+                       int64_t workspace_bytes, void *stream);
+#define MSDA_MODULE_DISCRETE_QUERY(WHAT)                                                               \
+    MSDA_API int64_t msda_bwd_fused_discrete_##WHAT(int64_t B, int64_t I, int64_t H, int64_t D,     \
+                       int64_t Q, int64_t L, const int32_t *points_per_level, int elem_size,        \
+                       int value_elem_size, int64_t max_level_cells, int flags);
+MSDA_MODULE_DISCRETE(f32) MSDA_MODULE_DISCRETE(f16) MSDA_MODULE_DISCRETE(bf16) MSDA_MODULE_DISCRETE(f64)
+MSDA_MODULE_DISCRETE(f32_vbf16) MSDA_MODULE_DISCRETE(f32_vf16) MSDA_MODULE_DISCRETE(f32_sbf16) MSDA_MODULE_DISCRETE(f32_sf16)
+MSDA_MODULE_DISCRETE_QUERY(workspace_bytes)
+#undef MSDA_MODULE_DISCRETE
+#undef MSDA_MODULE_DISCRETE_QUERY
+
+/*
  * Bytes of device workspace msda_bwd_<dtype> wants for these sizes.  elem_size: of everything but `value`;
  * value_elem_size: of `value` / `grad_value` (0: the same — 2 next to elem_size 4 for the mixed-storage entry points);
  * max_level_cells: as for the call (0: unknown).

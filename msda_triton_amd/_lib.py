@@ -68,6 +68,12 @@ MODULE_MASK_SYMBOLS = tuple(
     + [f"msda_{d}_fused_ragged_masked_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
 )
 
+# ... and the reference module's own rule in front of discrete sampling (has_module_discrete): the same suffixes
+MODULE_DISCRETE_SYMBOLS = tuple(
+    [f"msda_{d}_fused_discrete_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES]
+    + ["msda_bwd_fused_discrete_workspace_bytes"]
+)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -244,6 +250,21 @@ def load():
                 ghd.argtypes = [vp] * 7 + [i64] * 6 + [vp, vp, cd, i64, i64, vp, i64, vp]
             lib.msda_bwd_fused_hfbox_discrete_workspace_bytes.restype = i64
             lib.msda_bwd_fused_hfbox_discrete_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
+        # the module's own rule in front of discrete sampling: additions within ABI 12 (has_module_discrete); the
+        # hfbox-discrete pair's lists with `int ref_dim` in place of (level_scale, offset_scale)
+        if hasattr(lib, "msda_bwd_fused_discrete_workspace_bytes"):
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                fmd = getattr(lib, f"msda_fwd_fused_discrete_{suf}")
+                fmd.restype = ci
+                # (value, shapes, proj, ref, out, B ... L, points_per_level, ref_dim, value_row_stride, stream)
+                fmd.argtypes = [vp] * 5 + [i64] * 6 + [vp, ci, i64, vp]
+                gmd = getattr(lib, f"msda_bwd_fused_discrete_{suf}")
+                gmd.restype = ci
+                # (grad_out, value, shapes, proj, ref, grad_value, grad_proj, B ... L, points_per_level, ref_dim,
+                #  max_level_cells, value_row_stride, workspace, workspace_bytes, stream)
+                gmd.argtypes = [vp] * 7 + [i64] * 6 + [vp, ci, i64, i64, vp, i64, vp]
+            lib.msda_bwd_fused_discrete_workspace_bytes.restype = i64
+            lib.msda_bwd_fused_discrete_workspace_bytes.argtypes = [i64] * 6 + [vp, ci, ci, i64, ci]
         # both masks inside the module's own fused pairs: additions within ABI 12 (has_module_masks); the fused / fused
         # ragged pairs' lists with `value_mask`, `query_mask` behind `value`
         if hasattr(lib, "msda_bwd_fused_ragged_masked_f32"):
@@ -314,6 +335,13 @@ def has_fused_hfbox_discrete() -> bool:
     additions within ABI 12, found by symbol)?  Without them the caller composes transformers' prologue around the
     discrete operator."""
     return hasattr(load(), "msda_bwd_fused_hfbox_discrete_workspace_bytes")
+
+
+def has_module_discrete() -> bool:
+    """Does the loaded library have the reference module's rule in front of discrete sampling
+    (msda_fwd_fused_discrete_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller composes the
+    module's prologue around the discrete operator."""
+    return hasattr(load(), "msda_bwd_fused_discrete_workspace_bytes")
 
 
 def has_value_mask() -> bool:

@@ -174,6 +174,15 @@ extern "C" int64_t msda_bwd_fused_hfbox_discrete_workspace_bytes(int64_t B, int6
            msda::sorted_ws_bytes(d, elem_size, false, 0, msda::passes_of(flags));
 }
 
+// the reference module's rule in front of discrete sampling: the same buffers, so the same answer
+extern "C" int64_t msda_bwd_fused_discrete_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
+                                                           const int32_t *points_per_level, int elem_size,
+                                                           int value_elem_size, int64_t max_level_cells, int flags)
+{
+    return msda_bwd_fused_hfbox_discrete_workspace_bytes(B, I, H, D, Q, L, points_per_level, elem_size, value_elem_size,
+                                                         max_level_cells, flags);
+}
+
 extern "C" int msda_bwd_discrete_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                            const int32_t *points_per_level, int elem_size)
 {

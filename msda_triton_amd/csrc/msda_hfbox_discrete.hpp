@@ -1,5 +1,7 @@
 // msda_hfbox_discrete.hpp — Hugging Face's box rule in front of DISCRETE sampling (D-FINE / DEIMv2 / RT-DETRv2 with
-// decoder_method = "discrete"): msda_{fwd,bwd}_fused_hfbox_discrete_<suffix>.
+// decoder_method = "discrete"): msda_{fwd,bwd}_fused_hfbox_discrete_<suffix> — and, through the same two kernels
+// instantiated for another kernarg type, the reference module's own rule: msda_{fwd,bwd}_fused_discrete_<suffix>
+// (ModuleDiscreteParams; the rule is stated at its fused_discrete_sample overload below).
 //
 // The kernels are msda_discrete.hpp's — one (b, head) plane per workgroup, G lanes per unit, VEC channels per lane, chunked
 // trips over wide rows, the plane behind a buffer descriptor — with the module's prologue in the lanes instead of loaded
@@ -57,7 +59,7 @@ template <typename T> __device__ __forceinline__ UnitBox<typename Traits<T>::acc
 
 // Sample s of a unit from its projection triple: the point (x, y), the logit and the row offset of its ONE pixel.
 template <typename A, typename TS>
-__device__ __forceinline__ uint32_t hfbox_discrete_sample(const HfBoxDiscreteParams &p, const LevelTab &tab, const TS *proj3, int s,
+__device__ __forceinline__ uint32_t fused_discrete_sample(const HfBoxDiscreteParams &p, const LevelTab &tab, const TS *proj3, int s,
                                                          const UnitBox<A> &box, A &x, A &y, A &logit)
 {
     using SR = Traits<TS>;
@@ -72,9 +74,47 @@ __device__ __forceinline__ uint32_t hfbox_discrete_sample(const HfBoxDiscretePar
     return mad24(mad24((uint32_t)iy, (uint32_t)w, (uint32_t)tab.start[l]) + (uint32_t)ix, (uint32_t)p.v_row, 0u);
 }
 
+// ---- the reference module's rule (msda_*_fused_discrete_<suffix>; frontend.py:253-282, as the bilinear fused kernels keep
+// it): `ref` is [B, Q, ref_dim], the kernarg ModuleDiscreteParams ----
+//   2-d   x = ref_x + ox / h_l                 y = ref_y + oy / w_l          (img_shapes in its stored (h, w) order)
+//   4-d   x = ref_x + ox * ref_w / (2 P_l)     y = ref_y + oy * ref_h / (2 P_l)   (P_l: the count of the sample's own level)
+// a rounded multiply (4-d only), a correctly rounded TRUE division — not a multiplication by a reciprocal, which differs
+// for P_l = 3 —, a rounded add.  The division sits between the other two, so -ffp-contract=fast finds nothing to fuse.
+// The reference point of a unit's query: (x, y), and the box size for 4-d (zeros for 2-d: never read)
+template <typename T>
+__device__ __forceinline__ UnitBox<typename Traits<T>::acc> load_unit_box(const ModuleDiscreteParams &p, int b, int q)
+{
+    using TR = Traits<T>;
+    using A = typename TR::acc;
+    const T *r = static_cast<const T *>(p.ref) + ((size_t)b * p.Q + q) * p.ref_dim;
+    const bool box = p.ref_dim == 4;  // (uniform)
+    return {TR::to_acc(r[0]), TR::to_acc(r[1]), box ? TR::to_acc(r[2]) : (A)0, box ? TR::to_acc(r[3]) : (A)0};
+}
+template <typename A, typename TS>
+__device__ __forceinline__ uint32_t fused_discrete_sample(const ModuleDiscreteParams &p, const LevelTab &tab, const TS *proj3, int s,
+                                                         const UnitBox<A> &box, A &x, A &y, A &logit)
+{
+    using SR = Traits<TS>;
+    const A ox = SR::to_acc(proj3[3 * s]), oy = SR::to_acc(proj3[3 * s + 1]);
+    logit = SR::to_acc(proj3[3 * s + 2]);
+    int npts;
+    const int l = lvl_of(p, s, npts);
+    const int w = tab.w[l], h = tab.h[l];
+    // one division per axis for both rules: numerator and denominator are selected on the uniform ref_dim
+    const bool box4 = p.ref_dim == 4;
+    const A den = (A)(2 * npts);
+    const A nx = box4 ? ox * box.w : ox, ny = box4 ? oy * box.h : oy;
+    x = box.x + nx / (box4 ? den : (A)h);
+    y = box.y + ny / (box4 ? den : (A)w);
+    const int ix = discrete_pixel<A>(x, w), iy = discrete_pixel<A>(y, h);
+    return mad24(mad24((uint32_t)iy, (uint32_t)w, (uint32_t)tab.start[l]) + (uint32_t)ix, (uint32_t)p.v_row, 0u);
+}
+
+// The forward of either rule: PP = HfBoxDiscreteParams or ModuleDiscreteParams picks fused_discrete_sample's and
+// load_unit_box's overload, nothing else differs.
 // T: arithmetic and box type, TV: value rows, TS: projection and out
-template <typename T, int VEC, int G, typename TV, typename TS>
-__global__ __launch_bounds__(kBlock) void msda_fwd_hfbox_discrete_kernel(const HfBoxDiscreteParams p)
+template <typename T, int VEC, int G, typename TV, typename TS, typename PP>
+__global__ __launch_bounds__(kBlock) void msda_fwd_hfbox_discrete_kernel(const PP p)
 {
     using A = typename Traits<T>::acc;
     using SR = Traits<TS>;
@@ -109,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void msda_fwd_hfbox_discrete_kernel(const H
         A a = (A)0;
         if (live && s < S) {
             A x, y, logit;
-            off = hfbox_discrete_sample<A>(p, tab, proj3, s, box, x, y, logit);
+            off = fused_discrete_sample<A>(p, tab, proj3, s, box, x, y, logit);
             a = sm.weight(logit);
         }
         const int n = min(G, S - s0);  // (uniform)
@@ -170,8 +210,9 @@ template <typename A, typename TS> struct GradTriple {
     }
 };
 
-template <typename T, int VEC, int G, typename TV, typename TS>
-__global__ __launch_bounds__(kBlock) void msda_bwd_hfbox_discrete_kernel(const HfBoxDiscreteParams p)
+// (PP: as the forward's)
+template <typename T, int VEC, int G, typename TV, typename TS, typename PP>
+__global__ __launch_bounds__(kBlock) void msda_bwd_hfbox_discrete_kernel(const PP p)
 {
     using A = typename Traits<T>::acc;
     using SR = Traits<TS>;
@@ -214,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void msda_bwd_hfbox_discrete_kernel(const H
         A a = (A)0;
         if (live && s < S) {
             A x, y, logit;
-            off = hfbox_discrete_sample<A>(p, tab, proj3, s, box, x, y, logit);
+            off = fused_discrete_sample<A>(p, tab, proj3, s, box, x, y, logit);
             a = sm.weight(logit);
             if (p.mat_loc != nullptr) {  // for the grad_value passes: the point the forward sampled and its weight
                 Pack<MT, 2> m;

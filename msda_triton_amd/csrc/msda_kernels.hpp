@@ -295,6 +295,13 @@ struct HfBoxDiscreteParams : DiscreteParams {
 };
 template <typename PP> constexpr bool kHfBoxDiscrete = std::is_base_of<HfBoxDiscreteParams, PP>::value;
 template <typename PP> constexpr bool kHfBox = std::is_base_of<HfBoxParams, PP>::value || kHfBoxDiscrete<PP>;
+// ... and the REFERENCE MODULE's rule in front of discrete sampling (msda_*_fused_discrete_<dtype>, the kernel bodies of
+// msda_hfbox_discrete.hpp with another per-sample rule): the discrete kernarg under a type of its own and nothing behind
+// it — Params::ref_dim says which of the module's two rules applies, the level's own count comes from lvl_of's scan.
+struct ModuleDiscreteParams : DiscreteParams {};
+template <typename PP> constexpr bool kModuleDiscrete = std::is_base_of<ModuleDiscreteParams, PP>::value;
+// either prologue in front of discrete sampling: the launch layer's steps the two pairs share
+template <typename PP> constexpr bool kFusedDiscrete = kHfBoxDiscrete<PP> || kModuleDiscrete<PP>;
 
 // s_l of the sample's level, converted to the arithmetic type: a select per level on scalars at constant kernarg offsets
 // (as lvl_of's scan; the level itself comes from that scan, the host bounds L by kFusedRaggedMaxLevels).

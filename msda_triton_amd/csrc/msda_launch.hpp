@@ -997,8 +997,10 @@ template <typename T, int MODE, typename TV> inline int dispatch_discrete(Discre
 // MODE 0: the forward, 1: the backward (grad_proj; the points and weights for the grad_value passes).  The geometry is
 // launch_discrete's; the kernels' level scan is the fused kernels' (at most kFusedRaggedMaxLevels scales in the kernarg),
 // refused here, before anything is launched.
-template <typename T, int VEC, int G, int MODE, typename TV, typename TS>
-inline int launch_hfbox_discrete(HfBoxDiscreteParams &p, hipStream_t stream)
+// PP = ModuleDiscreteParams (msda_{fwd,bwd}_fused_discrete_<suffix>): the same bodies behind the reference module's rule —
+// the same variants, the same bound on L (lvl_of's count scan).
+template <typename T, int VEC, int G, int MODE, typename TV, typename TS, typename PP>
+inline int launch_hfbox_discrete(PP &p, hipStream_t stream)
 {
     constexpr int NU = kBlock / G;
     p.nqc = (p.Q + NU - 1) / NU;
@@ -1014,20 +1016,20 @@ inline int launch_hfbox_discrete(HfBoxDiscreteParams &p, hipStream_t stream)
         note_launch(3, (int)(grid.x * grid.y * grid.z));
         note_instance(8, VEC, G, p.D);
         note_launch(23, 1);
-        const ProfileScope prof("msda_fwd_hfbox_discrete_kernel", stream);
-        hipLaunchKernelGGL((msda_fwd_hfbox_discrete_kernel<T, VEC, G, TV, TS>), grid, dim3(kBlock), 0, stream, p);
+        const ProfileScope prof(kModuleDiscrete<PP> ? "msda_fwd_module_discrete_kernel" : "msda_fwd_hfbox_discrete_kernel", stream);
+        hipLaunchKernelGGL((msda_fwd_hfbox_discrete_kernel<T, VEC, G, TV, TS, PP>), grid, dim3(kBlock), 0, stream, p);
     } else {
         note_launch(4, 3);
         note_launch(5, 0);
         note_instance(11, VEC, G, p.D);
         note_launch(24, 1);
-        const ProfileScope prof("msda_bwd_hfbox_discrete_kernel", stream);
-        hipLaunchKernelGGL((msda_bwd_hfbox_discrete_kernel<T, VEC, G, TV, TS>), grid, dim3(kBlock), 0, stream, p);
+        const ProfileScope prof(kModuleDiscrete<PP> ? "msda_bwd_module_discrete_kernel" : "msda_bwd_hfbox_discrete_kernel", stream);
+        hipLaunchKernelGGL((msda_bwd_hfbox_discrete_kernel<T, VEC, G, TV, TS, PP>), grid, dim3(kBlock), 0, stream, p);
     }
     return (int)hipGetLastError();
 }
-template <typename T, int VEC, int MODE, typename TV, typename TS>
-inline int dispatch_hfbox_discrete_group(HfBoxDiscreteParams &p, hipStream_t stream)
+template <typename T, int VEC, int MODE, typename TV, typename TS, typename PP>
+inline int dispatch_hfbox_discrete_group(PP &p, hipStream_t stream)
 {
     switch (pick_group((p.D + VEC - 1) / VEC)) {
     case 4: return launch_hfbox_discrete<T, VEC, 4, MODE, TV, TS>(p, stream);
@@ -1037,12 +1039,12 @@ inline int dispatch_hfbox_discrete_group(HfBoxDiscreteParams &p, hipStream_t str
     default: return launch_hfbox_discrete<T, VEC, 64, MODE, TV, TS>(p, stream);
     }
 }
-template <typename T, int MODE, typename TV, typename TS>
-inline int dispatch_hfbox_discrete(HfBoxDiscreteParams &p, bool vec_ok, hipStream_t stream)
+template <typename T, int MODE, typename TV, typename TS, typename PP>
+inline int dispatch_hfbox_discrete(PP &p, bool vec_ok, hipStream_t stream)
 {
     constexpr int VECF = 16 / sizeof(T);
     if (p.L > kFusedRaggedMaxLevels) {
-        set_error("the fused box prologue serves at most %d levels, got %d", kFusedRaggedMaxLevels, p.L);
+        set_error("the fused %s prologue serves at most %d levels, got %d", kModuleDiscrete<PP> ? "module" : "box", kFusedRaggedMaxLevels, p.L);
         return MSDA_ERR_UNSUPPORTED;
     }
     if (vec_ok && (p.D % VECF) == 0) return dispatch_hfbox_discrete_group<T, VECF, MODE, TV, TS>(p, stream);
@@ -1156,6 +1158,7 @@ template <typename T, typename TV = T, typename PP = Params> int run_fwd(const C
 // holds L fp32 scales on the host, `offset_scale` the config's (the entry point checked ref_dim == 4)
 // PP = HfBoxDiscreteParams (msda_fwd_fused_hfbox_discrete_<dtype>): the same rule in front of discrete sampling, on the
 // kernels of msda_hfbox_discrete.hpp (no padding mode — border —, no 32-bit limit on the projection)
+// PP = ModuleDiscreteParams (msda_fwd_fused_discrete_<dtype>): the module's own rule (ref_dim 2 or 4) on the same kernel bodies
 // PP = MaskedParams (msda_fwd_fused_masked_<dtype>) / RaggedMaskedParams (msda_fwd_fused_ragged_masked_<dtype>): the module's
 // own rule, uniform / per-level counts, with the value mask and (unless NULL) the query mask in the kernels
 template <typename T, typename TV = T, typename TS = T, typename PP = Params> int run_fwd_fused(const Call &c)
@@ -1170,7 +1173,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     if (rc) return rc;
     if (samples(d) == 0 || d.I == 0) return zero_outputs({{c.out, out_bytes}}, stream);
     if ((rc = require_buffers({c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
-    if (!kHfBoxDiscrete<PP> && fused_limit_exceeded(d)) {  // (the discrete kernels index the projection in 64 bits)
+    if (!kFusedDiscrete<PP> && fused_limit_exceeded(d)) {  // (the discrete kernels index the projection in 64 bits)
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
@@ -1179,7 +1182,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     PP p{};
     if ((rc = fill_kernarg<TV>(p, c, d)) != 0) return rc;
     p.loc = c.proj;
-    if constexpr (kHfBoxDiscrete<PP>)
+    if constexpr (kFusedDiscrete<PP>)
         return launched(dispatch_hfbox_discrete<T, 0, TV, TS>(p, rows_vec_ok(p, c.out), stream), "fused discrete forward");
     else
         return launched(dispatch_gather<T, 2, TV, TS>(p, rows_vec_ok(p, c.out), stream), "fused forward");
@@ -1511,6 +1514,7 @@ inline MaskedParams &value_pass_params(LevelRefMaskedParams &p) { return p; }  /
 inline RaggedParams &value_pass_params(HfBoxParams &p) { return p; }
 // ... and in front of discrete sampling the DISCRETE pipeline (cell_of's one-corner records)
 inline DiscreteParams &value_pass_params(HfBoxDiscreteParams &p) { return p; }
+inline DiscreteParams &value_pass_params(ModuleDiscreteParams &p) { return p; }
 
 // PP = RaggedParams (msda_bwd_fused_ragged_<dtype>): per-level point counts, proj / grad_proj [B, Q, H, S, 3]; the
 // derived points and weights go to the workspace in the ragged operator's layout and its grad_value pipeline reads them
@@ -1519,6 +1523,7 @@ inline DiscreteParams &value_pass_params(HfBoxDiscreteParams &p) { return p; }
 // the host's `level_scale` [L] and `offset_scale`
 // PP = HfBoxDiscreteParams (msda_bwd_fused_hfbox_discrete_<dtype>): that rule in front of discrete sampling — grad_proj only
 // (no partials: c.grad_ref_partial stays null), the same head of the workspace, then the DISCRETE grad_value pipeline
+// PP = ModuleDiscreteParams (msda_bwd_fused_discrete_<dtype>): the same with the module's own rule
 template <typename T, typename TV = T, typename TS = T, typename PP = Params> int run_bwd_fused(const Call &c)
 {
     const Dims d = make_dims(c);
@@ -1530,7 +1535,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     if (rc) return rc;
     const size_t ns = (size_t)(d.B * d.Q * d.H * samples(d));
     // (discrete sampling: nothing differentiable reaches the box, there are no partials)
-    const size_t nref = kHfBoxDiscrete<PP> ? 0 : (size_t)(d.B * d.Q * d.H) * (kLevelRef<PP> ? (size_t)d.L : 1) * c.ref_dim;
+    const size_t nref = kFusedDiscrete<PP> ? 0 : (size_t)(d.B * d.Q * d.H) * (kLevelRef<PP> ? (size_t)d.L : 1) * c.ref_dim;
     // (a buffer of no elements may be null: PyTorch's empty tensors are — a call with Q = 0 has nothing to produce there)
     if ((ns && c.grad_proj == nullptr) || (nref && c.grad_ref_partial == nullptr)) {
         set_error("the fused backward always produces grad_proj and the grad_reference_points partials");
@@ -1540,7 +1545,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         return zero_outputs({{grad_value, (size_t)(d.B * d.I * d.H * d.D) * sizeof(TV)}, {c.grad_proj, ns * 3 * sizeof(TS)},
                              {c.grad_ref_partial, nref * sizeof(T)}}, stream);
     if ((rc = require_buffers({c.grad_out, c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
-    if (!kHfBoxDiscrete<PP> && fused_limit_exceeded(d)) {
+    if (!kFusedDiscrete<PP> && fused_limit_exceeded(d)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
@@ -1570,7 +1575,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         p.mat_loc = ws;
         p.mat_attn = ws + ns * 2 * sizeof(MT);
     }
-    if constexpr (kHfBoxDiscrete<PP>) {
+    if constexpr (kFusedDiscrete<PP>) {
         // this family refuses a grad_value call it cannot finish BEFORE its first kernel (run_value would say the same
         // behind it)
         if (want_value && (rc = value_route_status<MT, TV>(p, d, ws + mat, workspace_bytes - (int64_t)mat)) != 0) return rc;
@@ -1695,6 +1700,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TV, T)                                                \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)                                                           \
     MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TV, T)                                                  \
+    MSDA_DEFINE_FUSED_MODULE_DISCRETE_ENTRY_POINTS(SUF, T, TV, T)                                                 \
     MSDA_DEFINE_MODULE_MASK_ENTRY_POINTS(SUF, T, TV, T)
 
 // the module's kernels with a separate 16-bit STORAGE type TS for value, projection, out and their gradients next to
@@ -1724,6 +1730,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TS, TS)                                               \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)                                                          \
     MSDA_DEFINE_FUSED_HFBOX_DISCRETE_ENTRY_POINTS(SUF, T, TS, TS)                                                 \
+    MSDA_DEFINE_FUSED_MODULE_DISCRETE_ENTRY_POINTS(SUF, T, TS, TS)                                                \
     MSDA_DEFINE_MODULE_MASK_ENTRY_POINTS(SUF, T, TS, TS)
 
 // the module's fused kernels with per-level point counts: msda_{fwd,bwd}_fused_ragged_<suffix> (T arithmetic and reference
@@ -1834,6 +1841,34 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         c.grad_value = grad_value; c.grad_proj = grad_proj; c.ref_dim = ref_dim;                                 \
         MSDA_TAKE_SIZES MSDA_TAKE_WORKSPACE MSDA_TAKE_COUNTS MSDA_TAKE_BOX_RULE                                  \
         return msda::run_bwd_fused<T, TV, TS, msda::HfBoxDiscreteParams>(c);                                     \
+    }
+
+// the reference module's rule in front of DISCRETE sampling (MultiscaleDeformableAttention(sampling_mode="discrete")):
+// msda_{fwd,bwd}_fused_discrete_<suffix>, the hfbox-discrete pair's lists with `int ref_dim` (2 or 4) in place of
+// `level_scale, offset_scale`
+#define MSDA_DEFINE_FUSED_MODULE_DISCRETE_ENTRY_POINTS(SUF, T, TV, TS)                                            \
+    extern "C" int msda_fwd_fused_discrete_##SUF(const void *value, const int64_t *shapes, const void *proj,     \
+                                                 const void *ref, void *out, int64_t B, int64_t I, int64_t H,     \
+                                                 int64_t D, int64_t Q, int64_t L, const int32_t *points_per_level, \
+                                                 int ref_dim, int64_t value_row_stride, void *stream)             \
+    {                                                                                                            \
+        msda::Call c; c.value = value; c.shapes = shapes; c.proj = proj; c.ref = ref; c.out = out;               \
+        c.ref_dim = ref_dim; MSDA_TAKE_SIZES MSDA_TAKE_COUNTS                                                    \
+        if (const int rc = msda::check_ref_dim(ref_dim)) return rc;                                              \
+        return msda::run_fwd_fused<T, TV, TS, msda::ModuleDiscreteParams>(c);                                    \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_discrete_##SUF(const void *grad_out, const void *value, const int64_t *shapes, \
+                                                 const void *proj, const void *ref, void *grad_value,             \
+                                                 void *grad_proj, int64_t B, int64_t I, int64_t H, int64_t D,     \
+                                                 int64_t Q, int64_t L, const int32_t *points_per_level,           \
+                                                 int ref_dim, int64_t max_level_cells, int64_t value_row_stride,  \
+                                                 void *workspace, int64_t workspace_bytes, void *stream)          \
+    {                                                                                                            \
+        msda::Call c; c.grad_out = grad_out; c.value = value; c.shapes = shapes; c.proj = proj; c.ref = ref;     \
+        c.grad_value = grad_value; c.grad_proj = grad_proj; c.ref_dim = ref_dim;                                 \
+        MSDA_TAKE_SIZES MSDA_TAKE_WORKSPACE MSDA_TAKE_COUNTS                                                     \
+        if (const int rc = msda::check_ref_dim(ref_dim)) return rc;                                              \
+        return msda::run_bwd_fused<T, TV, TS, msda::ModuleDiscreteParams>(c);                                    \
     }
 
 // the value-mask twins: msda_{fwd,bwd}_masked_<suffix> and msda_{fwd,bwd}_fused_levelref_masked_<suffix> — the twins'

@@ -330,6 +330,188 @@ def fused_hf_box_discrete_core(img, img_shapes, proj, reference_points, points_p
     return _hf_box_discrete_composition(img, img_shapes, proj, reference_points, counts, offset_scale, level_shapes)
 
 
+# ------------------------------------------------------------------------------------------
+# the reference module's own rule in front of discrete sampling (MultiscaleDeformableAttention(sampling_mode="discrete")):
+# functional.fused_module_core(..., sampling_mode="discrete") on msda_*_fused_discrete_<suffix>
+# ------------------------------------------------------------------------------------------
+def module_discrete_hip_fwd_fused(img, img_shapes, proj, reference_points, counts):
+    """Forward with the softmax, the module's point rule (:func:`msda_triton_amd.ragged.ragged_module_sampling_inputs`) and
+    the pixel choice done in the kernel (``msda_fwd_fused_discrete_<suffix>``; ``proj`` ``[B, Q, H, S, 3]``,
+    ``reference_points`` ``[B, Q, 2 | 4]``).  None when the library declines (more than 8 levels) or predates these entry
+    points: the caller then composes the prologue around the discrete operator."""
+    if not _lib.has_module_discrete() or len(counts) > FUSED_BOX_MAX_LEVELS:  # (declined without a call)
+        return None
+    B, I, H, D = img.shape
+    B2, Q, H2, S, _ = proj.shape
+    ref_dim = reference_points.shape[-1]
+    if (B2, H2) != (B, H) or tuple(reference_points.shape) != (B, Q, ref_dim) or ref_dim not in (2, 4):
+        raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
+                         f"reference_points {tuple(reference_points.shape)}")
+    F._check_devices(img, img_shapes, proj, reference_points)
+    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    shapes = F._shapes_i64(img_shapes)
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    fn = getattr(_lib.load(), f"msda_fwd_fused_discrete_{suf}")
+
+    def call():
+        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+                  B, I, H, D, Q, len(counts), _counts_array(counts), ref_dim, vrow, F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_fwd_fused_discrete", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_fwd_fused_discrete_{suf}")
+    return out
+
+
+def module_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, counts, need_img: bool = True,
+                                  level_cells: int = 0, parked_points: bool = False):
+    """Backward of the discrete module core (``msda_bwd_fused_discrete_<suffix>``): ``(img_grad | None, proj_grad)`` — the
+    offset slots of ``proj_grad`` are stored zeros and the reference points have no gradient —, or None when the library
+    declines (nothing was launched).  ``parked_points``: as :func:`hf_box_discrete_hip_bwd_fused`."""
+    if not _lib.has_module_discrete() or len(counts) > FUSED_BOX_MAX_LEVELS:  # (declined without a call)
+        return None
+    B, I, H, D = img.shape
+    _, Q, _, S, _ = proj.shape
+    ref_dim = reference_points.shape[-1]
+    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
+    cdt = proj.dtype
+    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
+    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and reference points fp32)
+    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
+    out_grad = out_grad.contiguous()
+    if out_grad.dtype != cdt:
+        out_grad = out_grad.to(cdt)
+    shapes = F._shapes_i64(img_shapes)
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
+    lib = _lib.load()
+    fn = getattr(lib, f"msda_bwd_fused_discrete_{suf}")
+    arr = _counts_array(counts)
+    ws, ws_bytes = None, 0
+    level_cells = int(level_cells)
+    if need_img:  # (a frozen value pyramid needs no workspace at all)
+        ws_bytes = int(lib.msda_bwd_fused_discrete_workspace_bytes(
+            B, I, H, D, Q, len(counts), arr, 4 if storage else proj.element_size(), img.element_size(), level_cells, 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
+
+    def call():
+        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), B, I, H, D, Q, len(counts), arr, ref_dim,
+                  level_cells, vrow, ws.data_ptr() if ws is not None else None, ws_bytes, F._stream_ptr(img.device))
+
+    with F._OnDevice(img.device):
+        timer = F.KernelTimer.active
+        rc = timer.launch("msda_bwd_fused_discrete", img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"msda_bwd_fused_discrete_{suf}")
+    res = (g_img, g_proj)
+    if parked_points and ws is not None:
+        pdt = torch.float32 if reference_points.element_size() == 2 else reference_points.dtype
+        ns = B * Q * H * S
+        res += (ws[:ns * 2 * pdt.itemsize].view(pdt).view(B, Q, H, S, 2).clone(),
+                ws[ns * 2 * pdt.itemsize:ns * 3 * pdt.itemsize].view(pdt).view(B, Q, H, S).clone())
+    return res
+
+
+def _module_discrete_composition(img, img_shapes, proj, reference_points, counts, level_shapes):
+    """The module's prologue as PyTorch ops around the discrete operator (host tensors, traced calls, ``fuse_discrete=False``,
+    whatever the fused kernels do not take).  16-bit value / projection next to fp32 reference points: the prologue in fp32,
+    the mixed-storage operator, the result back in the projection's dtype."""
+    from .ragged import ragged_module_sampling_inputs
+    if img.device.type == "cuda" and F.fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype):
+        pts, att = ragged_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points, counts)
+        return discrete_multiscale_deformable_attention(img, img_shapes, pts, att, "border", False, counts,
+                                                        level_shapes).to(proj.dtype)
+    pts, att = ragged_module_sampling_inputs(proj, img_shapes, reference_points, counts)
+    return discrete_multiscale_deformable_attention(img, img_shapes, pts, att, "border", False, counts, level_shapes)
+
+
+class _HipFusedModuleDiscreteFunction(Function):
+    """The discrete module core on ``msda_*_fused_discrete_<dtype>`` (autocast: in fp32; the storage suffixes).  When the
+    library declines, the prologue runs in PyTorch around the discrete operator's kernels."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, img, img_shapes, proj, reference_points, counts, level_cells=0):
+        from .ragged import ragged_module_sampling_inputs
+        ctx.level_cells, ctx.counts = int(level_cells), counts
+        out = module_discrete_hip_fwd_fused(img, img_shapes, proj, reference_points, counts)
+        ctx.fused = out is not None  # the backward has the same limits: do not ask twice
+        if out is None:
+            pts, att = ragged_module_sampling_inputs(proj.to(reference_points.dtype), img_shapes, reference_points, counts)
+            out = discrete_hip_fwd(img, img_shapes, pts, att, counts).to(proj.dtype)
+        ctx.save_for_backward(img, img_shapes, proj, reference_points)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, out_grad):
+        from .ragged import ragged_module_sampling_inputs
+        img, img_shapes, proj, reference_points = ctx.saved_tensors
+        need_img, _, need_proj = ctx.needs_input_grad[:3]
+        counts = ctx.counts
+        if ctx.fused and need_proj:
+            res = module_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, counts, need_img,
+                                                level_cells=ctx.level_cells)
+            if res is not None:
+                return res[0], None, res[1], None, None, None
+        with torch.enable_grad():
+            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
+            pts, att = ragged_module_sampling_inputs(proj_, img_shapes, reference_points.detach(), counts)
+        g_img, g_att = discrete_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(), counts,
+                                        (need_img, need_proj), ctx.level_cells)
+        g_proj = None
+        if need_proj:
+            g_proj = torch.autograd.grad([att], [proj_], [g_att])[0].to(proj.dtype)
+        return g_img, None, g_proj, None, None, None  # (the reference points: no gradient in this mode)
+
+
+def fuse_discrete_default(img: torch.Tensor) -> bool:
+    """``fuse_discrete=None``: the kernels for the storage dtypes where they were measured faster than the composition in
+    every repeat (``msda_triton_amd.module.DISCRETE_IN_KERNELS_DTYPES``), the composition elsewhere."""
+    from . import module
+    return bool(module.DISCRETE_IN_KERNELS) and img.dtype in module.DISCRETE_IN_KERNELS_DTYPES
+
+
+def fused_module_discrete_core(img, img_shapes, proj, reference_points, points_per_level=None, level_shapes=None,
+                               fuse_discrete=None) -> torch.Tensor:
+    """:func:`msda_triton_amd.functional.fused_module_core` with ``sampling_mode="discrete"`` (masks already composed by
+    the caller).  ``proj`` is ``[B, Q, H, L, P, 3]``, or ``[B, Q, H, S, 3]`` with ``points_per_level`` — the kernels take the
+    per-level-count layout, a uniform count is the same call with equal counts.  Host tensors, traced calls,
+    ``fuse_discrete=False`` (``None``: :func:`fuse_discrete_default`), a library without the symbols, more than 8 levels and
+    unsupported dtype combinations compose the prologue around the discrete operator."""
+    from .ragged import check_proj_points_per_level
+    if points_per_level is None:
+        if proj.dim() != 6 or proj.shape[-1] != 3:
+            raise ValueError(f"expected proj [B,N,H,L,P,3] = (x offset, y offset, logit) per sample; got {tuple(proj.shape)}")
+        B, Q, H, L, P, _ = proj.shape
+        points_per_level = [P] * L
+        proj = proj.reshape(B, Q, H, L * P, 3)
+    counts = check_proj_points_per_level(img_shapes, proj, reference_points, points_per_level)
+    on_gpu = img.device.type == "cuda"
+    if on_gpu and img_shapes.device != img.device:
+        img_shapes = img_shapes.to(img.device)  # (a handful of integers: follow `img`, as the other cores do)
+    floating = img.is_floating_point() and proj.is_floating_point() and reference_points.is_floating_point()
+    if fuse_discrete is None:
+        fuse_discrete = fuse_discrete_default(img)
+    if fuse_discrete and on_gpu and floating and not torch.compiler.is_compiling() and _lib.has_module_discrete() \
+            and len(counts) <= FUSED_BOX_MAX_LEVELS:
+        F._check_devices(img, proj, reference_points)
+        same = F.dtypes_supported(img.dtype, proj.dtype) and reference_points.dtype == proj.dtype
+        if F._autocast_on() or F.fused_storage_dtypes(img.dtype, proj.dtype, reference_points.dtype) or same:
+            level_cells = F.level_cells_of(level_shapes, len(counts), img.shape[1])
+            if img.requires_grad and torch.is_grad_enabled():
+                check_backward_supported(img, proj, counts)
+            return _HipFusedModuleDiscreteFunction.apply(img, img_shapes, proj, reference_points, counts, level_cells)
+    return _module_discrete_composition(img, img_shapes, proj, reference_points, counts, level_shapes)
+
+
 def discrete_multiscale_deformable_attention(img, img_shapes, sampling_points, attention_weights, padding_mode,
                                              align_corners, points_per_level: Sequence[int] = None,
                                              level_shapes=None) -> torch.Tensor:

@@ -905,7 +905,8 @@ class _HipFusedModuleCoreFunction(Function):
 
 
 def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners, level_shapes=None,
-                      points_per_level=None, value_mask=None, query_mask=None, mask_in_kernels: bool = True) -> torch.Tensor:
+                      points_per_level=None, value_mask=None, query_mask=None, mask_in_kernels: bool = True,
+                      sampling_mode: str = "bilinear", fuse_discrete: Optional[bool] = None) -> torch.Tensor:
     """``multiscale_deformable_attention(img, img_shapes, *module_sampling_inputs(proj, ...))`` — on GPU tensors
     with the prologue fused into the forward kernel; on host tensors exactly that composition.  ``level_shapes``: the
     level sizes as host numbers, optional (:func:`level_cells_of`).  ``points_per_level``: a point count per level; then
@@ -921,7 +922,29 @@ def fused_module_core(img, img_shapes, proj, reference_points, padding_mode, ali
     declines (``MSDA_ERR_UNSUPPORTED``) compose :func:`apply_value_mask` / :func:`apply_query_mask` with the unmasked route.
     A BACKWARD the library declines after its forward ran masked — the grad_value pipeline's own limits: 2^22 pixels per
     plane and more, option "strict" with the plane-major place pass — raises ``MSDALibraryError`` with the library's
-    message; ``mask_in_kernels=False`` serves such a call."""
+    message; ``mask_in_kernels=False`` serves such a call.
+
+    ``sampling_mode="discrete"``: every sample reads the one pixel :mod:`msda_triton_amd.discrete` describes
+    (``padding_mode`` / ``align_corners`` must be ``"border"`` / ``False``); the reference points and the offset columns of
+    ``proj`` get no gradient.  GPU tensors run ``msda_*_fused_discrete_<dtype>`` — softmax, point rule and pixel choice in
+    the kernels, at most 8 levels — through a Python ``Function``; host tensors, traced calls, more levels, a library without
+    the symbols and a declined forward compose ``module_sampling_inputs`` / ``ragged_module_sampling_inputs`` with the
+    discrete operator.  ``fuse_discrete``: ``True`` the kernels whenever they take the call, ``False`` the composition,
+    ``None`` the measured per-dtype default (``msda_triton_amd.module.DISCRETE_IN_KERNELS_DTYPES``).  Masks in this mode
+    are always composed (``apply_value_mask`` / ``apply_query_mask`` around the route)."""
+    if sampling_mode != "bilinear":
+        from . import discrete
+        if sampling_mode not in discrete.SAMPLING_MODES:
+            raise ValueError(f"`sampling_mode` should be one of {list(discrete.SAMPLING_MODES)}, but got {sampling_mode!r}.")
+        discrete.check_discrete_mode(padding_mode, align_corners)
+        if query_mask is not None:
+            out = fused_module_core(img, img_shapes, apply_query_mask(proj, query_mask, 0.0),
+                                    apply_query_mask(reference_points, query_mask, 0.5), padding_mode, align_corners,
+                                    level_shapes, points_per_level, value_mask, None, mask_in_kernels, sampling_mode,
+                                    fuse_discrete)
+            return apply_query_mask(out, query_mask, 0.0)
+        return discrete.fused_module_discrete_core(apply_value_mask(img, value_mask), img_shapes, proj, reference_points,
+                                                   points_per_level, level_shapes, fuse_discrete)
     if points_per_level is not None and (value_mask is not None or query_mask is not None):
         from .ragged import fused_ragged_module_core
         return fused_ragged_module_core(img, img_shapes, proj, reference_points, padding_mode, align_corners,

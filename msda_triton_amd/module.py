@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from ._linear import projection
+from .discrete import SAMPLING_MODES, check_discrete_mode
 from .functional import fused_module_core, module_sampling_inputs
 from .ragged import ragged_module_sampling_inputs
 
@@ -23,6 +24,14 @@ from .ragged import ragged_module_sampling_inputs
 # forward plus backward (tools/module_mask_bench.py).  False: every call composes (A/B runs, and the parent's behaviour).
 MASK_IN_KERNELS = True
 MASK_IN_KERNELS_DTYPES = (torch.float32, torch.bfloat16)
+
+
+# sampling_mode="discrete": softmax, point rule and pixel choice inside msda_*_fused_discrete_<dtype> instead of the
+# prologue in PyTorch around the discrete operator.  The same rule per storage dtype of the value pyramid (DESIGN.md 21,
+# tools/module_discrete_bench.py, profiles/r16_module_discrete_bench.json): fp32 and bf16 were measured and are ahead in
+# every repeat, forward plus backward; fp16 and fp64 were not measured and compose.  False: every call composes.
+DISCRETE_IN_KERNELS = True
+DISCRETE_IN_KERNELS_DTYPES = (torch.float32, torch.bfloat16)
 
 
 def mask_in_kernels(value: torch.Tensor) -> bool:
@@ -55,15 +64,27 @@ class MultiscaleDeformableAttention(nn.Module):
             ``torch.autocast`` to that dtype the projection GEMM writes it directly; otherwise its output is cast
             once.  ``None`` (default): the reference's behaviour — everything in the parameters' dtype, fp32 under
             autocast.
+        sampling_mode: (not in the reference) ``"bilinear"`` (default) or ``"discrete"``: every sample reads its ONE
+            nearest pixel (``msda_triton_amd.discrete``; what D-FINE / DEIMv2 / RT-DETRv2 decoders are deployed with).
+            Needs ``padding_mode="border"``, ``align_corners=False``.  Same parameters and ``state_dict``; the sampling
+            offsets and the reference points get no gradient in this mode.
 
     Raises:
-        ValueError: if ``hidden_dim`` is not divisible by ``num_heads`` (frontend.py:211-212).
+        ValueError: if ``hidden_dim`` is not divisible by ``num_heads`` (frontend.py:211-212); for an unknown
+            ``sampling_mode``, or ``"discrete"`` with another padding mode or ``align_corners``.
     """
 
     def __init__(self, emb_dim: int, hidden_dim: int, num_levels: int, num_heads: int,
                  num_points: Union[int, Sequence[int]], padding_mode: Literal["border", "zeros"], align_corners: bool,
-                 value_dtype: Optional[torch.dtype] = None):
+                 value_dtype: Optional[torch.dtype] = None, sampling_mode: Literal["bilinear", "discrete"] = "bilinear"):
         super().__init__()
+        if sampling_mode not in SAMPLING_MODES:
+            raise ValueError(f"`sampling_mode` should be one of {list(SAMPLING_MODES)}, but got {sampling_mode!r}.")
+        if sampling_mode == "discrete":
+            check_discrete_mode(padding_mode, align_corners)
+        self.sampling_mode = sampling_mode
+        # `fuse_discrete` of the core: None = the measured per-dtype default above; True / False for A/B runs
+        self.fuse_discrete = None
         if hidden_dim % num_heads != 0:
             raise ValueError(
                 f"Hidden dimension ({hidden_dim=}) should be divisible by number of heads ({num_heads=}).")
@@ -151,7 +172,8 @@ class MultiscaleDeformableAttention(nn.Module):
             self.value_dtype in (None, proj.dtype) and value.dtype == proj.dtype
         if not storage16 and self.value_dtype is not None and value.device.type == "cuda":
             value = value.to(self.value_dtype)  # nothing to do when autocast already produced this dtype
-        masks = dict(value_mask=value_mask, query_mask=query_mask, mask_in_kernels=mask_in_kernels(value))
+        masks = dict(value_mask=value_mask, query_mask=query_mask, mask_in_kernels=mask_in_kernels(value),
+                     sampling_mode=self.sampling_mode, fuse_discrete=self.fuse_discrete)
         if storage16:
             # 16-bit projections (autocast's GEMMs, or 16-bit parameters) with fp32 reference points: the kernels read
             # and write the 16-bit tensors as they are and compute in fp32 — what the reference's core does under
