@@ -625,6 +625,44 @@ MSDA_MODULE_DISCRETE_QUERY(workspace_bytes)
 #undef MSDA_MODULE_DISCRETE_QUERY
 
 /*
+ * The per-level-reference pair on SPLIT projections (functional.fused_hf_module_core_split; the Hugging Face adapter's
+ * route for LoRA-wrapped, hooked or otherwise non-plain projection layers, and the tensors every module in the
+ * ecosystem has) — ADDITIONS WITHIN ABI 12, probed by symbol: msda_fwd_fused_levelref_split_<suffix> /
+ * msda_bwd_fused_levelref_split_<suffix> for the same eight suffixes.  The argument lists are
+ * msda_fwd_fused_levelref_<suffix>'s / msda_bwd_fused_levelref_<suffix>'s with
+ *
+ *   offsets, logits            [B, Q, H, L, P, 2] (x offset, y offset) and [B, Q, H, L, P] in place of `proj` — what the
+ *                              modules' two Linear layers produce, byte for byte the `loc` / `attn` layouts of msda_fwd_<dtype>
+ *   grad_offsets, grad_logits  shaped alike, in place of `grad_proj`; every element of both is written
+ *
+ * Phase 0 reads (ox, oy) at 2 * s, 2 * s + 1 of `offsets` and the logit at s of `logits`; nothing behind those loads
+ * differs from the interleaved pair — the arithmetic and its order, the parked points and weights, grad_value's pipeline,
+ * the variants with LDS-served levels — so the results are BIT FOR BIT that pair's on the same numbers.  Every guard is that
+ * pair's, in its order (sizes — the interleaved pair's 3 * Q * H * L * P bound included —, alignment to the element size,
+ * ref_dim, L * P <= msda_fused_lp_limit(D, elem_size) else MSDA_ERR_UNSUPPORTED and nothing is launched); a NULL `offsets`
+ * or `logits` (backward: `grad_offsets`, `grad_logits` too) is MSDA_ERR_BAD_ARG.  grad_ref_partial, the workspace,
+ * MSDA_WS_PASSES(n), max_level_cells and value_row_stride are the pair's: msda_bwd_fused_workspace_bytes answers for these
+ * calls too.  msda_last_launch_info reports the pair's variants; option "profile" names the launches
+ * msda_fwd_fused_levelref_split / msda_bwd_fused_levelref_split.  No padding masks (the caller composes them).
+ */
+#define MSDA_LEVELREF_SPLIT(SUF)                                                                       \
+    MSDA_API int msda_fwd_fused_levelref_split_##SUF(const void *value, const int64_t *shapes,      \
+                       const void *offsets, const void *logits, const void *ref, void *out,         \
+                       int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L, int64_t P, \
+                       int ref_dim, int padding_mode, int align_corners, int64_t value_row_stride,  \
+                       void *stream);                                                               \
+    MSDA_API int msda_bwd_fused_levelref_split_##SUF(const void *grad_out, const void *value,       \
+                       const int64_t *shapes, const void *offsets, const void *logits,              \
+                       const void *ref, void *grad_value, void *grad_offsets, void *grad_logits,    \
+                       void *grad_ref_partial, int64_t B, int64_t I, int64_t H, int64_t D,          \
+                       int64_t Q, int64_t L, int64_t P, int ref_dim, int padding_mode,              \
+                       int align_corners, int64_t max_level_cells, int64_t value_row_stride,        \
+                       void *workspace, int64_t workspace_bytes, void *stream);
+MSDA_LEVELREF_SPLIT(f32) MSDA_LEVELREF_SPLIT(f16) MSDA_LEVELREF_SPLIT(bf16) MSDA_LEVELREF_SPLIT(f64)
+MSDA_LEVELREF_SPLIT(f32_vbf16) MSDA_LEVELREF_SPLIT(f32_vf16) MSDA_LEVELREF_SPLIT(f32_sbf16) MSDA_LEVELREF_SPLIT(f32_sf16)
+#undef MSDA_LEVELREF_SPLIT
+
+/*
  * Bytes of device workspace msda_bwd_<dtype> wants for these sizes.  elem_size: of everything but `value`;
  * value_elem_size: of `value` / `grad_value` (0: the same — 2 next to elem_size 4 for the mixed-storage entry points);
  * max_level_cells: as for the call (0: unknown).

@@ -74,6 +74,11 @@ MODULE_DISCRETE_SYMBOLS = tuple(
     + ["msda_bwd_fused_discrete_workspace_bytes"]
 )
 
+# ... and the per-level-reference pair on split projections (has_levelref_split): `offsets`, `logits` in place of `proj`
+LEVELREF_SPLIT_SYMBOLS = tuple(
+    f"msda_{d}_fused_levelref_split_{s}" for d in ("fwd", "bwd") for s in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES
+)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -281,6 +286,16 @@ def load():
                 grm = getattr(lib, f"msda_bwd_fused_ragged_masked_{suf}")
                 grm.restype = ci
                 grm.argtypes = [vp] * 10 + [i64] * 6 + [vp, ci, ci, ci, i64, i64, vp, i64, vp]
+        # the per-level-reference pair on split projections: additions within ABI 12 (has_levelref_split); that pair's
+        # lists with (offsets, logits) in place of `proj` and (grad_offsets, grad_logits) in place of `grad_proj`
+        if hasattr(lib, "msda_bwd_fused_levelref_split_f32"):
+            for suf in DTYPE_SUFFIXES + FUSED_STORAGE_SUFFIXES:
+                fls = getattr(lib, f"msda_fwd_fused_levelref_split_{suf}")
+                fls.restype = ci
+                fls.argtypes = [vp] * 6 + [i64] * 7 + [ci, ci, ci, i64, vp]
+                gls = getattr(lib, f"msda_bwd_fused_levelref_split_{suf}")
+                gls.restype = ci
+                gls.argtypes = [vp] * 10 + [i64] * 7 + [ci, ci, ci, i64, i64, vp, i64, vp]
         lib.msda_profile_read.restype = ci
         lib.msda_profile_read.argtypes = [ctypes.c_char_p, ci]
         lib.msda_fused_lp_limit.restype = i64
@@ -342,6 +357,13 @@ def has_module_discrete() -> bool:
     (msda_fwd_fused_discrete_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller composes the
     module's prologue around the discrete operator."""
     return hasattr(load(), "msda_bwd_fused_discrete_workspace_bytes")
+
+
+def has_levelref_split() -> bool:
+    """Does the loaded library have the per-level-reference pair on split projections
+    (msda_fwd_fused_levelref_split_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller
+    interleaves offsets and logits and takes the pair it has."""
+    return hasattr(load(), "msda_bwd_fused_levelref_split_f32")
 
 
 def has_value_mask() -> bool:

@@ -186,6 +186,16 @@ template <typename A> __device__ __forceinline__ int discrete_pixel(A x, int n)
 // nothing behind Params: the uniform and the per-level-count instantiations keep their types and their code, and the
 // three rules hang on overloads / `if constexpr (kLevelRef<PP>)`.  Uniform point count only.
 struct LevelRefParams : Params {};
+// ... and the same pair on SPLIT projections (msda_*_fused_levelref_split_<dtype>): what the two Linear layers of every
+// module in the ecosystem produce — offsets [B, Q, H, L, P, 2] and logits [B, Q, H, L, P], byte for byte the `loc` and
+// `attn` layouts of the sampling operators.  `loc` holds the offsets and `grad_loc` their gradient; the logits and their
+// gradient ride BEHIND Params (the preloaded front is unchanged).  Only phase 0's three loads and phase 3's three stores
+// hang on `if constexpr (kSplitProj<PP>)`: everything between them is the level-reference pair's, operation by operation.
+struct LevelRefSplitParams : LevelRefParams {
+    const void *logits;
+    void *grad_logits;
+};
+template <typename PP> constexpr bool kSplitProj = std::is_base_of<LevelRefSplitParams, PP>::value;
 
 // ---- value padding mask (msda_*_masked_<dtype>, msda_*_fused_levelref_masked_<dtype>) ----
 // `vmask` is [B, I] bytes, non-zero = the pixel is real; a pixel whose byte is 0 counts as a row of zeros whatever bits it
@@ -625,6 +635,12 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
     [[maybe_unused]] const TS *proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;  // FUSED: raw projection (dx, dy, logit)
     const T *attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
+    // split projections: the plane's offsets (dx, dy) and, apart from them, its logits
+    [[maybe_unused]] const TS *off2 = nullptr, *lgt1 = nullptr;
+    if constexpr (kSplitProj<PP>) {
+        off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
+        lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
+    }
     // the wave's plane-dependent values for plane pair0 + hp_ (two planes per workgroup: per slice)
     auto select_plane = [&](int hp_) {
         h = pair0 + hp_ - b * p.H;
@@ -633,6 +649,10 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
         loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
         proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;
         attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
+        if constexpr (kSplitProj<PP>) {
+            off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
+            lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
+        }
     };
     const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * ref_row_elems(p) : nullptr;
     const int HLP = p.H * p.LP;
@@ -780,8 +800,14 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                             if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
                             else l = div_small(sl, p.P, inv_P);
                             const int sidx = imul24(fq, HLP) + sl;
-                            const A ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
-                            const A lg = SR::to_acc(proj3[3 * sidx + 2]);
+                            A ox, oy, lg;
+                            if constexpr (kSplitProj<PP>) {  // (the three loads are all that differs)
+                                ox = SR::to_acc(off2[2 * sidx]), oy = SR::to_acc(off2[2 * sidx + 1]);
+                                lg = SR::to_acc(lgt1[sidx]);
+                            } else {
+                                ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
+                                lg = SR::to_acc(proj3[3 * sidx + 2]);
+                            }
                             const T *r = ref_of(p, refp, fq, l);
                             Rec4<A> w;
                             w.v[0] = lg;
@@ -1178,6 +1204,12 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
     [[maybe_unused]] const TS *proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;  // FUSED: raw projection (dx, dy, logit)
     const T *attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
+    // split projections: the plane's offsets (dx, dy) and, apart from them, its logits (as in msda_fwd_kernel)
+    [[maybe_unused]] const TS *off2 = nullptr, *lgt1 = nullptr;
+    if constexpr (kSplitProj<PP>) {
+        off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
+        lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
+    }
     auto select_plane = [&](int hp_) {  // the plane-dependent values for plane pair0 + hp_
         h = pair0 + hp_ - b * p.H;
         rs = make_rsrc(plane_base<TV>(p, b, h), plane_span<TV>(p, h));
@@ -1185,6 +1217,10 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
         loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
         proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;
         attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
+        if constexpr (kSplitProj<PP>) {
+            off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
+            lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
+        }
     };
     const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * ref_row_elems(p) : nullptr;
     A *w_aux = lds.s_aux + wave * UPW * scp * 3;  // FUSED: [slot] = a, [UPW*scp + slot] = ox, [2*UPW*scp + slot] = oy
@@ -1338,8 +1374,14 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
                         else l = div_small(sl, p.P, inv_P);
                         const int sidx = imul24(fq, HLP) + sl;
-                        A ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
-                        const A lg = SR::to_acc(proj3[3 * sidx + 2]);
+                        A ox, oy, lg;
+                        if constexpr (kSplitProj<PP>) {  // (the three loads and phase 3's three stores are all that differs)
+                            ox = SR::to_acc(off2[2 * sidx]), oy = SR::to_acc(off2[2 * sidx + 1]);
+                            lg = SR::to_acc(lgt1[sidx]);
+                        } else {
+                            ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
+                            lg = SR::to_acc(proj3[3 * sidx + 2]);
+                        }
                         const T *r = ref_of(p, refp, fq, l);
                         Rec4<A> w;
                         w.v[0] = lg;
@@ -1902,11 +1944,21 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         g0.v[0] = SR::from_acc(res.v[1] * kx);
                         g1.v[0] = SR::from_acc(res.v[2] * ky);
                         g2.v[0] = SR::from_acc(a * (res.v[0] - dot));
+                        if constexpr (kSplitProj<PP>) {  // grad_offsets [.., 2] and, apart from it, grad_logits
+                            TS *go = static_cast<TS *>(p.grad_loc) + 2 * (plane_s0 + sidx);
+                            TS *gl = static_cast<TS *>(p.grad_logits) + (plane_s0 + sidx);
+                            if (!abl_gp) {
+                                store_stream(go, g0);
+                                store_stream(go + 1, g1);
+                                store_stream(gl, g2);
+                            }
+                        } else {
                         TS *gp = static_cast<TS *>(p.grad_loc) + 3 * (plane_s0 + sidx);
                         if (!abl_gp) {
                             store_stream(gp, g0);
                             store_stream(gp + 1, g1);
                             store_stream(gp + 2, g2);
+                        }
                         }
                     } else {
                         Pack<T, 1> ga;

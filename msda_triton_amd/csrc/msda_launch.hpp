@@ -377,6 +377,13 @@ template <typename T, int G, typename TV> inline LdsLevelsPlan lds_levels_plan(c
     return lds_levels_plan_rt(p, G, sizeof(typename Traits<T>::acc), sizeof(TV), aux, stage);
 }
 
+// what option "profile" calls a gather launch: the kernel's name — the split-projection pair reports its entry points' names
+template <int MODE, typename PP> constexpr const char *gather_profile_name()
+{
+    if constexpr (kSplitProj<PP>) return MODE == 2 ? "msda_fwd_fused_levelref_split" : "msda_bwd_fused_levelref_split";
+    else return MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel";
+}
+
 template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T, typename PP = Params> inline int launch_gather_lds(PP &p, const LdsLevelsPlan &pl, hipStream_t stream)
 {
     // MODE as in launch_gather: the forward and sample-gradient kernels, plain (0, 1) and with the module prologue (2, 3)
@@ -407,7 +414,7 @@ template <typename T, int VEC, int G, int MODE, typename TV, typename TS = T, ty
         note_instance(11, VEC, G, p.D);
         note_trips(24, p.LP, pl.sc);
     }
-    const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
+    const ProfileScope prof(gather_profile_name<MODE, PP>(), stream);
     if constexpr (MODE == 0 || MODE == 2) {
         auto kernel = msda_fwd_kernel<T, VEC, G, MODE == 2, TV, kBlockLds, true, std::conditional_t<MODE == 2, TS, T>, PP>;
         allow_big_lds(kernel, big_lds_done);
@@ -534,7 +541,7 @@ template <typename T, int VEC, int G, int MODE, typename TV = T, typename TS = T
         note_trips(24, p.LP, p.sc);
     }
     static std::atomic<uint64_t> big_lds_done{0};  // one per template instantiation
-    const ProfileScope prof(MODE == 0 || MODE == 2 ? "msda_fwd_kernel" : "msda_bwd_sample_kernel", stream);
+    const ProfileScope prof(gather_profile_name<MODE, PP>(), stream);
     if constexpr (MODE == 3) {
         auto kernel = msda_bwd_sample_kernel<T, VEC, G, true, TV, kBlock, false, TS, PP>;
         allow_big_lds(kernel, big_lds_done);
@@ -929,6 +936,14 @@ inline void fill_box_scales(Params &, const float *, double, int64_t) {}
 // pointer when the grad_value pipeline runs once per group of batch elements
 // ... and the query padding mask behind it (msda_*_qmasked_<dtype>): [B, Q] bytes, NULL from the _masked_ entry points
 // (one definition for every kernarg that carries the pair — kValueMask — and a no-op for the others)
+// the logits of a split projection and their gradient, behind the kernarg (a no-op for every other kernarg)
+template <typename PP> inline void set_split_logits(PP &p, const void *logits, void *grad_logits)
+{
+    if constexpr (kSplitProj<PP>) {
+        p.logits = logits;
+        p.grad_logits = grad_logits;
+    }
+}
 template <typename PP> inline void set_value_mask(PP &p, const uint8_t *vmask, const uint8_t *qmask)
 {
     if constexpr (kValueMask<PP>) {
@@ -1062,6 +1077,10 @@ struct Call {
     const void *loc = nullptr, *attn = nullptr, *proj = nullptr, *ref = nullptr;
     void *out = nullptr, *grad_value = nullptr, *grad_loc = nullptr, *grad_attn = nullptr, *grad_proj = nullptr,
          *grad_ref_partial = nullptr;
+    // split projections (msda_*_fused_levelref_split_<dtype>): `proj` / `grad_proj` then hold the offsets [.., 2] and their
+    // gradient, and the logits [..] and theirs sit here
+    const void *logits = nullptr;
+    void *grad_logits = nullptr;
     int64_t B = 0, I = 0, H = 0, D = 0, Q = 0, L = 0;
     int64_t P = 0, S = 0;  // per-level counts: their maximum and sum (take_counts); else the uniform P and 0
     const int32_t *points_per_level = nullptr;  // host, L counts
@@ -1109,6 +1128,7 @@ template <typename TV, typename PP> inline int fill_kernarg(PP &p, const Call &c
     fill_level_starts(p, c.points_per_level, d.L);
     fill_box_scales(p, c.level_scale, c.offset_scale, d.L);
     set_value_mask(p, c.value_mask, c.query_mask);
+    set_split_logits(p, c.logits, c.grad_logits);
     p.ref = c.ref;
     p.ref_dim = c.ref_dim;
     p.vrow_bytes = (int)(d.D * (int64_t)sizeof(TV));
@@ -1173,12 +1193,14 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     if (rc) return rc;
     if (samples(d) == 0 || d.I == 0) return zero_outputs({{c.out, out_bytes}}, stream);
     if ((rc = require_buffers({c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
+    if (kSplitProj<PP> && (rc = require_buffers({c.logits})) != 0) return rc;
     if (!kFusedDiscrete<PP> && fused_limit_exceeded(d)) {  // (the discrete kernels index the projection in 64 bits)
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
     }
     if ((rc = check_aligned({{c.value, sizeof(TV)}, {c.out, sizeof(TS)}, {c.proj, sizeof(TS)}, {c.ref, sizeof(T)}, {c.shapes, 8}})) != 0)
         return rc;
+    if (kSplitProj<PP> && (rc = check_aligned({{c.logits, sizeof(TS)}})) != 0) return rc;
     PP p{};
     if ((rc = fill_kernarg<TV>(p, c, d)) != 0) return rc;
     p.loc = c.proj;
@@ -1509,6 +1531,7 @@ inline size_t fused_mat_bytes(int64_t B, int64_t H, int64_t Q, int64_t S, size_t
 // only: grad_value is the UNIFORM pipeline on the parked points (no kernels of its own).
 template <typename PP> inline PP &value_pass_params(PP &p) { return p; }
 inline Params &value_pass_params(LevelRefParams &p) { return p; }
+inline Params &value_pass_params(LevelRefSplitParams &p) { return p; }  // (split projections: the parked points are the pair's)
 inline MaskedParams &value_pass_params(LevelRefMaskedParams &p) { return p; }  // (... the plain value-mask pipeline)
 // ... and so does Hugging Face's box rule: grad_value is the PER-LEVEL-COUNT pipeline on the parked points.
 inline RaggedParams &value_pass_params(HfBoxParams &p) { return p; }
@@ -1537,14 +1560,15 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     // (discrete sampling: nothing differentiable reaches the box, there are no partials)
     const size_t nref = kFusedDiscrete<PP> ? 0 : (size_t)(d.B * d.Q * d.H) * (kLevelRef<PP> ? (size_t)d.L : 1) * c.ref_dim;
     // (a buffer of no elements may be null: PyTorch's empty tensors are — a call with Q = 0 has nothing to produce there)
-    if ((ns && c.grad_proj == nullptr) || (nref && c.grad_ref_partial == nullptr)) {
+    if ((ns && c.grad_proj == nullptr) || (nref && c.grad_ref_partial == nullptr) || (kSplitProj<PP> && ns && c.grad_logits == nullptr)) {
         set_error("the fused backward always produces grad_proj and the grad_reference_points partials");
         return MSDA_ERR_BAD_ARG;
     }
-    if (nothing_sampled(d))
-        return zero_outputs({{grad_value, (size_t)(d.B * d.I * d.H * d.D) * sizeof(TV)}, {c.grad_proj, ns * 3 * sizeof(TS)},
-                             {c.grad_ref_partial, nref * sizeof(T)}}, stream);
+    if (nothing_sampled(d))  // (split projections: grad_proj is grad_offsets [.., 2], grad_logits apart from it)
+        return zero_outputs({{grad_value, (size_t)(d.B * d.I * d.H * d.D) * sizeof(TV)}, {c.grad_proj, ns * (kSplitProj<PP> ? 2 : 3) * sizeof(TS)},
+                             {c.grad_logits, kSplitProj<PP> ? ns * sizeof(TS) : 0}, {c.grad_ref_partial, nref * sizeof(T)}}, stream);
     if ((rc = require_buffers({c.grad_out, c.value, c.shapes, c.proj, c.ref})) != 0) return rc;
+    if (kSplitProj<PP> && (rc = require_buffers({c.logits})) != 0) return rc;
     if (!kFusedDiscrete<PP> && fused_limit_exceeded(d)) {
         set_error("projection too large for 32-bit sample offsets");
         return MSDA_ERR_TOO_LARGE;
@@ -1552,6 +1576,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     if ((rc = check_aligned({{c.value, sizeof(TV)}, {c.grad_out, sizeof(TS)}, {grad_value, sizeof(TV)}, {c.proj, sizeof(TS)},
                              {c.grad_proj, sizeof(TS)}, {c.ref, sizeof(T)}, {c.grad_ref_partial, sizeof(T)}, {c.shapes, 8}})) != 0)
         return rc;
+    if (kSplitProj<PP> && (rc = check_aligned({{c.logits, sizeof(TS)}, {c.grad_logits, sizeof(TS)}})) != 0) return rc;
     const bool want_value = grad_value != nullptr;
     // the derived points and weights are parked in float by the 16-bit operators too (ParkType), and their grad_value passes
     // are the float pipeline on 16-bit rows — so those calls have the float limits, as the workspace queries say
@@ -1696,6 +1721,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     MSDA_DEFINE_QMASKED_ENTRY_POINTS(SUF, T, TV)                                                                  \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TV, T)                                                          \
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TV, T)                                                        \
+    MSDA_DEFINE_FUSED_LEVELREF_SPLIT_ENTRY_POINTS(SUF, T, TV, T)                                                  \
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TV, T)                                                 \
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TV, T)                                                \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TV, T)                                                           \
@@ -1726,6 +1752,7 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     }                                                                                                            \
     MSDA_DEFINE_FUSED_RAGGED_ENTRY_POINTS(SUF, T, TS, TS)                                                         \
     MSDA_DEFINE_FUSED_LEVELREF_ENTRY_POINTS(SUF, T, TS, TS)                                                       \
+    MSDA_DEFINE_FUSED_LEVELREF_SPLIT_ENTRY_POINTS(SUF, T, TS, TS)                                                 \
     MSDA_DEFINE_FUSED_LEVELREF_MASKED_ENTRY_POINTS(SUF, T, TS, TS)                                                \
     MSDA_DEFINE_FUSED_LEVELREF_QMASKED_ENTRY_POINTS(SUF, T, TS, TS)                                               \
     MSDA_DEFINE_FUSED_HFBOX_ENTRY_POINTS(SUF, T, TS, TS)                                                          \
@@ -1781,6 +1808,37 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     {                                                                                                            \
         MSDA_TAKE_BWD_FUSED c.P = P;                                                                             \
         return msda::run_bwd_fused<T, TV, TS, msda::LevelRefParams>(c);                                          \
+    }
+
+// ... and the same pair on SPLIT projections: msda_{fwd,bwd}_fused_levelref_split_<suffix> — `offsets` [B, Q, H, L, P, 2]
+// and `logits` [B, Q, H, L, P] in place of `proj`, `grad_offsets` and `grad_logits` in place of `grad_proj`; every check,
+// in the pair's order, and the pair's workspace (msda_bwd_fused_workspace_bytes answers for it)
+#define MSDA_DEFINE_FUSED_LEVELREF_SPLIT_ENTRY_POINTS(SUF, T, TV, TS)                                             \
+    extern "C" int msda_fwd_fused_levelref_split_##SUF(const void *value, const int64_t *shapes,                 \
+                                                       const void *offsets, const void *logits, const void *ref,  \
+                                                       void *out, int64_t B, int64_t I, int64_t H, int64_t D,     \
+                                                       int64_t Q, int64_t L, int64_t P, int ref_dim,              \
+                                                       int padding_mode, int align_corners,                       \
+                                                       int64_t value_row_stride, void *stream)                    \
+    {                                                                                                            \
+        const void *const proj = offsets;                                                                        \
+        MSDA_TAKE_FWD_FUSED c.P = P; c.logits = logits;                                                          \
+        return msda::run_fwd_fused<T, TV, TS, msda::LevelRefSplitParams>(c);                                     \
+    }                                                                                                            \
+    extern "C" int msda_bwd_fused_levelref_split_##SUF(const void *grad_out, const void *value,                  \
+                                                       const int64_t *shapes, const void *offsets,                \
+                                                       const void *logits, const void *ref, void *grad_value,     \
+                                                       void *grad_offsets, void *grad_logits,                     \
+                                                       void *grad_ref_partial, int64_t B, int64_t I, int64_t H,   \
+                                                       int64_t D, int64_t Q, int64_t L, int64_t P, int ref_dim,   \
+                                                       int padding_mode, int align_corners,                       \
+                                                       int64_t max_level_cells, int64_t value_row_stride,         \
+                                                       void *workspace, int64_t workspace_bytes, void *stream)    \
+    {                                                                                                            \
+        const void *const proj = offsets;                                                                        \
+        void *const grad_proj = grad_offsets;                                                                    \
+        MSDA_TAKE_BWD_FUSED c.P = P; c.logits = logits; c.grad_logits = grad_logits;                             \
+        return msda::run_bwd_fused<T, TV, TS, msda::LevelRefSplitParams>(c);                                     \
     }
 
 // the module's fused kernels for Hugging Face's box rule with per-level point counts (D-FINE, DEIMv2, RT-DETRv2):

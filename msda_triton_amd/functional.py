@@ -1210,6 +1210,218 @@ def fused_hf_module_core(img, img_shapes, proj, reference_points, padding_mode, 
 
 
 # ------------------------------------------------------------------------------------------
+# ... on SPLIT projections: the offsets and the logits as the modules' two Linear layers produce them
+# (msda_*_fused_levelref_split_<dtype>)
+# ------------------------------------------------------------------------------------------
+def split_projection_views(sampling_offsets: torch.Tensor, attention_logits: torch.Tensor, H: int, L: int):
+    """The two projections as ``[B, Q, H, L, P, 2]`` and ``[B, Q, H, L, P]``: ``sampling_offsets`` in that shape or the
+    ``Linear``'s flat ``[B, Q, H*L*P*2]``, ``attention_logits`` as ``[B, Q, H, L, P]``, ``[B, Q, H, L*P]`` or flat.  Views
+    where the layout allows (a ``Linear``'s output always does)."""
+    if sampling_offsets.dim() == 3:
+        B, Q, flat = sampling_offsets.shape
+        if flat % (H * L * 2) != 0 or flat == 0:
+            raise ValueError(f"`sampling_offsets` [B, Q, {flat}] is not [B, Q, H*L*P*2] for H = {H}, L = {L}.")
+        sampling_offsets = sampling_offsets.reshape(B, Q, H, L, flat // (H * L * 2), 2)
+    if sampling_offsets.dim() != 6 or sampling_offsets.shape[-1] != 2 or tuple(sampling_offsets.shape[2:4]) != (H, L):
+        raise ValueError(f"`sampling_offsets` should be [B, Q, {H}, {L}, P, 2] or [B, Q, H*L*P*2], but got "
+                         f"{tuple(sampling_offsets.shape)}.")
+    want = tuple(sampling_offsets.shape[:5])
+    if attention_logits.dim() not in (3, 4, 5) or tuple(attention_logits.shape[:2]) != want[:2] or \
+            attention_logits.numel() != sampling_offsets.numel() // 2 or \
+            (attention_logits.dim() >= 4 and attention_logits.shape[2] != H):
+        raise ValueError(f"`attention_logits` should be {list(want)}, [B, Q, H, L*P] or [B, Q, H*L*P] next to "
+                         f"`sampling_offsets` {tuple(sampling_offsets.shape)}, but got {tuple(attention_logits.shape)}.")
+    return sampling_offsets, attention_logits.reshape(want)
+
+
+def stack_split_projection(sampling_offsets: torch.Tensor, attention_logits: torch.Tensor) -> torch.Tensor:
+    """``[B, Q, H, L, P, 3]`` (dx, dy, logit) from the split pair: the pass :func:`fused_hf_module_core_split` saves."""
+    return torch.cat([sampling_offsets, attention_logits[..., None]], -1)
+
+
+class _SplitCallDeclined(Exception):
+    """Raised by the forward of :class:`_HipFusedHFSplitFunction` when the library declines the call
+    (``MSDA_ERR_UNSUPPORTED``; nothing was launched): :func:`fused_hf_module_core_split` catches it and composes."""
+
+
+def msda_hip_fwd_fused_split(img, img_shapes, offsets, logits, reference_points, padding_mode,
+                             align_corners) -> Optional[torch.Tensor]:
+    """:func:`msda_hip_fwd_fused` with ``levelref=True`` on split projections (``msda_fwd_fused_levelref_split_<dtype>``):
+    ``offsets`` ``[B, Q, H, L, P, 2]``, ``logits`` ``[B, Q, H, L, P]``.  None when the library declines or lacks the symbol."""
+    B, I, H, D = img.shape
+    B2, Q, H2, L, P, two = offsets.shape
+    if (B2, H2, two) != (B, H, 2) or tuple(logits.shape) != (B, Q, H, L, P) or logits.dtype != offsets.dtype or \
+            tuple(reference_points.shape[:3]) != (B, Q, L) or reference_points.dim() != 4:
+        raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, offsets {tuple(offsets.shape)}, logits "
+                         f"{tuple(logits.shape)} ({logits.dtype} / {offsets.dtype}), reference_points "
+                         f"{tuple(reference_points.shape)}")
+    ref_dim = reference_points.shape[-1]
+    if ref_dim not in (2, 4):
+        raise ValueError(f"`reference_points` should have the last dim either 2 or 4, but got {ref_dim}.")
+    if tuple(img_shapes.shape) != (L, 2):
+        raise ValueError(f"`img_shapes` should be [{L}, 2], but got {tuple(img_shapes.shape)}.")
+    _check_devices(img, img_shapes, offsets, logits, reference_points)
+    pad = _padding_code(padding_mode)
+    cdt = offsets.dtype
+    suf = _fused_suffix_for(img.dtype, cdt, reference_points.dtype)
+    (img, vrow), offsets, logits = _value_rows(img), offsets.contiguous(), logits.contiguous()
+    reference_points = reference_points.contiguous()
+    shapes = _shapes_i64(img_shapes)
+    out = torch.empty((B, Q, H, D), dtype=cdt, device=img.device)
+    name = "msda_fwd_fused_levelref_split"
+    fn = getattr(_lib.load(), f"{name}_{suf}", None)
+    if fn is None:
+        return None
+
+    def call():
+        return fn(img.data_ptr(), shapes.data_ptr(), offsets.data_ptr(), logits.data_ptr(), reference_points.data_ptr(),
+                  out.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), vrow, _stream_ptr(img.device))
+
+    with _OnDevice(img.device):
+        timer = KernelTimer.active
+        rc = timer.launch(name, img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"{name}_{suf}")
+    return out
+
+
+def msda_hip_bwd_fused_split(out_grad, img, img_shapes, offsets, logits, reference_points, padding_mode, align_corners,
+                             need_img: bool = True, level_cells: int = 0, need_ref: bool = True):
+    """:func:`msda_hip_bwd_fused` with ``levelref=True`` on split projections (``msda_bwd_fused_levelref_split_<dtype>``):
+    ``(img_grad | None, offsets_grad, logits_grad, reference_points_grad | None)``, or None when the library declines."""
+    B, I, H, D = img.shape
+    _, Q, _, L, P, _ = offsets.shape
+    ref_dim = reference_points.shape[-1]
+    _check_devices(img, img_shapes, offsets, logits, reference_points, out_grad)
+    pad = _padding_code(padding_mode)
+    cdt = offsets.dtype
+    suf = _fused_suffix_for(img.dtype, cdt, reference_points.dtype)
+    storage = fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)
+    (img, vrow), offsets, logits = _value_rows(img), offsets.contiguous(), logits.contiguous()
+    reference_points = reference_points.contiguous()
+    out_grad = out_grad.contiguous()
+    if out_grad.dtype != cdt:
+        out_grad = out_grad.to(cdt)
+    shapes = _shapes_i64(img_shapes)
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_off = torch.empty((B, Q, H, L, P, 2), dtype=cdt, device=img.device)
+    g_lgt = torch.empty((B, Q, H, L, P), dtype=cdt, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, L, ref_dim), dtype=reference_points.dtype, device=img.device)
+    lib = _lib.load()
+    name = "msda_bwd_fused_levelref_split"
+    fn = getattr(lib, f"{name}_{suf}", None)
+    if fn is None:
+        return None
+    ws, ws_bytes = None, 0
+    level_cells = int(level_cells)
+    if need_img:  # (the interleaved pair's workspace: its query answers for these calls too)
+        ws_bytes = int(lib.msda_bwd_fused_workspace_bytes(B, I, H, D, Q, L, P, 4 if storage else offsets.element_size(),
+                                                          img.element_size(), level_cells, 0))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
+
+    def call():
+        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), offsets.data_ptr(), logits.data_ptr(),
+                  reference_points.data_ptr(), g_img.data_ptr() if need_img else None, g_off.data_ptr(), g_lgt.data_ptr(),
+                  g_ref_part.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
+                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream_ptr(img.device))
+
+    with _OnDevice(img.device):
+        timer = KernelTimer.active
+        rc = timer.launch(name, img.device, call) if timer else call()
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return None
+    _lib.check(rc, f"{name}_{suf}")
+    return g_img, g_off, g_lgt, (g_ref_part.sum(dim=2) if need_ref else None)
+
+
+class _HipFusedHFSplitFunction(Function):
+    """:class:`_HipFusedHFModuleCoreFunction` on split projections (``msda_*_fused_levelref_split_<dtype>``).  A forward the
+    library declines raises :class:`_SplitCallDeclined` — the caller composes; a backward it declines (the limits are the
+    forward's, so this is a library swapped in between) differentiates that composition."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, img, img_shapes, offsets, logits, reference_points, padding_mode, align_corners, level_cells=0):
+        ctx.level_cells = int(level_cells)
+        out = msda_hip_fwd_fused_split(img, img_shapes, offsets, logits, reference_points, padding_mode, align_corners)
+        if out is None:
+            raise _SplitCallDeclined()
+        ctx.save_for_backward(img, img_shapes, offsets, logits, reference_points)
+        ctx.padding_mode, ctx.align_corners = padding_mode, align_corners
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, out_grad):
+        img, img_shapes, offsets, logits, reference_points = ctx.saved_tensors
+        need_img, _, need_off, need_lgt, need_ref = ctx.needs_input_grad[:5]
+        res = msda_hip_bwd_fused_split(out_grad, img, img_shapes, offsets, logits, reference_points, ctx.padding_mode,
+                                       ctx.align_corners, need_img, level_cells=ctx.level_cells, need_ref=need_ref)
+        if res is None:
+            with torch.enable_grad():
+                leaves = [t.detach().requires_grad_(n) for t, n in ((img, need_img), (offsets, need_off), (logits, need_lgt),
+                                                                    (reference_points, need_ref))]
+                out = fused_hf_module_core(leaves[0], img_shapes, stack_split_projection(leaves[1], leaves[2]), leaves[3],
+                                           ctx.padding_mode, ctx.align_corners)
+                wrt = [t for t in leaves if t.requires_grad]
+                got = iter(torch.autograd.grad(out, wrt, out_grad.to(out.dtype), allow_unused=True))
+            res = [next(got) if t.requires_grad else None for t in leaves]
+        g_img, g_off, g_lgt, g_ref = res
+        return (g_img if need_img else None, None, g_off if need_off else None, g_lgt if need_lgt else None,
+                g_ref if need_ref else None, None, None, None)
+
+
+def fused_hf_module_core_split(img, img_shapes, sampling_offsets, attention_logits, reference_points, padding_mode,
+                               align_corners, level_shapes=None, value_mask=None, query_mask=None,
+                               split_in_kernels: bool = True) -> torch.Tensor:
+    """:func:`fused_hf_module_core` on the tensors a Hugging Face (or original Deformable-DETR, or mmcv) attention module
+    has: ``sampling_offsets`` ``[B, Q, H, L, P, 2]`` — or its ``Linear``'s flat ``[B, Q, H*L*P*2]`` — and
+    ``attention_logits`` ``[B, Q, H, L, P]``, ``[B, Q, H, L*P]`` or flat.  Its definition, and its route for host tensors,
+    is ``fused_hf_module_core(img, img_shapes, cat([offsets, logits[..., None]], -1), ...)``.  GPU tensors of the dtypes
+    that function's kernels serve (autocast and 16-bit storage next to fp32 reference points included) go to
+    ``msda_*_fused_levelref_split_<dtype>``, which read the two tensors where they are — no interleaving pass in either
+    direction — and return bit for bit what the interleaved kernels return.  Traced calls, a library without the symbols,
+    ``L * P`` beyond ``msda_fused_lp_limit``, a forward the library declines and ``split_in_kernels=False`` take the
+    composition.  ``value_mask`` / ``query_mask`` (``[B, I]`` / ``[B, Q]``, non-zero = real) compose around either route
+    with :func:`apply_value_mask` / :func:`apply_query_mask`.  Gradients go to ``img``, both projections and
+    ``reference_points``."""
+    if img.dim() != 4:
+        raise ValueError(f"`img` should be [B, I, H, D], but got {tuple(img.shape)}.")
+    offsets, logits = split_projection_views(sampling_offsets, attention_logits, img.shape[2], img_shapes.shape[0])
+    if query_mask is not None:
+        _validate_query_mask(query_mask, offsets)
+        offsets, logits = apply_query_mask(offsets, query_mask, 0.0), apply_query_mask(logits, query_mask, 0.0)
+        reference_points = apply_query_mask(reference_points, query_mask, 0.5)
+    img = apply_value_mask(img, value_mask)
+    out = None
+    cuda = img.device.type == "cuda"
+    if split_in_kernels and cuda and not torch.compiler.is_compiling() and offsets.dtype == logits.dtype and \
+            _lib.has_levelref_split():
+        _check_devices(img, offsets, logits, reference_points)
+        floating = img.is_floating_point() and offsets.is_floating_point() and reference_points.is_floating_point()
+        same = dtypes_supported(img.dtype, offsets.dtype) and reference_points.dtype == offsets.dtype
+        autocast = _autocast_on()
+        storage = fused_storage_dtypes(img.dtype, offsets.dtype, reference_points.dtype)
+        if floating and (autocast or same or storage) and \
+                offsets.shape[3] * offsets.shape[4] <= fused_lp_limit(img.shape[3], 4 if (autocast or storage)
+                                                                      else offsets.element_size()):
+            if img_shapes.device != img.device:
+                img_shapes = img_shapes.to(img.device)
+            try:
+                out = _HipFusedHFSplitFunction.apply(img, img_shapes, offsets, logits, reference_points, padding_mode,
+                                                     bool(align_corners),
+                                                     level_cells_of(level_shapes, img_shapes.shape[0], img.shape[1]))
+            except _SplitCallDeclined:
+                out = None
+    if out is None:
+        out = fused_hf_module_core(img, img_shapes, stack_split_projection(offsets, logits), reference_points, padding_mode,
+                                   align_corners, level_shapes)
+    return apply_query_mask(out, query_mask, 0.0)
+
+
+# ------------------------------------------------------------------------------------------
 # ... and for the Hugging Face modules with per-level point counts and the box rule (D-FINE, DEIMv2, RT-DETRv2:
 # transformers/models/d_fine/modeling_d_fine.py, DFineMultiscaleDeformableAttention.forward)
 # ------------------------------------------------------------------------------------------

@@ -21,13 +21,15 @@ rounded pixel per sample, :mod:`msda_triton_amd.discrete`) — and is what ``rep
 from __future__ import annotations
 
 import inspect
+import sys
 
 import numpy as np
 import torch
 from torch import nn
 
-from .functional import (_autocast_on, fused_hf_box_core, fused_hf_module_core, hf_box_level_scale,
-                         multiscale_deformable_attention)
+from ._linear import _plain_linear
+from .functional import (_autocast_on, fused_hf_box_core, fused_hf_module_core, fused_hf_module_core_split,
+                         hf_box_level_scale, multiscale_deformable_attention)
 
 
 class MultiScaleDeformableAttention(nn.Module):
@@ -139,6 +141,19 @@ def mask_in_kernels(value: torch.Tensor, num_queries: int) -> bool:
     return bool(MASK_IN_KERNELS) and value.device.type == "cuda" and value.dtype in (torch.float32, torch.bfloat16)
 
 
+# Measured (profiles/r17_levelref_split_bench.json): storage dtypes for which the split-projection kernels
+# (msda_*_fused_levelref_split_<dtype>) are ahead of `cat` + the interleaved kernels by the project's rule — slowest repeat
+# below the other leg's fastest, forward plus backward.  The adapter's non-plain route hands the two layers' outputs to those
+# kernels for these dtypes and interleaves them for every other one.
+SPLIT_IN_KERNELS_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def split_in_kernels(value: torch.Tensor) -> bool:
+    """Does the adapter's route for non-plain projection layers take the split-projection kernels for this pyramid, or
+    interleave the two outputs in front of the interleaved kernels (the rule above)?"""
+    return value.device.type == "cuda" and value.dtype in SPLIT_IN_KERNELS_DTYPES
+
+
 class FusedHFDeformableAttention:
     """Mixed into the class of a Hugging Face attention module (``DeformableDetrMultiscaleDeformableAttention``,
     ``GroundingDinoMultiscaleDeformableAttention``, the RT-DETR family's ...) by ``replace_hf_msda(model, fused=True)``:
@@ -158,7 +173,12 @@ class FusedHFDeformableAttention:
     cross-attention read them as values through the same mask (a row of zeros whatever they hold), and the two-stage
     proposals ``masked_fill`` them.  Taken only when all three hold: a mask was passed, the layer attends to its own
     hidden states (tested on the arguments, before the position embeddings are added), and the mask's shape is
-    ``hidden_states.shape[:2]``."""
+    ``hidden_states.shape[:2]``.
+
+    The one GEMM reads the two projection layers' ``.weight`` and ``.bias`` and never calls the layers, so it is taken only
+    for plain, hook-free ``nn.Linear`` pairs (``_linear._plain_linear``).  A LoRA / PEFT wrapper, a subclass, a quantised
+    replacement, a layer with hooks — and every traced call — has the two layers called as they are, and their outputs go
+    to :func:`fused_hf_module_core_split`, whose kernels read offsets and logits where the layers left them."""
 
     return_attention_weights = False
     skip_padded_queries = False
@@ -173,6 +193,28 @@ class FusedHFDeformableAttention:
             idx = torch.stack([2 * s, 2 * s + 1, 2 * n + s], -1).reshape(-1)
             self.__dict__["_msda_proj_rows"] = idx  # (not a buffer: state_dict stays the HF module's)
         return idx
+
+    def _plain_projections(self) -> bool:
+        return not torch.compiler.is_compiling() and _plain_linear(self.sampling_offsets) and \
+            _plain_linear(self.attention_weights)
+
+    def _split_route(self, hidden_states, value, reference_points, shapes, level_shapes, mask_kw) -> torch.Tensor:
+        """The core behind projection layers that must be CALLED: their outputs, as they are, to the split-projection
+        kernels (masks compose there)."""
+        offsets, logits = self.sampling_offsets(hidden_states), self.attention_weights(hidden_states)
+        kw = dict(level_shapes=level_shapes, value_mask=mask_kw.get("value_mask"), query_mask=mask_kw.get("query_mask"),
+                  split_in_kernels=split_in_kernels(value))
+        if value.device.type == "cuda" and value.dtype in (torch.bfloat16, torch.float16) and offsets.dtype == value.dtype \
+                and logits.dtype == value.dtype and reference_points.dtype == torch.float32:
+            with torch.autocast("cuda", enabled=False):  # (the module-storage kernels, as the plain route below)
+                return fused_hf_module_core_split(value, shapes, offsets, logits, reference_points, "zeros", False, **kw)
+        if offsets.dtype != value.dtype:
+            offsets = offsets.to(value.dtype)
+        if logits.dtype != value.dtype:
+            logits = logits.to(value.dtype)
+        if reference_points.dtype != value.dtype:
+            reference_points = reference_points.to(value.dtype)
+        return fused_hf_module_core_split(value, shapes, offsets, logits, reference_points, "zeros", False, **kw)
 
     def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
                 position_embeddings=None, reference_points=None, spatial_shapes=None, spatial_shapes_list=None,
@@ -196,6 +238,19 @@ class FusedHFDeformableAttention:
             mask_kw = dict(value_mask=attention_mask, mask_in_kernels=mask_in_kernels(value, num_queries))
             if self.skip_padded_queries and self_attention and tuple(attention_mask.shape) == (batch_size, num_queries):
                 mask_kw["query_mask"] = attention_mask  # every pixel is a query too: the mask covers both roles
+        return self._attend(hidden_states, value, reference_points, spatial_shapes, spatial_shapes_list, mask_kw)
+
+    def _attend(self, hidden_states, value, reference_points, spatial_shapes, spatial_shapes_list, mask_kw):
+        """Projections, core and output projection: ``hidden_states`` with its position embeddings added, ``value``
+        ``[B, I, H, D]`` unmasked, ``mask_kw`` the masks in the core's polarity (non-zero = real)."""
+        batch_size, num_queries, _ = hidden_states.shape
+        if not self._plain_projections():
+            level_shapes = spatial_shapes_list if isinstance(spatial_shapes_list, (list, tuple)) else None
+            shapes = spatial_shapes
+            if not torch.is_tensor(shapes):
+                shapes = _shapes_tensor(shapes if shapes is not None else spatial_shapes_list, value.device)
+            out = self._split_route(hidden_states, value, reference_points, shapes, level_shapes, mask_kw)
+            return self.output_proj(out.flatten(2)), None
         # ONE GEMM for offsets and logits, laid out [B, Q, H, L, P, 3]; the weight is gathered from the two HF parameters
         # (autograd routes its gradient back to them)
         rows = self._proj_rows(hidden_states.device)
@@ -242,6 +297,132 @@ def _wrap_fused(module: nn.Module) -> bool:
     if fused is None:
         fused = _FUSED_CLASSES[cls] = type("Fused" + cls.__name__, (FusedHFDeformableAttention, cls), {})
     module.__class__ = fused
+    return True
+
+
+_HIP_CORE = MultiScaleDeformableAttention()  # (parameter-free: the operator with "zeros" padding and the flatten behind it)
+
+
+class HFPixelDecoderDeformableAttention:
+    """Mixed into the class of a Mask2Former / OneFormer pixel-decoder attention module
+    (``Mask2FormerPixelDecoderEncoderMultiscaleDeformableAttention``, ``OneFormerPixelDecoderEncoder...``) by
+    ``replace_hf_msda(model)``.  Those modules carry the attributes of the Deformable-DETR ones and transformers'
+    level-reference rule, but call a module-level function ``multi_scale_deformable_attention`` instead of an ``attn``
+    child, take the level shapes as host numbers (``spatial_shapes_list``; older OneFormer: a ``spatial_shapes`` tensor)
+    and an ``attention_mask`` of the INVERSE polarity: ``True`` marks padding.  This forward is transformers' own, line by
+    line, with that function replaced by the HIP operator; ``state_dict`` keys are unchanged.  ``output_attentions=True``
+    (or ``module.return_attention_weights = True``) takes the original forward."""
+
+    return_attention_weights = False
+
+    def _named_args(self, args, kwargs):
+        # positional arguments behind `reference_points` follow the wrapped class's own order (Mask2Former's and OneFormer's differ)
+        if args:
+            names = type(self).__dict__.get("_msda_arg_names")
+            if names is None:
+                names = tuple(inspect.signature(self._msda_base.forward).parameters)[7:]
+                type(self)._msda_arg_names = names
+            kwargs.update(zip(names, args))
+        return kwargs
+
+    @staticmethod
+    def _level_shapes(kwargs, device):
+        shapes_list, shapes = kwargs.get("spatial_shapes_list"), kwargs.get("spatial_shapes")
+        if shapes_list is None and not torch.is_tensor(shapes):
+            shapes_list, shapes = shapes, None
+        if torch.is_tensor(shapes):
+            return shapes, None
+        level_shapes = [(int(h), int(w)) for h, w in shapes_list]
+        return _shapes_tensor(level_shapes, device), level_shapes
+
+    def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
+                position_embeddings=None, reference_points=None, *args, **kwargs):
+        kwargs = self._named_args(args, kwargs)
+        if self.return_attention_weights or kwargs.get("output_attentions"):
+            return self._msda_base.forward(self, hidden_states, attention_mask, encoder_hidden_states, encoder_attention_mask,
+                                           position_embeddings, reference_points, **kwargs)
+        if position_embeddings is not None:
+            hidden_states = hidden_states + position_embeddings
+        batch_size, num_queries, _ = hidden_states.shape
+        sequence_length = encoder_hidden_states.shape[1]
+        value = self.value_proj(encoder_hidden_states)
+        if attention_mask is not None:
+            value = value.masked_fill(attention_mask[..., None], float(0))  # (True = padding)
+        value = value.view(batch_size, sequence_length, self.n_heads, value.shape[-1] // self.n_heads)
+        shapes, level_shapes = self._level_shapes(kwargs, value.device)
+        sampling_offsets = self.sampling_offsets(hidden_states).view(
+            batch_size, num_queries, self.n_heads, self.n_levels, self.n_points, 2)
+        attention_weights = self.attention_weights(hidden_states).view(
+            batch_size, num_queries, self.n_heads, self.n_levels * self.n_points)
+        attention_weights = nn.functional.softmax(attention_weights, -1).view(
+            batch_size, num_queries, self.n_heads, self.n_levels, self.n_points)
+        if reference_points.shape[-1] == 2:
+            offset_normalizer = torch.stack([shapes[..., 1], shapes[..., 0]], -1)
+            sampling_locations = (reference_points[:, :, None, :, None, :]
+                                  + sampling_offsets / offset_normalizer[None, None, None, :, None, :])
+        elif reference_points.shape[-1] == 4:
+            sampling_locations = (reference_points[:, :, None, :, None, :2]
+                                  + sampling_offsets / self.n_points * reference_points[:, :, None, :, None, 2:] * 0.5)
+        else:
+            raise ValueError(f"Last dim of reference_points must be 2 or 4, but got {reference_points.shape[-1]}")
+        output = _HIP_CORE(value, shapes, level_shapes, None, sampling_locations, attention_weights)
+        return self.output_proj(output), attention_weights
+
+
+class FusedHFPixelDecoderDeformableAttention(HFPixelDecoderDeformableAttention, FusedHFDeformableAttention):
+    """The same modules under ``replace_hf_msda(model, fused=True)``: :class:`FusedHFDeformableAttention`'s forward — one
+    GEMM for a plain ``nn.Linear`` pair, the split-projection kernels behind anything else — with the shapes tensor built
+    from ``spatial_shapes_list`` and ``~attention_mask`` as ``value_mask`` (and, with ``skip_padded_queries`` in a
+    self-attending layer, as ``query_mask``).  The second element of the returned pair is ``None``."""
+
+    def forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None, encoder_attention_mask=None,
+                position_embeddings=None, reference_points=None, *args, **kwargs):
+        kwargs = self._named_args(args, kwargs)
+        if self.return_attention_weights or kwargs.get("output_attentions"):
+            return self._msda_base.forward(self, hidden_states, attention_mask, encoder_hidden_states, encoder_attention_mask,
+                                           position_embeddings, reference_points, **kwargs)
+        self_attention = encoder_hidden_states is hidden_states  # (on the arguments: the sum below makes a new tensor)
+        if position_embeddings is not None:
+            hidden_states = hidden_states + position_embeddings
+        batch_size, num_queries, _ = hidden_states.shape
+        sequence_length = encoder_hidden_states.shape[1]
+        value = self.value_proj(encoder_hidden_states)
+        value = value.view(batch_size, sequence_length, self.n_heads, value.shape[-1] // self.n_heads)
+        shapes, level_shapes = self._level_shapes(kwargs, value.device)
+        mask_kw = {}
+        if attention_mask is not None:
+            real = ~attention_mask if attention_mask.dtype == torch.bool else attention_mask == 0
+            mask_kw = dict(value_mask=real, mask_in_kernels=mask_in_kernels(value, num_queries))
+            if self.skip_padded_queries and self_attention and tuple(attention_mask.shape) == (batch_size, num_queries):
+                mask_kw["query_mask"] = real
+        return self._attend(hidden_states, value, reference_points, shapes, level_shapes, mask_kw)
+
+
+def _pixel_decoder_module(module: nn.Module) -> bool:
+    """The seven attributes, no ``attn`` child, and a ``multi_scale_deformable_attention`` function in the class's module."""
+    if isinstance(module, FusedHFDeformableAttention) or not all(hasattr(module, a) for a in _FUSED_ATTRS):
+        return False
+    if isinstance(getattr(module, "attn", None), nn.Module):
+        return False
+    home = sys.modules.get(getattr(type(module), "_msda_base", type(module)).__module__)
+    return callable(getattr(home, "multi_scale_deformable_attention", None))
+
+
+def _wrap_pixel_decoder(module: nn.Module, fused: bool) -> bool:
+    """Swap the class of a Mask2Former / OneFormer pixel-decoder attention module (matched by names, as everything here)
+    for its subclass with the HIP core — the fused one with ``fused``.  A module wrapped without ``fused`` before is
+    upgraded by a later call with it; nothing else is wrapped twice."""
+    if not _pixel_decoder_module(module):
+        return False
+    mixin = FusedHFPixelDecoderDeformableAttention if fused else HFPixelDecoderDeformableAttention
+    if isinstance(module, HFPixelDecoderDeformableAttention) and not fused:
+        return False
+    cls = getattr(type(module), "_msda_base", type(module))
+    key = (cls, mixin)
+    sub = _FUSED_CLASSES.get(key)
+    if sub is None:
+        sub = _FUSED_CLASSES[key] = type(("Fused" if fused else "Hip") + cls.__name__, (mixin, cls), {"_msda_base": cls})
+    module.__class__ = sub
     return True
 
 
@@ -401,7 +582,11 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
     number plus the modules wrapped (a D-FINE decoder layer then counts twice, once for its core and once for the
     wrapper).  ``skip_padded_queries=True`` (opt-in, no effect without ``fused=True``) sets
     :attr:`FusedHFDeformableAttention.skip_padded_queries` on every module wrapped as one: encoder layers then hand their
-    padding mask to the core as ``query_mask`` too (see the class); the count is what it is without the flag."""
+    padding mask to the core as ``query_mask`` too (see the class); the count is what it is without the flag.
+    Mask2Former's and OneFormer's pixel-decoder attention modules — the seven attributes above, no ``attn`` child, a
+    ``multi_scale_deformable_attention`` function in their class's module — have their class swapped for a subclass and are
+    counted: :class:`HFPixelDecoderDeformableAttention` without ``fused``, :class:`FusedHFPixelDecoderDeformableAttention`
+    with it (``skip_padded_queries`` applies to those as well)."""
     count = 0
     for parent in model.modules():
         for name, child in list(parent.named_children()):
@@ -417,6 +602,9 @@ def replace_hf_msda(model: nn.Module, discrete: bool = False, fused: bool = Fals
                 getattr(module, "decoder_method", None) == "discrete" and \
                 module.ms_deformable_attn_core is not ms_deformable_attn_core_v2:
             module.ms_deformable_attn_core = ms_deformable_attn_core_v2
+            count += 1
+    for module in list(model.modules()):
+        if _wrap_pixel_decoder(module, fused):  # (Mask2Former / OneFormer: no `attn` child to swap, the class carries the core)
             count += 1
     if fused:
         for module in list(model.modules()):
