@@ -171,25 +171,13 @@ def hf_box_discrete_hip_fwd_fused(img, img_shapes, proj, reference_points, count
     if (B2, H2) != (B, H) or tuple(reference_points.shape) != (B, Q, 4):
         raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
                          f"reference_points {tuple(reference_points.shape)}")
-    F._check_devices(img, img_shapes, proj, reference_points)
-    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    shapes = F._shapes_i64(img_shapes)
-    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    suf, _, img, vrow, shapes, proj, reference_points, _ = F._fused_prepare(img, img_shapes, proj, reference_points)
     fn = getattr(_lib.load(), f"msda_fwd_fused_hfbox_discrete_{suf}")
-
-    def call():
-        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
-                  B, I, H, D, Q, len(counts), _counts_array(counts), _scale_array(counts), float(offset_scale), vrow,
-                  F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_fwd_fused_hfbox_discrete", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
-        return None
-    _lib.check(rc, f"msda_fwd_fused_hfbox_discrete_{suf}")
-    return out
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    ok = F._fused_run("msda_fwd_fused_hfbox_discrete", f"msda_fwd_fused_hfbox_discrete_{suf}", img.device, fn,
+                      (img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+                       B, I, H, D, Q, len(counts), _counts_array(counts), _scale_array(counts), float(offset_scale), vrow))
+    return out if ok else None
 
 
 def hf_box_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, counts, offset_scale: float = 0.5,
@@ -204,45 +192,24 @@ def hf_box_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_poi
         return None
     B, I, H, D = img.shape
     _, Q, _, S, _ = proj.shape
-    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
-    cdt = proj.dtype
-    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and boxes fp32)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    out_grad = out_grad.contiguous()
-    if out_grad.dtype != cdt:
-        out_grad = out_grad.to(cdt)
-    shapes = F._shapes_i64(img_shapes)
-    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
-    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
+    suf, _, img, vrow, shapes, proj, reference_points, out_grad = F._fused_prepare(img, img_shapes, proj, reference_points,
+                                                                                   out_grad=out_grad)
     lib = _lib.load()
     fn = getattr(lib, f"msda_bwd_fused_hfbox_discrete_{suf}")
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=proj.dtype, device=img.device)
     arr, scale = _counts_array(counts), _scale_array(counts)
-    ws, ws_bytes = None, 0
     level_cells = int(level_cells)
-    if need_img:  # (a frozen value pyramid needs no workspace at all)
-        ws_bytes = int(lib.msda_bwd_fused_hfbox_discrete_workspace_bytes(
-            B, I, H, D, Q, len(counts), arr, 4 if storage else proj.element_size(), img.element_size(), level_cells, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
-
-    def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
-                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), B, I, H, D, Q, len(counts), arr, scale,
-                  float(offset_scale), level_cells, vrow, ws.data_ptr() if ws is not None else None, ws_bytes,
-                  F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_bwd_fused_hfbox_discrete", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+    ws, ws_bytes = F._fused_workspace(need_img, lib.msda_bwd_fused_hfbox_discrete_workspace_bytes,
+                                      (B, I, H, D, Q, len(counts), arr), suf, proj, img, level_cells)
+    if not F._fused_run("msda_bwd_fused_hfbox_discrete", f"msda_bwd_fused_hfbox_discrete_{suf}", img.device, fn,
+                        (out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                         g_img.data_ptr() if need_img else None, g_proj.data_ptr(), B, I, H, D, Q, len(counts), arr, scale,
+                         float(offset_scale), level_cells, vrow, ws.data_ptr() if need_img else None, ws_bytes)):
         return None
-    _lib.check(rc, f"msda_bwd_fused_hfbox_discrete_{suf}")
     res = (g_img, g_proj)
     if parked_points and ws is not None:
-        pdt = torch.float32 if reference_points.element_size() == 2 else reference_points.dtype
-        ns = B * Q * H * S
-        res += (ws[:ns * 2 * pdt.itemsize].view(pdt).view(B, Q, H, S, 2).clone(),
-                ws[ns * 2 * pdt.itemsize:ns * 3 * pdt.itemsize].view(pdt).view(B, Q, H, S).clone())
+        res += F._parked(ws, reference_points, B, Q, H, S, weights=True)
     return res
 
 
@@ -286,14 +253,11 @@ class _HipFusedHfBoxDiscreteFunction(Function):
                                                 need_img, level_cells=ctx.level_cells)
             if res is not None:
                 return res[0], None, res[1], None, None, None, None
-        with torch.enable_grad():
-            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
-            pts, att = F.hf_box_sampling_inputs(proj_, reference_points.detach(), counts, ctx.offset_scale)
-        g_img, g_att = discrete_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(), counts,
-                                        (need_img, need_proj), ctx.level_cells)
-        g_proj = None
-        if need_proj:
-            g_proj = torch.autograd.grad([att], [proj_], [g_att])[0].to(proj.dtype)
+        g_img, g_proj, _ = F._composed_backward(
+            lambda proj_, ref_: F.hf_box_sampling_inputs(proj_, ref_, counts, ctx.offset_scale),
+            lambda g, pts, att, want_img, want_attn: discrete_hip_bwd(g, img, img_shapes, pts, att, counts,
+                                                                      (want_img, want_attn), ctx.level_cells),
+            out_grad, proj, reference_points, need_img, need_proj, False)
         return g_img, None, g_proj, None, None, None, None
 
 
@@ -347,24 +311,13 @@ def module_discrete_hip_fwd_fused(img, img_shapes, proj, reference_points, count
     if (B2, H2) != (B, H) or tuple(reference_points.shape) != (B, Q, ref_dim) or ref_dim not in (2, 4):
         raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
                          f"reference_points {tuple(reference_points.shape)}")
-    F._check_devices(img, img_shapes, proj, reference_points)
-    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    shapes = F._shapes_i64(img_shapes)
-    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    suf, _, img, vrow, shapes, proj, reference_points, _ = F._fused_prepare(img, img_shapes, proj, reference_points)
     fn = getattr(_lib.load(), f"msda_fwd_fused_discrete_{suf}")
-
-    def call():
-        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
-                  B, I, H, D, Q, len(counts), _counts_array(counts), ref_dim, vrow, F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_fwd_fused_discrete", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
-        return None
-    _lib.check(rc, f"msda_fwd_fused_discrete_{suf}")
-    return out
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    ok = F._fused_run("msda_fwd_fused_discrete", f"msda_fwd_fused_discrete_{suf}", img.device, fn,
+                      (img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+                       B, I, H, D, Q, len(counts), _counts_array(counts), ref_dim, vrow))
+    return out if ok else None
 
 
 def module_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, counts, need_img: bool = True,
@@ -377,44 +330,24 @@ def module_discrete_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_poi
     B, I, H, D = img.shape
     _, Q, _, S, _ = proj.shape
     ref_dim = reference_points.shape[-1]
-    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
-    cdt = proj.dtype
-    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and reference points fp32)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    out_grad = out_grad.contiguous()
-    if out_grad.dtype != cdt:
-        out_grad = out_grad.to(cdt)
-    shapes = F._shapes_i64(img_shapes)
-    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
-    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
+    suf, _, img, vrow, shapes, proj, reference_points, out_grad = F._fused_prepare(img, img_shapes, proj, reference_points,
+                                                                                   out_grad=out_grad)
     lib = _lib.load()
     fn = getattr(lib, f"msda_bwd_fused_discrete_{suf}")
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=proj.dtype, device=img.device)
     arr = _counts_array(counts)
-    ws, ws_bytes = None, 0
     level_cells = int(level_cells)
-    if need_img:  # (a frozen value pyramid needs no workspace at all)
-        ws_bytes = int(lib.msda_bwd_fused_discrete_workspace_bytes(
-            B, I, H, D, Q, len(counts), arr, 4 if storage else proj.element_size(), img.element_size(), level_cells, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
-
-    def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
-                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), B, I, H, D, Q, len(counts), arr, ref_dim,
-                  level_cells, vrow, ws.data_ptr() if ws is not None else None, ws_bytes, F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_bwd_fused_discrete", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+    ws, ws_bytes = F._fused_workspace(need_img, lib.msda_bwd_fused_discrete_workspace_bytes,
+                                      (B, I, H, D, Q, len(counts), arr), suf, proj, img, level_cells)
+    if not F._fused_run("msda_bwd_fused_discrete", f"msda_bwd_fused_discrete_{suf}", img.device, fn,
+                        (out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                         g_img.data_ptr() if need_img else None, g_proj.data_ptr(), B, I, H, D, Q, len(counts), arr, ref_dim,
+                         level_cells, vrow, ws.data_ptr() if need_img else None, ws_bytes)):
         return None
-    _lib.check(rc, f"msda_bwd_fused_discrete_{suf}")
     res = (g_img, g_proj)
     if parked_points and ws is not None:
-        pdt = torch.float32 if reference_points.element_size() == 2 else reference_points.dtype
-        ns = B * Q * H * S
-        res += (ws[:ns * 2 * pdt.itemsize].view(pdt).view(B, Q, H, S, 2).clone(),
-                ws[ns * 2 * pdt.itemsize:ns * 3 * pdt.itemsize].view(pdt).view(B, Q, H, S).clone())
+        res += F._parked(ws, reference_points, B, Q, H, S, weights=True)
     return res
 
 
@@ -461,14 +394,11 @@ class _HipFusedModuleDiscreteFunction(Function):
                                                 level_cells=ctx.level_cells)
             if res is not None:
                 return res[0], None, res[1], None, None, None
-        with torch.enable_grad():
-            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
-            pts, att = ragged_module_sampling_inputs(proj_, img_shapes, reference_points.detach(), counts)
-        g_img, g_att = discrete_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(), counts,
-                                        (need_img, need_proj), ctx.level_cells)
-        g_proj = None
-        if need_proj:
-            g_proj = torch.autograd.grad([att], [proj_], [g_att])[0].to(proj.dtype)
+        g_img, g_proj, _ = F._composed_backward(
+            lambda proj_, ref_: ragged_module_sampling_inputs(proj_, img_shapes, ref_, counts),
+            lambda g, pts, att, want_img, want_attn: discrete_hip_bwd(g, img, img_shapes, pts, att, counts,
+                                                                      (want_img, want_attn), ctx.level_cells),
+            out_grad, proj, reference_points, need_img, need_proj, False)
         return g_img, None, g_proj, None, None, None  # (the reference points: no gradient in this mode)
 
 

@@ -417,6 +417,85 @@ class KernelTimer:
 
 
 # ------------------------------------------------------------------------------------------
+# the steps every fused launcher shares (here, in .ragged and in .discrete): a launcher keeps its own shape check, its
+# output shapes and its argument tuple
+# ------------------------------------------------------------------------------------------
+def _fused_prepare(img, img_shapes, proj, reference_points, padding_mode=None, out_grad=None, logits=None):
+    """Device check, suffix, and every tensor as the kernels take it -> ``(suffix, padding code | None, img,
+    value_row_stride, shapes, proj, reference_points, out_grad | None)``, and ``logits`` behind those for the split pair.
+    ``out_grad`` (a backward): contiguous, in the projection's dtype — one rule for every family."""
+    _check_devices(*[t for t in (img, img_shapes, proj, logits, reference_points, out_grad) if t is not None])
+    pad = None if padding_mode is None else _padding_code(padding_mode)
+    cdt = proj.dtype
+    suf = _fused_suffix_for(img.dtype, cdt, reference_points.dtype)
+    (img, vrow), proj, reference_points = _value_rows(img), proj.contiguous(), reference_points.contiguous()
+    if out_grad is not None:
+        out_grad = out_grad.contiguous()
+        if out_grad.dtype != cdt:
+            out_grad = out_grad.to(cdt)
+    res = (suf, pad, img, vrow, _shapes_i64(img_shapes), proj, reference_points, out_grad)
+    return res if logits is None else res + (logits.contiguous(),)
+
+
+def _fused_workspace(need_img: bool, query, dims, suf: str, proj, img, level_cells: int):
+    """-> (workspace, its bytes) of a fused backward: ``query`` is the family's size query, ``dims`` its leading arguments
+    (B, I, H, D, Q, L and P or the counts array).  (None, 0) for a frozen value pyramid, which needs none at all (ADVICE
+    r04).  The arithmetic element size is 4 under a storage suffix (fp32 arithmetic on 16-bit tensors), else ``proj``'s."""
+    if not need_img:
+        return None, 0
+    ws_bytes = int(query(*dims, 4 if suf in _lib.FUSED_STORAGE_SUFFIXES else proj.element_size(), img.element_size(),
+                         level_cells, 0))
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=img.device), ws_bytes
+
+
+def _fused_run(group: str, symbol: str, device: torch.device, fn, args) -> bool:
+    """Issue ``fn(*args, stream)`` on ``device``'s current stream, under the per-kernel timer's ``group`` when one is
+    active.  False when the library declines the call (nothing was launched); any other failure raises."""
+    with _OnDevice(device):
+        timer = KernelTimer.active
+        if timer is None:
+            rc = fn(*args, _stream_ptr(device))
+        else:
+            rc = timer.launch(group, device, lambda: fn(*args, _stream_ptr(device)))
+    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+        return False
+    _lib.check(rc, symbol)
+    return True
+
+
+def _parked(ws, reference_points, B, Q, H, S, weights: bool):
+    """Copies of what a fused backward left at the head of its workspace for the grad_value passes: the sampling points
+    ``[B, Q, H, S, 2]`` and, behind them (``weights``: the discrete pairs), the softmaxed weights ``[B, Q, H, S]`` — in the
+    arithmetic dtype, float32 for the 16-bit operators (msda_common.hpp, ParkType)."""
+    pdt = torch.float32 if reference_points.element_size() == 2 else reference_points.dtype
+    n = B * Q * H * S * pdt.itemsize
+    points = ws[:2 * n].view(pdt).view(B, Q, H, S, 2).clone()
+    return (points, ws[2 * n:3 * n].view(pdt).view(B, Q, H, S).clone()) if weights else (points,)
+
+
+def _composed_backward(prologue, op_bwd, out_grad, proj, reference_points, need_img, need_proj, need_ref):
+    """The backward of a fused core the library declined: the prologue in PyTorch around the unfused operator's backward
+    -> ``(g_img, g_proj, g_ref)``.  ``prologue(proj, reference_points) -> (points, weights)`` in the reference points'
+    dtype; ``op_bwd(out_grad, points, weights, need_img, need_sample)`` the operator's backward — ``(g_img, g_points,
+    g_weights)``, or ``(g_img, g_weights)`` from the discrete operator, whose points take no gradient."""
+    with torch.enable_grad():
+        proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
+        ref_ = reference_points.detach().requires_grad_(need_ref)
+        pts, att = prologue(proj_, ref_)
+    need_sample = need_proj or need_ref
+    g_img, *g_sample = op_bwd(out_grad.to(pts.dtype), pts.detach(), att.detach(), need_img, need_sample)
+    g_proj = g_ref = None
+    if need_sample:
+        wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
+        grads = list(torch.autograd.grad([pts, att][-len(g_sample):], wrt, g_sample, allow_unused=True))
+        if need_proj:
+            g_proj = grads.pop(0).to(proj.dtype)
+        if need_ref:
+            g_ref = grads.pop(0)
+    return g_img, g_proj, g_ref
+
+
+# ------------------------------------------------------------------------------------------
 # launcher pair — the native seam (reference: kernels.py:351-379, 556-592)
 # ------------------------------------------------------------------------------------------
 def msda_hip_fwd(img, img_shapes, sampling_points, attention_weights, padding_mode, align_corners,
@@ -753,33 +832,20 @@ def msda_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, al
         raise ValueError(f"`reference_points` should have the last dim either 2 or 4, but got {ref_dim}.")
     if tuple(img_shapes.shape) != (L, 2):
         raise ValueError(f"`img_shapes` should be [{L}, 2], but got {tuple(img_shapes.shape)}.")
-    _check_devices(img, img_shapes, proj, reference_points)
-    pad = _padding_code(padding_mode)
-    cdt = proj.dtype
-    suf = _fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    (img, vrow), proj, reference_points = _value_rows(img), proj.contiguous(), reference_points.contiguous()
-    shapes = _shapes_i64(img_shapes)
-    out = torch.empty((B, Q, H, D), dtype=cdt, device=img.device)
-    lib = _lib.load()
+    suf, pad, img, vrow, shapes, proj, reference_points, _ = _fused_prepare(img, img_shapes, proj, reference_points,
+                                                                            padding_mode)
     name = "msda_fwd_fused_levelref" if levelref else "msda_fwd_fused"
     sym, mask_arg, _masks = _mask_args(name, value_mask, query_mask, img, proj) if levelref else \
         _module_mask_args(name, value_mask, query_mask, img, proj, masks_checked)
-    # (the timer's group stays the pair's — "msda_fwd_fused_levelref" — with or without a mask: it names the launcher)
-    fn = getattr(lib, f"{sym}_{suf}", None)
+    fn = getattr(_lib.load(), f"{sym}_{suf}", None)
     if fn is None:  # (a library built before the per-level entry points: the caller composes)
         return None
-
-    def call():
-        return fn(img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
-                  B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), vrow, _stream_ptr(img.device))
-
-    with _OnDevice(img.device):
-        timer = KernelTimer.active
-        rc = timer.launch(name, img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
-        return None
-    _lib.check(rc, f"{sym}_{suf}")
-    return out
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    # (the timer's group stays the pair's — "msda_fwd_fused_levelref" — with or without a mask: it names the launcher)
+    ok = _fused_run(name, f"{sym}_{suf}", img.device, fn,
+                    (img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                     out.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), vrow))
+    return out if ok else None
 
 
 def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners,
@@ -793,21 +859,8 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
     B, I, H, D = img.shape
     _, Q, _, L, P, _ = proj.shape
     ref_dim = reference_points.shape[-1]
-    _check_devices(img, img_shapes, proj, reference_points, out_grad)
-    pad = _padding_code(padding_mode)
-    cdt = proj.dtype
-    suf = _fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    storage = fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and reference points fp32)
-    (img, vrow), proj, reference_points = _value_rows(img), proj.contiguous(), reference_points.contiguous()
-    out_grad = out_grad.contiguous()
-    if out_grad.dtype != cdt:
-        out_grad = out_grad.to(cdt)
-    shapes = _shapes_i64(img_shapes)
-    kw = dict(dtype=cdt, device=img.device)
-    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
-    g_proj = torch.empty((B, Q, H, L, P, 3), **kw)
-    g_ref_part = torch.empty((B, Q, H, L, ref_dim) if levelref else (B, Q, H, ref_dim), dtype=reference_points.dtype,
-                             device=img.device)
+    suf, pad, img, vrow, shapes, proj, reference_points, out_grad = _fused_prepare(img, img_shapes, proj, reference_points,
+                                                                                   padding_mode, out_grad)
     lib = _lib.load()
     name = "msda_bwd_fused_levelref" if levelref else "msda_bwd_fused"
     # (the masked entry points; the workspace is the twin's)
@@ -816,25 +869,19 @@ def msda_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, paddin
     fn = getattr(lib, f"{sym}_{suf}", None)  # (the timer's group stays the pair's, as in the forward)
     if fn is None:
         return None
-    ws, ws_bytes = None, 0
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, L, P, 3), dtype=proj.dtype, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, L, ref_dim) if levelref else (B, Q, H, ref_dim), dtype=reference_points.dtype,
+                             device=img.device)
     level_cells = int(level_cells)  # the level-size bound (level_cells_of), an argument of the size query and the launch
-    if need_img:  # (a frozen value pyramid needs no workspace at all — ADVICE r04)
-        ws_bytes = int(lib.msda_bwd_fused_workspace_bytes(B, I, H, D, Q, L, P, 4 if storage else proj.element_size(),
-                                                          img.element_size(), level_cells, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
-
-    def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
-                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
-                  B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
-                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream_ptr(img.device))
-
-    with _OnDevice(img.device):
-        timer = KernelTimer.active
-        rc = timer.launch(name, img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+    ws, ws_bytes = _fused_workspace(need_img, lib.msda_bwd_fused_workspace_bytes, (B, I, H, D, Q, L, P), suf, proj, img,
+                                    level_cells)
+    if not _fused_run(name, f"{sym}_{suf}", img.device, fn,
+                      (out_grad.data_ptr(), img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(),
+                       reference_points.data_ptr(), g_img.data_ptr() if need_img else None, g_proj.data_ptr(),
+                       g_ref_part.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
+                       ws.data_ptr() if need_img else None, ws_bytes)):
         return None
-    _lib.check(rc, f"{sym}_{suf}")
     # (the kernel leaves per-head partials of grad_reference_points; their sum is a launch of its own — 16 us at the c2
     # shape — and reference points rarely require a gradient)
     return g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None)
@@ -884,23 +931,12 @@ class _HipFusedModuleCoreFunction(Function):
         if masked:  # (the forward ran masked; only the grad_value pipeline can decline here, and the message says why)
             raise _lib.MSDALibraryError("the masked fused backward was declined after its forward ran: "
                                         + _lib.load().msda_last_error().decode(errors="replace"))
-        with torch.enable_grad():
-            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
-            ref_ = reference_points.detach().requires_grad_(need_ref)
-            pts, att = module_sampling_inputs(proj_, img_shapes, ref_)
-        out_grad = out_grad.to(pts.dtype)
-        need_sample = need_proj or need_ref
-        g_img, g_pts, g_att = msda_hip_bwd(out_grad, img, img_shapes, pts.detach(), att.detach(), ctx.padding_mode,
-                                           ctx.align_corners, (need_img, need_sample, need_sample),
-                                           level_cells=ctx.level_cells)
-        g_proj = g_ref = None
-        if need_sample:
-            wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
-            grads = list(torch.autograd.grad([pts, att], wrt, [g_pts, g_att], allow_unused=True))
-            if need_proj:
-                g_proj = grads.pop(0).to(proj.dtype)
-            if need_ref:
-                g_ref = grads.pop(0)
+        g_img, g_proj, g_ref = _composed_backward(
+            lambda proj_, ref_: module_sampling_inputs(proj_, img_shapes, ref_),
+            lambda g, pts, att, want_img, want_sample: msda_hip_bwd(
+                g, img, img_shapes, pts, att, ctx.padding_mode, ctx.align_corners, (want_img, want_sample, want_sample),
+                level_cells=ctx.level_cells),
+            out_grad, proj, reference_points, need_img, need_proj, need_ref)
         return g_img, None, g_proj, g_ref, None, None, None, None, None
 
 
@@ -1114,26 +1150,14 @@ class _HipFusedHFModuleCoreFunction(Function):
             if res is not None:
                 g_img, g_proj, g_ref = res
                 return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None, None
-        with torch.enable_grad():
-            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
-            ref_ = reference_points.detach().requires_grad_(need_ref)
+        g_img, g_proj, g_ref = _composed_backward(
             # (a query mask: the chain rule runs on the sanitised inputs, so a masked query's gradients are where's zeros)
-            pts, att = hf_module_sampling_inputs(apply_query_mask(proj_, ctx.query_mask, 0.0), img_shapes,
-                                                 apply_query_mask(ref_, ctx.query_mask, 0.5))
-        out_grad = out_grad.to(pts.dtype)
-        need_sample = need_proj or need_ref
-        g_img, g_pts, g_att = msda_hip_bwd(out_grad, img, img_shapes, pts.detach(), att.detach(), ctx.padding_mode,
-                                           ctx.align_corners, (need_img, need_sample, need_sample),
-                                           level_cells=ctx.level_cells, value_mask=ctx.value_mask,
-                                           query_mask=ctx.query_mask)
-        g_proj = g_ref = None
-        if need_sample:
-            wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
-            grads = list(torch.autograd.grad([pts, att], wrt, [g_pts, g_att], allow_unused=True))
-            if need_proj:
-                g_proj = grads.pop(0).to(proj.dtype)
-            if need_ref:
-                g_ref = grads.pop(0)
+            lambda proj_, ref_: hf_module_sampling_inputs(apply_query_mask(proj_, ctx.query_mask, 0.0), img_shapes,
+                                                          apply_query_mask(ref_, ctx.query_mask, 0.5)),
+            lambda g, pts, att, want_img, want_sample: msda_hip_bwd(
+                g, img, img_shapes, pts, att, ctx.padding_mode, ctx.align_corners, (want_img, want_sample, want_sample),
+                level_cells=ctx.level_cells, value_mask=ctx.value_mask, query_mask=ctx.query_mask),
+            out_grad, proj, reference_points, need_img, need_proj, need_ref)
         return g_img, None, g_proj, g_ref, None, None, None, None, None
 
 
@@ -1260,30 +1284,17 @@ def msda_hip_fwd_fused_split(img, img_shapes, offsets, logits, reference_points,
         raise ValueError(f"`reference_points` should have the last dim either 2 or 4, but got {ref_dim}.")
     if tuple(img_shapes.shape) != (L, 2):
         raise ValueError(f"`img_shapes` should be [{L}, 2], but got {tuple(img_shapes.shape)}.")
-    _check_devices(img, img_shapes, offsets, logits, reference_points)
-    pad = _padding_code(padding_mode)
-    cdt = offsets.dtype
-    suf = _fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    (img, vrow), offsets, logits = _value_rows(img), offsets.contiguous(), logits.contiguous()
-    reference_points = reference_points.contiguous()
-    shapes = _shapes_i64(img_shapes)
-    out = torch.empty((B, Q, H, D), dtype=cdt, device=img.device)
+    suf, pad, img, vrow, shapes, offsets, reference_points, _, logits = _fused_prepare(
+        img, img_shapes, offsets, reference_points, padding_mode, logits=logits)
     name = "msda_fwd_fused_levelref_split"
     fn = getattr(_lib.load(), f"{name}_{suf}", None)
     if fn is None:
         return None
-
-    def call():
-        return fn(img.data_ptr(), shapes.data_ptr(), offsets.data_ptr(), logits.data_ptr(), reference_points.data_ptr(),
-                  out.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), vrow, _stream_ptr(img.device))
-
-    with _OnDevice(img.device):
-        timer = KernelTimer.active
-        rc = timer.launch(name, img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
-        return None
-    _lib.check(rc, f"{name}_{suf}")
-    return out
+    out = torch.empty((B, Q, H, D), dtype=offsets.dtype, device=img.device)
+    ok = _fused_run(name, f"{name}_{suf}", img.device, fn,
+                    (img.data_ptr(), shapes.data_ptr(), offsets.data_ptr(), logits.data_ptr(), reference_points.data_ptr(),
+                     out.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), vrow))
+    return out if ok else None
 
 
 def msda_hip_bwd_fused_split(out_grad, img, img_shapes, offsets, logits, reference_points, padding_mode, align_corners,
@@ -1293,45 +1304,28 @@ def msda_hip_bwd_fused_split(out_grad, img, img_shapes, offsets, logits, referen
     B, I, H, D = img.shape
     _, Q, _, L, P, _ = offsets.shape
     ref_dim = reference_points.shape[-1]
-    _check_devices(img, img_shapes, offsets, logits, reference_points, out_grad)
-    pad = _padding_code(padding_mode)
-    cdt = offsets.dtype
-    suf = _fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    storage = fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)
-    (img, vrow), offsets, logits = _value_rows(img), offsets.contiguous(), logits.contiguous()
-    reference_points = reference_points.contiguous()
-    out_grad = out_grad.contiguous()
-    if out_grad.dtype != cdt:
-        out_grad = out_grad.to(cdt)
-    shapes = _shapes_i64(img_shapes)
-    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
-    g_off = torch.empty((B, Q, H, L, P, 2), dtype=cdt, device=img.device)
-    g_lgt = torch.empty((B, Q, H, L, P), dtype=cdt, device=img.device)
-    g_ref_part = torch.empty((B, Q, H, L, ref_dim), dtype=reference_points.dtype, device=img.device)
+    suf, pad, img, vrow, shapes, offsets, reference_points, out_grad, logits = _fused_prepare(
+        img, img_shapes, offsets, reference_points, padding_mode, out_grad, logits)
     lib = _lib.load()
     name = "msda_bwd_fused_levelref_split"
     fn = getattr(lib, f"{name}_{suf}", None)
     if fn is None:
         return None
-    ws, ws_bytes = None, 0
+    cdt = offsets.dtype
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_off = torch.empty((B, Q, H, L, P, 2), dtype=cdt, device=img.device)
+    g_lgt = torch.empty((B, Q, H, L, P), dtype=cdt, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, L, ref_dim), dtype=reference_points.dtype, device=img.device)
     level_cells = int(level_cells)
-    if need_img:  # (the interleaved pair's workspace: its query answers for these calls too)
-        ws_bytes = int(lib.msda_bwd_fused_workspace_bytes(B, I, H, D, Q, L, P, 4 if storage else offsets.element_size(),
-                                                          img.element_size(), level_cells, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
-
-    def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), offsets.data_ptr(), logits.data_ptr(),
-                  reference_points.data_ptr(), g_img.data_ptr() if need_img else None, g_off.data_ptr(), g_lgt.data_ptr(),
-                  g_ref_part.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
-                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream_ptr(img.device))
-
-    with _OnDevice(img.device):
-        timer = KernelTimer.active
-        rc = timer.launch(name, img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+    # (the interleaved pair's workspace: its query answers for these calls too)
+    ws, ws_bytes = _fused_workspace(need_img, lib.msda_bwd_fused_workspace_bytes, (B, I, H, D, Q, L, P), suf, offsets, img,
+                                    level_cells)
+    if not _fused_run(name, f"{name}_{suf}", img.device, fn,
+                      (out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), offsets.data_ptr(), logits.data_ptr(),
+                       reference_points.data_ptr(), g_img.data_ptr() if need_img else None, g_off.data_ptr(),
+                       g_lgt.data_ptr(), g_ref_part.data_ptr(), B, I, H, D, Q, L, P, ref_dim, pad, int(bool(align_corners)),
+                       level_cells, vrow, ws.data_ptr() if need_img else None, ws_bytes)):
         return None
-    _lib.check(rc, f"{name}_{suf}")
     return g_img, g_off, g_lgt, (g_ref_part.sum(dim=2) if need_ref else None)
 
 

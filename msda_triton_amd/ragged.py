@@ -291,29 +291,18 @@ def ragged_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, 
     if (B2, H2) != (B, H) or reference_points.shape[0] != B:
         raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
                          f"reference_points {tuple(reference_points.shape)}")
-    F._check_devices(img, img_shapes, proj, reference_points)
-    pad = F._padding_code(padding_mode)
-    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    shapes = F._shapes_i64(img_shapes)
-    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    suf, pad, img, vrow, shapes, proj, reference_points, _ = F._fused_prepare(img, img_shapes, proj, reference_points,
+                                                                              padding_mode)
     sym, mask_arg, _masks = F._module_mask_args("msda_fwd_fused_ragged", value_mask, query_mask, img, proj, masks_checked)
     fn = getattr(_lib.load(), f"{sym}_{suf}", None)
     if fn is None:
         return None
-
-    def call():
-        return fn(img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
-                  B, I, H, D, Q, len(counts), _counts_array(counts), reference_points.shape[-1], pad,
-                  int(bool(align_corners)), vrow, F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_fwd_fused_ragged", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
-        return None
-    _lib.check(rc, f"{sym}_{suf}")
-    return out
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    ok = F._fused_run("msda_fwd_fused_ragged", f"{sym}_{suf}", img.device, fn,
+                      (img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                       out.data_ptr(), B, I, H, D, Q, len(counts), _counts_array(counts), reference_points.shape[-1], pad,
+                       int(bool(align_corners)), vrow))
+    return out if ok else None
 
 
 def ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
@@ -327,46 +316,27 @@ def ragged_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padd
     B, I, H, D = img.shape
     _, Q, _, S, _ = proj.shape
     ref_dim = reference_points.shape[-1]
-    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
-    pad = F._padding_code(padding_mode)
-    cdt = proj.dtype
-    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and reference points fp32)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    out_grad = out_grad.contiguous()
-    if out_grad.dtype != cdt:
-        out_grad = out_grad.to(cdt)
-    shapes = F._shapes_i64(img_shapes)
-    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
-    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
-    g_ref_part = torch.empty((B, Q, H, ref_dim), dtype=reference_points.dtype, device=img.device)
+    suf, pad, img, vrow, shapes, proj, reference_points, out_grad = F._fused_prepare(
+        img, img_shapes, proj, reference_points, padding_mode, out_grad)
     lib = _lib.load()
     # (the masked pair msda_bwd_fused_ragged_masked_<suffix>; the workspace is the twin's)
     sym, mask_arg, _masks = F._module_mask_args("msda_bwd_fused_ragged", value_mask, query_mask, img, proj, masks_checked)
     fn = getattr(lib, f"{sym}_{suf}", None)
     if fn is None:
         return None
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=proj.dtype, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, ref_dim), dtype=reference_points.dtype, device=img.device)
     arr = _counts_array(counts)
-    ws, ws_bytes = None, 0
     level_cells = int(level_cells)
-    if need_img:  # (a frozen value pyramid needs no workspace at all)
-        ws_bytes = int(lib.msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, len(counts), arr,
-                                                                 4 if storage else proj.element_size(),
-                                                                 img.element_size(), level_cells, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
-
-    def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
-                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
-                  B, I, H, D, Q, len(counts), arr, ref_dim, pad, int(bool(align_corners)), level_cells, vrow,
-                  ws.data_ptr() if ws is not None else None, ws_bytes, F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_bwd_fused_ragged", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+    ws, ws_bytes = F._fused_workspace(need_img, lib.msda_bwd_fused_ragged_workspace_bytes,
+                                      (B, I, H, D, Q, len(counts), arr), suf, proj, img, level_cells)
+    if not F._fused_run("msda_bwd_fused_ragged", f"{sym}_{suf}", img.device, fn,
+                        (out_grad.data_ptr(), img.data_ptr(), *mask_arg, shapes.data_ptr(), proj.data_ptr(),
+                         reference_points.data_ptr(), g_img.data_ptr() if need_img else None, g_proj.data_ptr(),
+                         g_ref_part.data_ptr(), B, I, H, D, Q, len(counts), arr, ref_dim, pad, int(bool(align_corners)),
+                         level_cells, vrow, ws.data_ptr() if need_img else None, ws_bytes)):
         return None
-    _lib.check(rc, f"{sym}_{suf}")
     return g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None)
 
 
@@ -416,22 +386,12 @@ class _HipFusedRaggedModuleCoreFunction(Function):
         if masked:  # (the forward ran masked; only the grad_value pipeline can decline here, and the message says why)
             raise _lib.MSDALibraryError("the masked fused ragged backward was declined after its forward ran: "
                                         + _lib.load().msda_last_error().decode(errors="replace"))
-        with torch.enable_grad():
-            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
-            ref_ = reference_points.detach().requires_grad_(need_ref)
-            pts, att = ragged_module_sampling_inputs(proj_, img_shapes, ref_, counts)
-        need_sample = need_proj or need_ref
-        g_img, g_pts, g_att = ragged_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(),
-                                             ctx.padding_mode, ctx.align_corners, counts,
-                                             (need_img, need_sample, need_sample), ctx.level_cells)
-        g_proj = g_ref = None
-        if need_sample:
-            wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
-            grads = list(torch.autograd.grad([pts, att], wrt, [g_pts, g_att], allow_unused=True))
-            if need_proj:
-                g_proj = grads.pop(0).to(proj.dtype)
-            if need_ref:
-                g_ref = grads.pop(0)
+        g_img, g_proj, g_ref = F._composed_backward(
+            lambda proj_, ref_: ragged_module_sampling_inputs(proj_, img_shapes, ref_, counts),
+            lambda g, pts, att, want_img, want_sample: ragged_hip_bwd(
+                g, img, img_shapes, pts, att, ctx.padding_mode, ctx.align_corners, counts,
+                (want_img, want_sample, want_sample), ctx.level_cells),
+            out_grad, proj, reference_points, need_img, need_proj, need_ref)
         return g_img, None, g_proj, g_ref, None, None, None, None, None, None
 
 
@@ -532,26 +492,15 @@ def hf_box_hip_fwd_fused(img, img_shapes, proj, reference_points, padding_mode, 
     if (B2, H2) != (B, H) or tuple(reference_points.shape) != (B, Q, 4):
         raise ValueError(f"inconsistent shapes: img {tuple(img.shape)}, proj {tuple(proj.shape)}, "
                          f"reference_points {tuple(reference_points.shape)}")
-    F._check_devices(img, img_shapes, proj, reference_points)
-    pad = F._padding_code(padding_mode)
-    suf = F._fused_suffix_for(img.dtype, proj.dtype, reference_points.dtype)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    shapes = F._shapes_i64(img_shapes)
-    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    suf, pad, img, vrow, shapes, proj, reference_points, _ = F._fused_prepare(img, img_shapes, proj, reference_points,
+                                                                              padding_mode)
     fn = getattr(_lib.load(), f"msda_fwd_fused_hfbox_{suf}")
-
-    def call():
-        return fn(img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
-                  B, I, H, D, Q, len(counts), _counts_array(counts), _scale_array(counts), float(offset_scale), 4, pad,
-                  int(bool(align_corners)), vrow, F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_fwd_fused_hfbox", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
-        return None
-    _lib.check(rc, f"msda_fwd_fused_hfbox_{suf}")
-    return out
+    out = torch.empty((B, Q, H, D), dtype=proj.dtype, device=img.device)
+    ok = F._fused_run("msda_fwd_fused_hfbox", f"msda_fwd_fused_hfbox_{suf}", img.device, fn,
+                      (img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), out.data_ptr(),
+                       B, I, H, D, Q, len(counts), _counts_array(counts), _scale_array(counts), float(offset_scale), 4, pad,
+                       int(bool(align_corners)), vrow))
+    return out if ok else None
 
 
 def hf_box_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padding_mode, align_corners, counts,
@@ -566,48 +515,27 @@ def hf_box_hip_bwd_fused(out_grad, img, img_shapes, proj, reference_points, padd
         return None
     B, I, H, D = img.shape
     _, Q, _, S, _ = proj.shape
-    F._check_devices(img, img_shapes, proj, reference_points, out_grad)
-    pad = F._padding_code(padding_mode)
-    cdt = proj.dtype
-    suf = F._fused_suffix_for(img.dtype, cdt, reference_points.dtype)
-    storage = F.fused_storage_dtypes(img.dtype, cdt, reference_points.dtype)  # (arithmetic and reference points fp32)
-    (img, vrow), proj, reference_points = F._value_rows(img), proj.contiguous(), reference_points.contiguous()
-    out_grad = out_grad.contiguous()
-    if out_grad.dtype != cdt:
-        out_grad = out_grad.to(cdt)
-    shapes = F._shapes_i64(img_shapes)
-    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
-    g_proj = torch.empty((B, Q, H, S, 3), dtype=cdt, device=img.device)
-    g_ref_part = torch.empty((B, Q, H, 4), dtype=reference_points.dtype, device=img.device)
+    suf, pad, img, vrow, shapes, proj, reference_points, out_grad = F._fused_prepare(
+        img, img_shapes, proj, reference_points, padding_mode, out_grad)
     lib = _lib.load()
     fn = getattr(lib, f"msda_bwd_fused_hfbox_{suf}")
+    g_img = torch.empty((B, I, H, D), dtype=img.dtype, device=img.device) if need_img else None
+    g_proj = torch.empty((B, Q, H, S, 3), dtype=proj.dtype, device=img.device)
+    g_ref_part = torch.empty((B, Q, H, 4), dtype=reference_points.dtype, device=img.device)
     arr, scale = _counts_array(counts), _scale_array(counts)
-    ws, ws_bytes = None, 0
     level_cells = int(level_cells)
-    if need_img:  # (a frozen value pyramid needs no workspace at all); the fused per-level-count pair's query answers
-        ws_bytes = int(lib.msda_bwd_fused_ragged_workspace_bytes(B, I, H, D, Q, len(counts), arr,
-                                                                 4 if storage else proj.element_size(),
-                                                                 img.element_size(), level_cells, 0))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=img.device)
-
-    def call():
-        return fn(out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
-                  g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
-                  B, I, H, D, Q, len(counts), arr, scale, float(offset_scale), 4, pad, int(bool(align_corners)),
-                  level_cells, vrow, ws.data_ptr() if ws is not None else None, ws_bytes, F._stream_ptr(img.device))
-
-    with F._OnDevice(img.device):
-        timer = F.KernelTimer.active
-        rc = timer.launch("msda_bwd_fused_hfbox", img.device, call) if timer else call()
-    if rc == -5:  # MSDA_ERR_UNSUPPORTED
+    # (the fused per-level-count pair's query answers)
+    ws, ws_bytes = F._fused_workspace(need_img, lib.msda_bwd_fused_ragged_workspace_bytes,
+                                      (B, I, H, D, Q, len(counts), arr), suf, proj, img, level_cells)
+    if not F._fused_run("msda_bwd_fused_hfbox", f"msda_bwd_fused_hfbox_{suf}", img.device, fn,
+                        (out_grad.data_ptr(), img.data_ptr(), shapes.data_ptr(), proj.data_ptr(), reference_points.data_ptr(),
+                         g_img.data_ptr() if need_img else None, g_proj.data_ptr(), g_ref_part.data_ptr(),
+                         B, I, H, D, Q, len(counts), arr, scale, float(offset_scale), 4, pad, int(bool(align_corners)),
+                         level_cells, vrow, ws.data_ptr() if need_img else None, ws_bytes)):
         return None
-    _lib.check(rc, f"msda_bwd_fused_hfbox_{suf}")
     res = (g_img, g_proj, (g_ref_part.sum(dim=2) if need_ref else None))
     if parked_points and ws is not None:
-        # (the 16-bit operators park them in float32: msda_common.hpp, ParkType)
-        pdt = torch.float32 if reference_points.element_size() == 2 else reference_points.dtype
-        n = B * Q * H * S * 2 * pdt.itemsize
-        res += (ws[:n].view(pdt).view(B, Q, H, S, 2).clone(),)
+        res += F._parked(ws, reference_points, B, Q, H, S, weights=False)
     return res
 
 
@@ -657,22 +585,12 @@ class _HipFusedHfBoxCoreFunction(Function):
             if res is not None:
                 g_img, g_proj, g_ref = res
                 return g_img, None, (g_proj if need_proj else None), (g_ref if need_ref else None), None, None, None, None, None
-        with torch.enable_grad():
-            proj_ = proj.detach().to(reference_points.dtype).requires_grad_(need_proj)
-            ref_ = reference_points.detach().requires_grad_(need_ref)
-            pts, att = F.hf_box_sampling_inputs(proj_, ref_, counts, ctx.offset_scale)
-        need_sample = need_proj or need_ref
-        g_img, g_pts, g_att = ragged_hip_bwd(out_grad.to(pts.dtype), img, img_shapes, pts.detach(), att.detach(),
-                                             ctx.padding_mode, ctx.align_corners, counts,
-                                             (need_img, need_sample, need_sample), ctx.level_cells)
-        g_proj = g_ref = None
-        if need_sample:
-            wrt = [t for t, n in ((proj_, need_proj), (ref_, need_ref)) if n]
-            grads = list(torch.autograd.grad([pts, att], wrt, [g_pts, g_att], allow_unused=True))
-            if need_proj:
-                g_proj = grads.pop(0).to(proj.dtype)
-            if need_ref:
-                g_ref = grads.pop(0)
+        g_img, g_proj, g_ref = F._composed_backward(
+            lambda proj_, ref_: F.hf_box_sampling_inputs(proj_, ref_, counts, ctx.offset_scale),
+            lambda g, pts, att, want_img, want_sample: ragged_hip_bwd(
+                g, img, img_shapes, pts, att, ctx.padding_mode, ctx.align_corners, counts,
+                (want_img, want_sample, want_sample), ctx.level_cells),
+            out_grad, proj, reference_points, need_img, need_proj, need_ref)
         return g_img, None, g_proj, g_ref, None, None, None, None, None
 
 
