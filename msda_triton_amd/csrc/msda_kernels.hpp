@@ -184,13 +184,15 @@ template <typename A> __device__ __forceinline__ int discrete_pixel(A x, int n)
 //   4-d   x = ref_x + ox / P * ref_w * 0.5  y = ref_y + oy / P * ref_h * 0.5
 // and the backward leaves a grad_reference_points partial per (b, q, head, LEVEL).  A kernarg type of its own with
 // nothing behind Params: the uniform and the per-level-count instantiations keep their types and their code, and the
-// three rules hang on overloads / `if constexpr (kLevelRef<PP>)`.  Uniform point count only.
+// rules are LEVELREF2D / LEVELREFBOX of msda_prologue.hpp's rule ladder (ref_of / ref_row_elems: overloads).  Uniform
+// point count only.
 struct LevelRefParams : Params {};
 // ... and the same pair on SPLIT projections (msda_*_fused_levelref_split_<dtype>): what the two Linear layers of every
 // module in the ecosystem produce — offsets [B, Q, H, L, P, 2] and logits [B, Q, H, L, P], byte for byte the `loc` and
 // `attn` layouts of the sampling operators.  `loc` holds the offsets and `grad_loc` their gradient; the logits and their
 // gradient ride BEHIND Params (the preloaded front is unchanged).  Only phase 0's three loads and phase 3's three stores
-// hang on `if constexpr (kSplitProj<PP>)`: everything between them is the level-reference pair's, operation by operation.
+// differ (MSDA_PROJ_LOAD / MSDA_PROJ_STORE, msda_prologue.hpp): everything between them is the level-reference pair's,
+// operation by operation.
 struct LevelRefSplitParams : LevelRefParams {
     const void *logits;
     void *grad_logits;
@@ -252,35 +254,6 @@ template <typename PP> struct MaskSrc<PP, true> {
 template <typename PP>
 constexpr bool kLevelRef = std::is_base_of<LevelRefParams, PP>::value || std::is_base_of<LevelRefMaskedParams, PP>::value;
 
-// Elements of `ref` per query, and the reference point of (query fq, level l) behind the batch element's base.
-__device__ __forceinline__ int ref_row_elems(const Params &p) { return p.ref_dim; }
-__device__ __forceinline__ int ref_row_elems(const LevelRefParams &p) { return p.L * p.ref_dim; }
-__device__ __forceinline__ int ref_row_elems(const LevelRefMaskedParams &p) { return p.L * p.ref_dim; }
-template <typename T> __device__ __forceinline__ const T *ref_of(const Params &p, const T *refp, int fq, int)
-{
-    return refp + (size_t)fq * p.ref_dim;
-}
-template <typename T> __device__ __forceinline__ const T *ref_of(const LevelRefParams &p, const T *refp, int fq, int l)
-{
-    return refp + ((size_t)fq * p.L + l) * p.ref_dim;
-}
-template <typename T> __device__ __forceinline__ const T *ref_of(const LevelRefMaskedParams &p, const T *refp, int fq, int l)
-{
-    return refp + ((size_t)fq * p.L + l) * p.ref_dim;
-}
-// The 4-d point from the offset already divided by P: two rounded multiplies, then a rounded add — transformers'
-// `ref + offsets / P * size * 0.5`, operation by operation.  The translation units are built with -ffp-contract=fast;
-// the product passes through an empty asm statement (as discrete_pixel's) so that the add cannot take it as an FMA
-// operand: the point is bit for bit the host's, and grad_value's parked copy of it (the backward's phase 3 calls this
-// again on the same operands) names the cell the forward sampled.
-template <typename A> __device__ __forceinline__ A levelref_box_point(A r, A q, A size)
-{
-    A t = q * size;
-    t = t * (A)0.5;
-    asm("" : "+v"(t));
-    return r + t;
-}
-
 // ---- Hugging Face's box rule with per-level point counts (msda_*_fused_hfbox_<dtype>): the fused module kernels for
 // D-FINE, DEIMv2 and RT-DETRv2 ----
 // The layout is the per-level-count pair's (`proj` [B, Q, H, S, 3] level-major, `ref` [B, Q, 4], the partials
@@ -290,8 +263,8 @@ template <typename A> __device__ __forceinline__ A levelref_box_point(A r, A q, 
 // the scale as an fp32 buffer and converts it, so in fp64 it is float32(1/3) widened, not 1/3 — and offset_scale the
 // config's Python float.  Both ride behind the level starts at the end of the kernarg (the preloaded front is unchanged):
 // a kernarg type of its own, derived from RaggedParams so that the level scan, the parked level and the ragged
-// grad_value pipeline (value_pass_params, msda_launch.hpp) serve it as they are, and the rule hangs on
-// `if constexpr (kHfBox<PP>)` in front of the other rules' branches.
+// grad_value pipeline (value_pass_params, msda_launch.hpp) serve it as they are, and the rule is HFBOX,
+// the first line of msda_prologue.hpp's rule ladder.
 struct HfBoxParams : RaggedParams {
     float lscale[kFusedRaggedMaxLevels];  // s_l; entries beyond L are 0
     double off_scale;
@@ -313,33 +286,6 @@ template <typename PP> constexpr bool kModuleDiscrete = std::is_base_of<ModuleDi
 // either prologue in front of discrete sampling: the launch layer's steps the two pairs share
 template <typename PP> constexpr bool kFusedDiscrete = kHfBoxDiscrete<PP> || kModuleDiscrete<PP>;
 
-// s_l of the sample's level, converted to the arithmetic type: a select per level on scalars at constant kernarg offsets
-// (as lvl_of's scan; the level itself comes from that scan, the host bounds L by kFusedRaggedMaxLevels).
-template <typename A, typename PP> __device__ __forceinline__ A hfbox_scale(const PP &p, int l)
-{
-    if constexpr (kHfBox<PP>) {
-        float s = p.lscale[0];
-#pragma unroll
-        for (int k = 1; k < kFusedRaggedMaxLevels; ++k) {
-            if (k >= p.L) break;
-            s = l >= k ? p.lscale[k] : s;
-        }
-        return (A)s;
-    } else {
-        return (A)0;
-    }
-}
-// The point from q = o * s_l (the backward parks q: phase 3 calls this again on the same operands, so the copy written
-// for grad_value names the cell the forward sampled).  The translation units are built with -ffp-contract=fast; the last
-// product passes through an empty asm statement (as levelref_box_point's) so that the add cannot take it as an FMA operand.
-template <typename A> __device__ __forceinline__ A hfbox_point(A r, A q, A size, A off_scale)
-{
-    A t = q * size;
-    t = t * off_scale;
-    asm("" : "+v"(t));
-    return r + t;
-}
-
 template <typename A> struct alignas(16) Rec4 {
     A v[4];
 };
@@ -352,6 +298,13 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+}  // namespace msda
+
+// the fused prologues' sampling-point rules, projection layouts and softmax statistics (reads the kernarg types above)
+#include "msda_prologue.hpp"
+
+namespace msda {
 
 // The (b, h) plane of `value`: pixel rows Params::v_row bytes apart (H * D * sizeof(TV) when dense; a caller that owns the
 // layout may pad every pixel's H rows by one 128-byte line so that a head's rows cycle through all residues mod 8 of
@@ -633,26 +586,16 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
     // per-plane bases (64-bit, uniform) + 32-bit per-sample indices (the host checks Q*H*L*P*3 < 2^31)
     size_t plane_s0 = ((size_t)b * p.Q * p.H + h) * p.LP;
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
-    [[maybe_unused]] const TS *proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;  // FUSED: raw projection (dx, dy, logit)
     const T *attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
-    // split projections: the plane's offsets (dx, dy) and, apart from them, its logits
-    [[maybe_unused]] const TS *off2 = nullptr, *lgt1 = nullptr;
-    if constexpr (kSplitProj<PP>) {
-        off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
-        lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
-    }
+    MSDA_PROJ_DECLARE(plane_s0)  // FUSED: the raw projection (dx, dy, logit), interleaved or split
     // the wave's plane-dependent values for plane pair0 + hp_ (two planes per workgroup: per slice)
     auto select_plane = [&](int hp_) {
         h = pair0 + hp_ - b * p.H;
         rs = make_rsrc(plane_base<TV>(p, b, h), plane_span<TV>(p, h));
         plane_s0 = ((size_t)b * p.Q * p.H + h) * p.LP;
         loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
-        proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;
         attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
-        if constexpr (kSplitProj<PP>) {
-            off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
-            lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
-        }
+        MSDA_PROJ_REBASE(plane_s0)
     };
     const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * ref_row_elems(p) : nullptr;
     const int HLP = p.H * p.LP;
@@ -795,65 +738,20 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(BLK == kBlo
                         const int sl = f - imul24(fu, sc);
                         const int fq = wq0 + fu;
                         if (fq < q_end_ && unit_live(fu)) {
-                            [[maybe_unused]] int npts = p.P;  // per-level point counts: the count of the sample's own level
-                            int l;
-                            if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
-                            else l = div_small(sl, p.P, inv_P);
+                            MSDA_SAMPLE_LEVEL(sl, l, npts)  // (npts: the point count of the sample's own level)
                             const int sidx = imul24(fq, HLP) + sl;
                             A ox, oy, lg;
-                            if constexpr (kSplitProj<PP>) {  // (the three loads are all that differs)
-                                ox = SR::to_acc(off2[2 * sidx]), oy = SR::to_acc(off2[2 * sidx + 1]);
-                                lg = SR::to_acc(lgt1[sidx]);
-                            } else {
-                                ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
-                                lg = SR::to_acc(proj3[3 * sidx + 2]);
-                            }
+                            MSDA_PROJ_LOAD(sidx, ox, oy, lg)
                             const T *r = ref_of(p, refp, fq, l);
                             Rec4<A> w;
                             w.v[0] = lg;
-                            if constexpr (kHfBox<PP>) {  // transformers' box rule with the level's own 1 / P_l
-                                const A s = hfbox_scale<A>(p, l), os = (A)p.off_scale;
-                                w.v[1] = hfbox_point<A>(TR::to_acc(r[0]), ox * s, TR::to_acc(r[2]), os);
-                                w.v[2] = hfbox_point<A>(TR::to_acc(r[1]), oy * s, TR::to_acc(r[3]), os);
-                            } else if constexpr (kLevelRef<PP>) {  // transformers' rule on the level's own reference point
-                                if (p.ref_dim == 2) {
-                                    w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->w[l];
-                                    w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->h[l];
-                                } else {
-                                    w.v[1] = levelref_box_point<A>(TR::to_acc(r[0]), ox / (A)p.P, TR::to_acc(r[2]));
-                                    w.v[2] = levelref_box_point<A>(TR::to_acc(r[1]), oy / (A)p.P, TR::to_acc(r[3]));
-                                }
-                            } else if (p.ref_dim == 2) {
-                                // NB: (x, y) offsets are divided by img_shapes in its stored (h, w) order (frontend.py:275)
-                                w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->h[l];
-                                w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->w[l];
-                            } else if constexpr (kRagged<PP>) {
-                                // multiply, divide, add — each rounded once, nothing for the compiler to fuse: the point
-                                // is bit for bit what the same expression gives in PyTorch, so a sample within an ulp of
-                                // a pixel boundary lands on the same side of it as in the unfused composition
-                                w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) / (A)(2 * npts);
-                                w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) / (A)(2 * npts);
-                            } else {
-                                w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) / (A)(2 * p.P);
-                                w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) / (A)(2 * p.P);
-                            }
+                            MSDA_RULE_FORWARD(r, l, npts, ox, oy, w.v[1], w.v[2])
                             w.v[3] = kRagged<PP> ? (A)l : (A)0;  // (per-level counts: phase 1 takes the level from here)
                             w_rec[imul24(fu, scp) + sl] = w;
                         }
                     }
                     wave_lds_sync();
-                    if (unit_ok && q_real) {
-                        A mx = -__builtin_huge_val();
-                        for (int sl = j; sl < sc; sl += G) mx = fmax_t(mx, w_rec[imul24(wunit, scp) + sl].v[0]);
-                        mx = group_max<G>(mx);
-                        A sum = (A)0;
-                        for (int sl = j; sl < sc; sl += G) sum += exp_t(w_rec[imul24(wunit, scp) + sl].v[0] - mx);
-                        sum = group_sum<G>(sum);
-                        if (j == 0) {
-                            w_rec[imul24(wunit, scp) + sc].v[0] = mx;
-                            w_rec[imul24(wunit, scp) + sc].v[1] = (A)1 / sum;
-                        }
-                    }
+                    if (unit_ok && q_real) MSDA_UNIT_SOFTMAX_STATS(w_rec, imul24(wunit, scp), sc, j)
                     wave_lds_sync();
                 }
                 // ---- phase 1: the wave's UPW * sc samples, one per lane and trip ----
@@ -1202,30 +1100,20 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
     // per-plane bases (64-bit, uniform) + 32-bit per-sample indices (the host checks Q*H*L*P*2 < 2^31)
     size_t plane_s0 = ((size_t)b * p.Q * p.H + h) * p.LP;
     const T *loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
-    [[maybe_unused]] const TS *proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;  // FUSED: raw projection (dx, dy, logit)
     const T *attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
-    // split projections: the plane's offsets (dx, dy) and, apart from them, its logits (as in msda_fwd_kernel)
-    [[maybe_unused]] const TS *off2 = nullptr, *lgt1 = nullptr;
-    if constexpr (kSplitProj<PP>) {
-        off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
-        lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
-    }
+    MSDA_PROJ_DECLARE(plane_s0)  // FUSED: the raw projection (dx, dy, logit), interleaved or split
     auto select_plane = [&](int hp_) {  // the plane-dependent values for plane pair0 + hp_
         h = pair0 + hp_ - b * p.H;
         rs = make_rsrc(plane_base<TV>(p, b, h), plane_span<TV>(p, h));
         plane_s0 = ((size_t)b * p.Q * p.H + h) * p.LP;
         loc = static_cast<const T *>(p.loc) + 2 * plane_s0;
-        proj3 = static_cast<const TS *>(p.loc) + 3 * plane_s0;
         attn = FUSED ? nullptr : static_cast<const T *>(p.attn) + plane_s0;
-        if constexpr (kSplitProj<PP>) {
-            off2 = static_cast<const TS *>(p.loc) + 2 * plane_s0;
-            lgt1 = static_cast<const TS *>(p.logits) + plane_s0;
-        }
+        MSDA_PROJ_REBASE(plane_s0)
     };
     const T *refp = FUSED ? static_cast<const T *>(p.ref) + (size_t)b * p.Q * ref_row_elems(p) : nullptr;
     A *w_aux = lds.s_aux + wave * UPW * scp * 3;  // FUSED: [slot] = a, [UPW*scp + slot] = ox, [2*UPW*scp + slot] = oy
     A *w_a = w_aux, *w_ox = w_aux + UPW * scp, *w_oy = w_aux + 2 * UPW * scp;
-    const A half_inv_P = (A)1 / (A)(2 * p.P);
+    MSDA_RULE_BACKWARD_SETUP;
     const int HLP = p.H * p.LP;
     const float inv_P = 1.0f / (float)p.P;
     const int nchan_chunks = (p.D + G * VEC - 1) / (G * VEC);
@@ -1338,7 +1226,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     if constexpr (FUSED) {
                         TS *gp = static_cast<TS *>(p.grad_loc) + 3 * u0;
                         for (int e = j; e < 3 * p.LP; e += G) gp[e] = SR::from_acc((A)0);
-                        const int npart = kLevelRef<PP> ? p.L * p.ref_dim : p.ref_dim;  // the unit's reference-point partials
+                        const int npart = ref_row_elems(p);  // the unit's reference-point partials
                         T *gr = static_cast<T *>(p.grad_attn) + ((size_t)(b * (size_t)p.Q + q) * p.H + h) * npart;
                         for (int e = j; e < npart; e += G) gr[e] = TR::from_acc((A)0);
                     } else {
@@ -1369,65 +1257,14 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     const int sl = f - imul24(fu, sc);
                     const int fq = wq0 + fu;
                     if (fq < q_end_ && unit_live(fu)) {
-                        [[maybe_unused]] int npts = p.P;  // per-level point counts: the count of the sample's own level
-                        int l;
-                        if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
-                        else l = div_small(sl, p.P, inv_P);
+                        MSDA_SAMPLE_LEVEL(sl, l, npts)  // (npts: the point count of the sample's own level)
                         const int sidx = imul24(fq, HLP) + sl;
                         A ox, oy, lg;
-                        if constexpr (kSplitProj<PP>) {  // (the three loads and phase 3's three stores are all that differs)
-                            ox = SR::to_acc(off2[2 * sidx]), oy = SR::to_acc(off2[2 * sidx + 1]);
-                            lg = SR::to_acc(lgt1[sidx]);
-                        } else {
-                            ox = SR::to_acc(proj3[3 * sidx]), oy = SR::to_acc(proj3[3 * sidx + 1]);
-                            lg = SR::to_acc(proj3[3 * sidx + 2]);
-                        }
+                        MSDA_PROJ_LOAD(sidx, ox, oy, lg)
                         const T *r = ref_of(p, refp, fq, l);
                         Rec4<A> w;
                         w.v[0] = lg;
-                        if constexpr (kHfBox<PP>) {
-                            // transformers' box rule, as the fused forward forms it; the offsets are then parked
-                            // SCALED by their level's s_l: phase 3 forms the point written for the grad_value passes
-                            // from the parked product by the same operations, and the box-size gradient is the
-                            // location gradient times it (times offset_scale)
-                            const A s = hfbox_scale<A>(p, l), os = (A)p.off_scale;
-                            ox = ox * s;
-                            oy = oy * s;
-                            w.v[1] = hfbox_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]), os);
-                            w.v[2] = hfbox_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]), os);
-                        } else if constexpr (kLevelRef<PP>) {
-                            // transformers' rule, as the fused forward forms it; the offsets are then parked DIVIDED
-                            // (by the level's width / height, or by P): the point written for the grad_value passes
-                            // is formed from the parked quotient by the same operations, and the box-size gradient
-                            // is the location gradient times it
-                            if (p.ref_dim == 2) {
-                                ox = ox / (A)tab->w[l];
-                                oy = oy / (A)tab->h[l];
-                                w.v[1] = TR::to_acc(r[0]) + ox;
-                                w.v[2] = TR::to_acc(r[1]) + oy;
-                            } else {
-                                ox = ox / (A)p.P;
-                                oy = oy / (A)p.P;
-                                w.v[1] = levelref_box_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]));
-                                w.v[2] = levelref_box_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]));
-                            }
-                        } else if (p.ref_dim == 2) {
-                            w.v[1] = TR::to_acc(r[0]) + ox / (A)tab->h[l];  // NB: (x, y) / img_shapes in its stored (h, w) order
-                            w.v[2] = TR::to_acc(r[1]) + oy / (A)tab->w[l];
-                        } else if constexpr (kRagged<PP>) {
-                            // the point as the fused forward forms it (multiply, divide, add: PyTorch's bits, so the
-                            // location gradient sees the same bilinear cell as the unfused composition); the offsets are
-                            // then parked SCALED by their level's 1 / (2 P_l): the box-size gradient below and the point
-                            // written for the grad_value passes need no level look-up of their own
-                            w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) / (A)(2 * npts);
-                            w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) / (A)(2 * npts);
-                            const A hinv = (A)1 / (A)(2 * npts);
-                            ox *= hinv;
-                            oy *= hinv;
-                        } else {
-                            w.v[1] = TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) * half_inv_P;
-                            w.v[2] = TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) * half_inv_P;
-                        }
+                        MSDA_RULE_BACKWARD(r, l, npts, ox, oy, w.v[1], w.v[2])  // (ox, oy: now what the rule parks of them)
                         w.v[3] = kRagged<PP> ? (A)l : (A)0;  // (per-level counts: phase 1 takes the level from here)
                         w_rec[imul24(fu, scp) + sl] = w;
                         w_ox[imul24(fu, scp) + sl] = ox;
@@ -1435,18 +1272,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     }
                 }
                 wave_lds_sync();
-                if (unit_ok) {
-                    A mx = -__builtin_huge_val();
-                    for (int sl = j; sl < sc; sl += G) mx = fmax_t(mx, w_rec[imul24(wunit, scp) + sl].v[0]);
-                    mx = group_max<G>(mx);
-                    A sum = (A)0;
-                    for (int sl = j; sl < sc; sl += G) sum += exp_t(w_rec[imul24(wunit, scp) + sl].v[0] - mx);
-                    sum = group_sum<G>(sum);
-                    if (j == 0) {
-                        w_rec[imul24(wunit, scp) + sc].v[0] = mx;
-                        w_rec[imul24(wunit, scp) + sc].v[1] = (A)1 / sum;
-                    }
-                }
+                if (unit_ok) MSDA_UNIT_SOFTMAX_STATS(w_rec, imul24(wunit, scp), sc, j)
                 wave_lds_sync();
             }
             // ---- phase 1 ----
@@ -1790,7 +1616,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                 // ---- phase 2b: per-unit sums for the prologue's chain rule, off the gather's critical path: the
                 // unit's lanes stride over its parked results, DPP-reduce ----
                 wave_lds_sync();
-                if constexpr (kLevelRef<PP>) {
+                if constexpr (kLevelRef<PP>) {  // (another REDUCTION, not another point rule: those are msda_prologue.hpp's)
                     // per-level reference points: the softmax's dot product as below; the reference-point gradient is a
                     // partial per LEVEL — lane j of the unit sums the P parked results of the levels j, j + G, ... in
                     // sample order (no exchange between lanes: L segment sums of P terms, off the gather's critical
@@ -1815,10 +1641,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                             T *gl = gr + imul24(l, p.ref_dim);
                             gl[0] = TR::from_acc(gx);
                             gl[1] = TR::from_acc(gy);
-                            if (p.ref_dim == 4) {  // (d point / d size = offset / P * 0.5; the parked offsets carry the 1 / P)
-                                gl[2] = TR::from_acc(gw * (A)0.5);
-                                gl[3] = TR::from_acc(gh * (A)0.5);
-                            }
+                            MSDA_RULE_STORE_SIZE_GRADS(gl, gw, gh)
                         }
                         if (j == 0) w_a[imul24(wunit, scp) + sc] = f_dot;  // the unit's padding slot
                     }
@@ -1847,14 +1670,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     T *gr = static_cast<T *>(p.grad_attn) + ((size_t)(b * (size_t)p.Q + q) * p.H + h) * p.ref_dim;
                     gr[0] = TR::from_acc(f_gx);
                     gr[1] = TR::from_acc(f_gy);
-                    if constexpr (kHfBox<PP>) {  // (the parked offsets carry their level's s_l: d point / d size = q * offset_scale)
-                        gr[2] = TR::from_acc(f_gw * (A)p.off_scale);
-                        gr[3] = TR::from_acc(f_gh * (A)p.off_scale);
-                    } else if (p.ref_dim == 4) {
-                        // (per-level point counts: the parked offsets already carry their level's 1 / (2 P_l))
-                        gr[2] = TR::from_acc(kRagged<PP> ? f_gw : f_gw * half_inv_P);
-                        gr[3] = TR::from_acc(kRagged<PP> ? f_gh : f_gh * half_inv_P);
-                    }
+                    MSDA_RULE_STORE_SIZE_GRADS(gr, f_gw, f_gh)  // (the rule's factor on sum(grad_point * parked offset))
                 }
                 }
             }
@@ -1872,37 +1688,12 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                     const Rec4<A> res = w_rec[imul24(fu, scp) + (sl - s0)];
                     if constexpr (FUSED) {
                         // chain rule through the prologue: softmax (logit), offset scaling (dx, dy)
-                        [[maybe_unused]] int npts = p.P;
-                        int l;
-                        if constexpr (kRagged<PP>) l = lvl_of(p, sl, npts);
-                        else l = div_small(sl, p.P, inv_P);
+                        MSDA_SAMPLE_LEVEL(sl, l, npts)  // (npts: the point count of the sample's own level)
                         const int rs_ = imul24(fu, scp) + (sl - s0);
                         const A a = w_a[rs_], dot = w_a[imul24(fu, scp) + sc];
                         const T *r = ref_of(p, refp, fq, l);
-                        A kx, ky;
-                        if constexpr (kHfBox<PP>) {  // d point / d offset = s_l * size * offset_scale
-                            const A s = hfbox_scale<A>(p, l), os = (A)p.off_scale;
-                            kx = s * TR::to_acc(r[2]) * os;
-                            ky = s * TR::to_acc(r[3]) * os;
-                        } else if constexpr (kLevelRef<PP>) {
-                            if (p.ref_dim == 2) {
-                                kx = (A)1 / (A)tab->w[l];
-                                ky = (A)1 / (A)tab->h[l];
-                            } else {
-                                kx = TR::to_acc(r[2]) * half_inv_P;
-                                ky = TR::to_acc(r[3]) * half_inv_P;
-                            }
-                        } else if (p.ref_dim == 2) {
-                            kx = (A)1 / (A)tab->h[l];
-                            ky = (A)1 / (A)tab->w[l];
-                        } else if constexpr (kRagged<PP>) {
-                            const A hinv = (A)1 / (A)(2 * npts);
-                            kx = TR::to_acc(r[2]) * hinv;
-                            ky = TR::to_acc(r[3]) * hinv;
-                        } else {
-                            kx = TR::to_acc(r[2]) * half_inv_P;
-                            ky = TR::to_acc(r[3]) * half_inv_P;
-                        }
+                        A kx, ky;  // d point / d offset
+                        MSDA_RULE_SLOPE(r, l, npts, kx, ky)
 #ifdef MSDA_DEV  // ablations: 4096 no parked points / weights, 8192 no grad_proj stores
                         const bool abl_mat = p.debug & 4096, abl_gp = p.debug & 8192;
 #else
@@ -1911,32 +1702,13 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         if (p.mat_loc != nullptr && !abl_mat) {
                             // the sampling point and attention weight this kernel derived, for the grad_value passes
                             // (stored here, at the end of the wave's life, where nothing waits behind the stores)
-                            const A ox = w_ox[rs_], oy = w_oy[rs_];
+                            const A ox = w_ox[rs_], oy = w_oy[rs_];  // (as phase 0 parked them)
                             // (parked in float by the 16-bit operators too — ParkType: grad_value samples where `out` and grad_proj do)
                             using MT = ParkType<T>;
                             using MR = Traits<MT>;
-                            Pack<MT, 2> m;
-                            if constexpr (kHfBox<PP>) {  // (ox, oy: the products phase 0 parked; the same operations)
-                                m.v[0] = MR::from_acc(hfbox_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2]), (A)p.off_scale));
-                                m.v[1] = MR::from_acc(hfbox_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3]), (A)p.off_scale));
-                            } else if constexpr (kLevelRef<PP>) {  // (ox, oy: the quotients phase 0 parked; the same operations)
-                                if (p.ref_dim == 2) {
-                                    m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox);
-                                    m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy);
-                                } else {
-                                    m.v[0] = MR::from_acc(levelref_box_point<A>(TR::to_acc(r[0]), ox, TR::to_acc(r[2])));
-                                    m.v[1] = MR::from_acc(levelref_box_point<A>(TR::to_acc(r[1]), oy, TR::to_acc(r[3])));
-                                }
-                            } else if (p.ref_dim == 2) {
-                                m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox / (A)tab->h[l]);
-                                m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy / (A)tab->w[l]);
-                            } else if constexpr (kRagged<PP>) {  // (ox, oy: scaled when they were parked)
-                                m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]));
-                                m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]));
-                            } else {
-                                m.v[0] = MR::from_acc(TR::to_acc(r[0]) + ox * TR::to_acc(r[2]) * half_inv_P);
-                                m.v[1] = MR::from_acc(TR::to_acc(r[1]) + oy * TR::to_acc(r[3]) * half_inv_P);
-                            }
+                            static_assert(std::is_same<MT, A>::value, "the parked point is stored in the arithmetic type");
+                            Pack<MT, 2> m;  // (the cell phase 0's point named)
+                            MSDA_RULE_REFORM(MR::from_acc, r, l, ox, oy, m.v[0], m.v[1])
                             *reinterpret_cast<Pack<MT, 2> *>(static_cast<MT *>(p.mat_loc) + 2 * (plane_s0 + sidx)) = m;
                             static_cast<MT *>(p.mat_attn)[plane_s0 + sidx] = MR::from_acc(a);
                         }
@@ -1944,22 +1716,7 @@ __global__ __launch_bounds__(BLK) void msda_bwd_sample_kernel(const PP p)
                         g0.v[0] = SR::from_acc(res.v[1] * kx);
                         g1.v[0] = SR::from_acc(res.v[2] * ky);
                         g2.v[0] = SR::from_acc(a * (res.v[0] - dot));
-                        if constexpr (kSplitProj<PP>) {  // grad_offsets [.., 2] and, apart from it, grad_logits
-                            TS *go = static_cast<TS *>(p.grad_loc) + 2 * (plane_s0 + sidx);
-                            TS *gl = static_cast<TS *>(p.grad_logits) + (plane_s0 + sidx);
-                            if (!abl_gp) {
-                                store_stream(go, g0);
-                                store_stream(go + 1, g1);
-                                store_stream(gl, g2);
-                            }
-                        } else {
-                        TS *gp = static_cast<TS *>(p.grad_loc) + 3 * (plane_s0 + sidx);
-                        if (!abl_gp) {
-                            store_stream(gp, g0);
-                            store_stream(gp + 1, g1);
-                            store_stream(gp + 2, g2);
-                        }
-                        }
+                        MSDA_PROJ_STORE(plane_s0 + sidx, !abl_gp, g0, g1, g2)
                     } else {
                         Pack<T, 1> ga;
                         ga.v[0] = TR::from_acc(res.v[0]);
