@@ -840,6 +840,61 @@ MSDA_API int msda_get_option(const char *key);
  * Unknown key: MSDA_ERR_BAD_ARG. */
 MSDA_API int msda_last_launch_info(const char *key);
 
+/* ---- key-aware deformable attention (additions within ABI 12, found by symbol: msda_keyaware_bwd_workspace_bytes) ----
+ * The weights of a (b, q, head) unit's S = L * P samples are a softmax over what was SAMPLED, not an input:
+ *   K_s = bilinear(key_h, p_s)   V_s = bilinear(value_h, p_s)   z_s = scale * <query[b, q, h, :], K_s>
+ *   a = softmax_s(z)             out[b, q, h, :] = sum_s a_s * V_s
+ * query [B, Q, H, D]; key, value [B, I, H, D] of one shape and ONE row stride (value_row_stride applies to both; 0: dense);
+ * sampling_points [B, Q, H, L, P, 2]; img_shapes [L, 2] int64 on the device.  One storage type for every tensor (f32, f64,
+ * bf16, f16), arithmetic in the accumulate type; `scale` is cast once to that type.  NOTE the order of the sizes: B, I, H,
+ * D, L, P, Q.  Padding masks compose: the caller zero-fills both pyramids.
+ *
+ * msda_keyaware_fwd_<dtype> writes out [B, Q, H, D] and attn [B, Q, H, L, P] (the softmaxed weights: the backward reads
+ * them, a caller may return them).  Both fully overwritten, no memset, no host synchronisation, graph-capturable.  Checks in
+ * msda_fwd_<dtype>'s order: an empty `out` returns 0; sizes, padding mode, L, the size limits of DESIGN.md 2; `out` / `attn`;
+ * S = 0 or I = 0 stores zeros; the inputs; alignment (every buffer on its element size, sampling_points on two);
+ * value_row_stride.  A head row must fit one channel chunk (D <= 64 lanes x 16 bytes, or D <= 64 when D is no multiple of 16
+ * bytes or a row buffer is not 16-byte aligned): MSDA_ERR_UNSUPPORTED beyond.
+ *
+ * msda_keyaware_bwd_<dtype>: from grad_out [B, Q, H, D] and the forward's attn to
+ *   grad_query [B, Q, H, D] and grad_loc [B, Q, H, L, P, 2]  — both given or both NULL (MSDA_ERR_BAD_ARG otherwise);
+ *   grad_key, grad_value [B, I, H, D], written dense        — each may be NULL on its own (a frozen pyramid).
+ * With dz_s = a_s (<grad_out, V_s> - sum_t a_t <grad_out, V_t>): grad_query = scale sum_s dz_s K_s; grad_loc_s = a_s
+ * d<grad_out, V_s>/dp + scale dz_s d<query, K_s>/dp, un-normalised as msda_bwd's grad_loc; grad_value is msda_bwd's grad_value
+ * for weights a and rows grad_out, grad_key the same for weights scale * dz and rows query — the same route (single-launch
+ * kernel or sorted pipeline, max_level_cells as there), run once per pyramid in the same workspace.  No atomics on
+ * floating-point data; reproducible as msda_bwd's outputs are.  The workspace (256-byte aligned, NULL / 0 allowed when both
+ * pyramids are frozen) holds scale * dz [B, Q, H, L, P] — float32 for the 16-bit operators, which also park the points and
+ * weights in float32 behind it and run the float32 grad_value passes on their 16-bit rows — and then what a grad_value-only
+ * msda_bwd call needs.  A call for pyramid gradients that has no route is refused before its first kernel.
+ *
+ * msda_keyaware_bwd_workspace_bytes: that size for elements of elem_size bytes (flags: MSDA_WS_PASSES(n) only); 0 where the
+ * call would be refused or no pyramid-gradient route exists.  msda_keyaware_trip_samples: samples of a unit the forward
+ * parks in LDS per trip on its 16-byte path (a unit of more samples carries its softmax state across trips); 0 for
+ * arguments without a kernel.  msda_last_launch_info: "fwd_variant" 5 and "sample_variant" 4 are this family's kernels;
+ * "fwd_trips" / "sample_trips", the instantiation keys and "value_path" (the route of the pyramid gradients) as elsewhere. */
+#define MSDA_KEYAWARE(SUF)                                                                               \
+    MSDA_API int msda_keyaware_fwd_##SUF(const void *query, const void *key, const void *value,      \
+        const int64_t *img_shapes, const void *sampling_points, void *out, void *attn, int64_t B,     \
+        int64_t I, int64_t H, int64_t D, int64_t L, int64_t P, int64_t Q, int padding_mode,           \
+        int align_corners, double scale, int64_t value_row_stride, void *stream);                     \
+    MSDA_API int msda_keyaware_bwd_##SUF(const void *grad_out, const void *query, const void *key,   \
+        const void *value, const int64_t *img_shapes, const void *sampling_points, const void *attn,  \
+        void *grad_query, void *grad_key, void *grad_value, void *grad_loc, int64_t B, int64_t I,     \
+        int64_t H, int64_t D, int64_t L, int64_t P, int64_t Q, int padding_mode, int align_corners,   \
+        double scale, int64_t max_level_cells, int64_t value_row_stride, void *workspace,             \
+        int64_t workspace_bytes, void *stream);
+MSDA_KEYAWARE(f32)
+MSDA_KEYAWARE(f16)
+MSDA_KEYAWARE(bf16)
+MSDA_KEYAWARE(f64)
+#undef MSDA_KEYAWARE
+#define MSDA_KEYAWARE_QUERY(WHAT, ...) MSDA_API int64_t msda_keyaware_##WHAT(__VA_ARGS__);
+MSDA_KEYAWARE_QUERY(bwd_workspace_bytes, int64_t B, int64_t I, int64_t H, int64_t D, int64_t L, int64_t P, int64_t Q,
+                    int elem_size, int flags)
+MSDA_KEYAWARE_QUERY(trip_samples, int64_t D, int elem_size)
+#undef MSDA_KEYAWARE_QUERY
+
 #ifdef __cplusplus
 }
 #endif

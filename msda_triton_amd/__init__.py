@@ -14,6 +14,7 @@ from .functional import (  # noqa: F401
     multiscale_deformable_attention,
     native_multiscale_deformable_attention,
 )
+from .key_aware import KeyAwareDeformableAttention, key_aware_deformable_attention  # noqa: F401
 from .module import MultiscaleDeformableAttention  # noqa: F401
 
 __version__ = "0.1.0"
@@ -25,4 +26,6 @@ __all__ = [
     "native_multiscale_deformable_attention",
     "msda_hip_fwd",
     "msda_hip_bwd",
+    "key_aware_deformable_attention",
+    "KeyAwareDeformableAttention",
 ]

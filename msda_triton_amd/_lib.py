@@ -99,6 +99,22 @@ MODULE_DISCRETE_SYMBOLS = tuple(_pair("fused_discrete") + ["msda_bwd_fused_discr
 LEVELREF_SPLIT_SYMBOLS = tuple(_pair("fused_levelref_split"))
 
 
+# key-aware attention (has_keyaware).  Not a _FAMILIES row: its lists lead with query / key, order the sizes B, I, H, D,
+# L, P, Q and carry the score scale as a double (include/msda_hip.h) — explicit argtypes below.
+KEYAWARE_SUFFIXES = ("f32", "f16", "bf16", "f64")
+KEYAWARE_SYMBOLS = tuple([f"msda_keyaware_{d}_{s}" for d in ("fwd", "bwd") for s in KEYAWARE_SUFFIXES]
+                         + ["msda_keyaware_bwd_workspace_bytes", "msda_keyaware_trip_samples"])
+
+
+def _keyaware_signatures():
+    modes = [_I64] * 7 + [_CI, _CI, _CD]  # B, I, H, D, L, P, Q, padding_mode, align_corners, scale
+    for suf in KEYAWARE_SUFFIXES:
+        yield f"msda_keyaware_fwd_{suf}", _CI, [_VP] * 7 + modes + [_I64, _VP]
+        yield f"msda_keyaware_bwd_{suf}", _CI, [_VP] * 11 + modes + [_I64, _I64, _VP, _I64, _VP]
+    yield "msda_keyaware_bwd_workspace_bytes", _I64, [_I64] * 7 + [_CI, _CI]
+    yield "msda_keyaware_trip_samples", _I64, [_I64, _CI]
+
+
 def _signatures(lib):
     """(symbol, restype, argtypes) of every kernel entry point and size query the loaded library has."""
     for infix, probe, suffixes, fwd_ptrs, bwd_ptrs, last_dim, extras, mode, queries in _FAMILIES:
@@ -116,6 +132,8 @@ def _signatures(lib):
             yield f"msda_bwd_{stem}workspace_bytes", _I64, dims + [_CI, _CI, _I64, _CI]
         if "supported" in queries:  # (dims, elem_size)
             yield f"msda_bwd_{stem}supported", _CI, dims + [_CI]
+    if hasattr(lib, "msda_keyaware_bwd_workspace_bytes"):
+        yield from _keyaware_signatures()
 
 
 def _has(infix: str) -> bool:
@@ -231,6 +249,12 @@ def has_levelref_split() -> bool:
     (msda_fwd_fused_levelref_split_<dtype> ..., additions within ABI 12, found by symbol)?  Without them the caller
     interleaves offsets and logits and takes the pair it has."""
     return _has("fused_levelref_split")
+
+
+def has_keyaware() -> bool:
+    """Does the loaded library have the key-aware attention kernels (msda_keyaware_fwd_<dtype> ..., additions within ABI 12,
+    found by symbol)?  Without them ``key_aware_deformable_attention`` runs its PyTorch formulation."""
+    return hasattr(load(), "msda_keyaware_bwd_workspace_bytes")
 
 
 def has_value_mask() -> bool:

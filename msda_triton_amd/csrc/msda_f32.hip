@@ -183,6 +183,26 @@ extern "C" int64_t msda_bwd_fused_discrete_workspace_bytes(int64_t B, int64_t I,
                                                          max_level_cells, flags);
 }
 
+// key-aware attention (include/msda_hip.h): the head of the workspace — scale * dz, and the 16-bit operators' float points and
+// weights — then what a grad_value-only call of the plain operator needs (the 16-bit operators': of the float pipeline)
+extern "C" int64_t msda_keyaware_bwd_workspace_bytes(int64_t B, int64_t I, int64_t H, int64_t D, int64_t L, int64_t P,
+                                                     int64_t Q, int elem_size, int flags)
+{
+    if (msda::any_negative(B, I, H, D, Q, L, P) || (elem_size != 2 && elem_size != 4 && elem_size != 8)) return 0;
+    const msda::Dims d{B, I, H, D, Q, L, P};
+    const int park = elem_size == 2 ? 4 : elem_size;
+    if (msda::common_limits_exceeded(d, elem_size) || msda::common_limits_exceeded(d, park) || !msda::bwd_supported(d, park)) return 0;
+    if (msda::nothing_sampled(d)) return 0;
+    return (int64_t)msda::keyaware_head((size_t)(B * Q * H * msda::samples(d)), (size_t)elem_size).bytes +
+           msda::sorted_ws_bytes(d, park, false, 0, msda::passes_of(flags));
+}
+
+extern "C" int64_t msda_keyaware_trip_samples(int64_t D, int elem_size)
+{
+    if (D <= 0 || (elem_size != 2 && elem_size != 4 && elem_size != 8)) return 0;
+    return msda::keyaware_trip_samples(D, elem_size);
+}
+
 extern "C" int msda_bwd_discrete_supported(int64_t B, int64_t I, int64_t H, int64_t D, int64_t Q, int64_t L,
                                            const int32_t *points_per_level, int elem_size)
 {

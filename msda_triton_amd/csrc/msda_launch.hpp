@@ -12,6 +12,7 @@
 #include "msda_value_small.hpp"
 #include "msda_discrete.hpp"
 #include "msda_hfbox_discrete.hpp"
+#include "msda_keyaware.hpp"
 #include "msda_options.hpp"
 
 namespace msda {
@@ -1081,6 +1082,11 @@ struct Call {
     // gradient, and the logits [..] and theirs sit here
     const void *logits = nullptr;
     void *grad_logits = nullptr;
+    // key-aware attention (msda_keyaware_*_<dtype>): the query rows, the key pyramid and the score scale; `attn_out` the forward's
+    // second output (the backward reads it back through `attn`), `grad_query` / `grad_key` next to grad_value and grad_loc
+    const void *query = nullptr, *key = nullptr;
+    void *attn_out = nullptr, *grad_query = nullptr, *grad_key = nullptr;
+    double scale = 0.0;
     int64_t B = 0, I = 0, H = 0, D = 0, Q = 0, L = 0;
     int64_t P = 0, S = 0;  // per-level counts: their maximum and sum (take_counts); else the uniform P and 0
     const int32_t *points_per_level = nullptr;  // host, L counts
@@ -1622,6 +1628,195 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
     return rc;
 }
 
+// ---- key-aware attention: msda_keyaware_{fwd,bwd}_<dtype>, kernels in msda_keyaware.hpp ----
+// MODE 0: the forward, 1: the sample half of the backward.  The geometry is launch_discrete's — a workgroup per (plane,
+// chunk of kBlock / G queries) — and the records are plan_gather's (the backward's with its three extra scalars per slot).
+template <typename T, int VEC, int G, int MODE> inline int launch_keyaware(KeyAwareParams &p, hipStream_t stream)
+{
+    using A = typename Traits<T>::acc;
+    constexpr int NU = kBlock / G;
+    size_t lds;
+    plan_gather(NU, p.LP, sizeof(A), p.sc, lds, MODE == 1);
+    p.nqc = (p.Q + NU - 1) / NU;
+    dim3 grid;
+    if (!plane_grid(p, p.B * p.H, p.nqc, grid)) {
+        set_error("grid too large");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    static std::atomic<uint64_t> big_lds_done{0};
+    if (MODE == 0) {
+        note_launch(0, 5);
+        note_launch(1, 0);
+        note_launch(2, 1);
+        note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, G, p.D);
+        note_trips(23, p.LP, p.sc);
+        const ProfileScope prof("msda_keyaware_fwd_kernel", stream);
+        allow_big_lds(msda_keyaware_fwd_kernel<T, VEC, G>, big_lds_done);
+        hipLaunchKernelGGL((msda_keyaware_fwd_kernel<T, VEC, G>), grid, dim3(kBlock), lds, stream, p);
+    } else {
+        note_launch(4, 4);
+        note_launch(5, 0);
+        note_instance(11, VEC, G, p.D);
+        note_trips(24, p.LP, p.sc);
+        const ProfileScope prof("msda_keyaware_bwd_sample_kernel", stream);
+        allow_big_lds(msda_keyaware_bwd_sample_kernel<T, VEC, G>, big_lds_done);
+        hipLaunchKernelGGL((msda_keyaware_bwd_sample_kernel<T, VEC, G>), grid, dim3(kBlock), lds, stream, p);
+    }
+    return (int)hipGetLastError();
+}
+template <typename T, int VEC, int MODE> inline int dispatch_keyaware_group(KeyAwareParams &p, hipStream_t stream)
+{
+    const int lanes = (p.D + VEC - 1) / VEC;
+    if (lanes > kWave) {  // (the head rows of query and grad_out stay in registers: one channel chunk)
+        set_error("key-aware attention serves head rows of at most %d channels here, got D = %d", kWave * VEC, p.D);
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    switch (pick_group(lanes)) {
+    case 4: return launch_keyaware<T, VEC, 4, MODE>(p, stream);
+    case 8: return launch_keyaware<T, VEC, 8, MODE>(p, stream);
+    case 16: return launch_keyaware<T, VEC, 16, MODE>(p, stream);
+    case 32: return launch_keyaware<T, VEC, 32, MODE>(p, stream);
+    default: return launch_keyaware<T, VEC, 64, MODE>(p, stream);
+    }
+}
+template <typename T, int MODE> inline int dispatch_keyaware(KeyAwareParams &p, bool vec_ok, hipStream_t stream)
+{
+    constexpr int VECF = 16 / sizeof(T);
+    if (vec_ok && (p.D % VECF) == 0) return dispatch_keyaware_group<T, VECF, MODE>(p, stream);
+    return dispatch_keyaware_group<T, 1, MODE>(p, stream);
+}
+// samples of a unit the forward parks per trip on its 16-byte path (msda_keyaware_trip_samples)
+inline int keyaware_trip_samples(int64_t D, int elem_size)
+{
+    const int vec = 16 / elem_size;
+    const int lanes = (int)((D % vec) == 0 ? D / vec : D);
+    int sc;
+    size_t lds;
+    plan_gather(kBlock / pick_group(lanes), 1 << 22, elem_size == 8 ? 8 : 4, sc, lds, false);
+    return sc;
+}
+
+// The head of the backward's workspace: scale * dz [B, Q, H, S] in ParkType, then — the 16-bit operators — the points
+// [B, Q, H, S, 2] and weights [B, Q, H, S] once more in float32; each part rounded up to 256 bytes.
+struct KeyAwareHead {
+    size_t off_loc, off_attn, bytes;
+};
+inline KeyAwareHead keyaware_head(size_t ns, size_t elem)
+{
+    const size_t park = elem == 2 ? 4 : elem;
+    KeyAwareHead hd;
+    hd.off_loc = align_up(ns * park, 256);
+    hd.off_attn = hd.off_loc + (elem == 2 ? align_up(ns * 2 * park, 256) : 0);
+    hd.bytes = hd.off_attn + (elem == 2 ? align_up(ns * park, 256) : 0);
+    return hd;
+}
+
+template <typename T> int run_keyaware_fwd(const Call &c)
+{
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    const size_t out_bytes = (size_t)(d.B * d.Q * d.H * d.D) * sizeof(T);
+    const size_t attn_bytes = (size_t)(d.B * d.Q * d.H * samples(d)) * sizeof(T);
+    if (out_bytes == 0) return 0;  // nothing to produce
+    int rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc == 0) rc = require_buffers({c.out});
+    if (rc == 0 && attn_bytes) rc = require_buffers({c.attn_out});
+    if (rc) return rc;
+    if (samples(d) == 0 || d.I == 0) return zero_outputs({{c.out, out_bytes}, {c.attn_out, attn_bytes}}, stream);  // empty sum
+    if ((rc = require_buffers({c.query, c.key, c.value, c.shapes, c.loc})) != 0) return rc;
+    if ((rc = check_aligned({{c.query, sizeof(T)}, {c.key, sizeof(T)}, {c.value, sizeof(T)}, {c.out, sizeof(T)}, {c.attn_out, sizeof(T)},
+                             {c.loc, 2 * sizeof(T)}, {c.shapes, 8}})) != 0)
+        return rc;
+    KeyAwareParams p{};
+    if ((rc = fill_kernarg<T>(p, c, d)) != 0) return rc;
+    p.query = c.query;
+    p.key = c.key;
+    p.scale = c.scale;
+    p.mat_attn = c.attn_out;
+    const bool vec_ok = rows_vec_ok(p, c.out) && aligned_to(c.key, 16) && aligned_to(c.query, 16);
+    return launched(dispatch_keyaware<T, 0>(p, vec_ok, stream), "key-aware forward");
+}
+
+// grad_query and grad_loc come from the sample kernel (both or neither); grad_value and grad_key from the grad_value route
+// run_value picks, run twice in the same workspace behind the head: weights `attn` on the rows of grad_out, then weights
+// scale * dz on the rows of query.  Either pyramid may be frozen; with both frozen only the sample kernel runs.
+template <typename T> int run_keyaware_bwd(const Call &c)
+{
+    using MT = ParkType<T>;
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    int rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc) return rc;
+    const size_t ns = (size_t)(d.B * d.Q * d.H * samples(d));
+    const size_t pyramid_bytes = (size_t)(d.B * d.I * d.H * d.D) * sizeof(T), rows_bytes = (size_t)(d.B * d.Q * d.H * d.D) * sizeof(T);
+    if (nothing_sampled(d))
+        return zero_outputs({{c.grad_value, pyramid_bytes}, {c.grad_key, pyramid_bytes}, {c.grad_query, rows_bytes}, {c.grad_loc, ns * 2 * sizeof(T)}}, stream);
+    const bool want_pyramid = c.grad_value != nullptr || c.grad_key != nullptr;
+    const bool want_sample = c.grad_query != nullptr || c.grad_loc != nullptr;
+    if (want_sample && (c.grad_query == nullptr || c.grad_loc == nullptr)) {
+        set_error("grad_query and grad_loc must be both null or both non-null");
+        return MSDA_ERR_BAD_ARG;
+    }
+    if ((rc = require_buffers({c.grad_out, c.query, c.key, c.value, c.shapes, c.loc, c.attn})) != 0) return rc;
+    if ((rc = check_aligned({{c.grad_out, sizeof(T)}, {c.query, sizeof(T)}, {c.key, sizeof(T)}, {c.value, sizeof(T)}, {c.loc, 2 * sizeof(T)},
+                             {c.attn, sizeof(T)}, {c.grad_query, sizeof(T)}, {c.grad_key, sizeof(T)}, {c.grad_value, sizeof(T)},
+                             {c.grad_loc, 2 * sizeof(T)}, {c.shapes, 8}})) != 0)
+        return rc;
+    // (the 16-bit operators' pyramid gradients are the float pipeline on 16-bit rows: its limits, as the workspace query says)
+    if (want_pyramid && sizeof(MT) != sizeof(T) && common_limits_exceeded(d, (int64_t)sizeof(MT))) {
+        set_error("tensor too large for the key-aware backward's float32 grad_value passes");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    const KeyAwareHead hd = keyaware_head(ns, sizeof(T));
+    if (want_pyramid && (c.workspace == nullptr || !aligned_to(c.workspace, 256) || (uint64_t)c.workspace_bytes < hd.bytes)) {
+        set_error("the key-aware backward needs a 256-byte aligned workspace of msda_keyaware_bwd_workspace_bytes(...) bytes "
+                  "(at least %zu) for grad_key / grad_value", hd.bytes);
+        return MSDA_ERR_BAD_ARG;
+    }
+    KeyAwareParams p{};
+    if ((rc = fill_kernarg<T>(p, c, d)) != 0) return rc;
+    p.query = c.query;
+    p.key = c.key;
+    p.scale = c.scale;
+    p.out = c.grad_query;
+    p.grad_attn = nullptr;
+    unsigned char *ws = static_cast<unsigned char *>(c.workspace);
+    unsigned char *rest = want_pyramid ? ws + hd.bytes : nullptr;
+    const int64_t rest_bytes = want_pyramid ? c.workspace_bytes - (int64_t)hd.bytes : 0;
+    if (want_pyramid) {
+        p.mat_attn = ws;
+        if (sizeof(MT) != sizeof(T)) {
+            p.mat_loc = ws + hd.off_loc;
+            p.grad_attn = ws + hd.off_attn;
+        }
+        // a call for pyramid gradients it cannot finish is refused before its first kernel
+        if ((rc = value_route_status<MT, T>(p, d, rest, rest_bytes)) != 0) return rc;
+    }
+    // (the sample kernel also derives scale * dz and parks the 16-bit operators' floats: only an fp32 / fp64 call for
+    // grad_value alone does without it)
+    if (want_sample || c.grad_key != nullptr || (want_pyramid && sizeof(MT) != sizeof(T))) {
+        const bool vec_ok = rows_vec_ok(p, c.grad_out) && aligned_to(c.key, 16) && aligned_to(c.query, 16) &&
+                            (c.grad_query == nullptr || aligned_to(c.grad_query, 16));
+        if ((rc = launched(dispatch_keyaware<T, 1>(p, vec_ok, stream), "key-aware backward (grad_query/grad_loc)")) != 0) return rc;
+    }
+    auto pyramid = [&](const void *weights, const void *rows, void *grad) -> int {
+        Params pv = p;  // (the plain operator's kernarg: the pipelines are msda_bwd's own instantiations)
+        pv.out = nullptr;
+        pv.grad_loc = pv.grad_attn = pv.mat_loc = pv.mat_attn = nullptr;
+        pv.loc = sizeof(MT) != sizeof(T) ? ws + hd.off_loc : c.loc;
+        pv.attn = weights;
+        pv.grad_out = rows;
+        pv.grad_value = grad;
+        if constexpr (sizeof(MT) != sizeof(T)) return run_value_float<T, T>(pv, d, rest, rest_bytes, stream);
+        else return run_value<T, T, T>(pv, d, rest, rest_bytes, stream);
+    };
+    if (c.grad_value != nullptr && (rc = pyramid(sizeof(MT) != sizeof(T) ? (const void *)(ws + hd.off_attn) : c.attn, c.grad_out, c.grad_value)) != 0)
+        return rc;
+    if (c.grad_key != nullptr && (rc = pyramid(ws, c.query, c.grad_key)) != 0) return rc;
+    return 0;
+}
+
 }  // namespace msda
 
 // ---- the extern "C" entry points (include/msda_hip.h has the argument lists): each fills a Call by name — the groups
@@ -2094,5 +2289,33 @@ template <typename T, typename TV = T, typename TS = T, typename PP = Params> in
         return msda::run_bwd_fused<T, TV, TS, msda::RaggedMaskedParams>(c);                                      \
     }
 
+// key-aware attention: msda_keyaware_{fwd,bwd}_<dtype> — one storage type for every tensor
+#define MSDA_TAKE_KEYAWARE                                                                                       \
+    msda::Call c; c.query = query; c.key = key; c.value = value; c.shapes = img_shapes; c.loc = sampling_points; \
+    c.P = P; c.scale = scale; MSDA_TAKE_SIZES MSDA_TAKE_MODES
+#define MSDA_DEFINE_KEYAWARE_ENTRY_POINTS(SUF, T)                                                                \
+    extern "C" int msda_keyaware_fwd_##SUF(const void *query, const void *key, const void *value,               \
+                                           const int64_t *img_shapes, const void *sampling_points, void *out,    \
+                                           void *attn, int64_t B, int64_t I, int64_t H, int64_t D, int64_t L,    \
+                                           int64_t P, int64_t Q, int padding_mode, int align_corners,            \
+                                           double scale, int64_t value_row_stride, void *stream)                 \
+    {                                                                                                            \
+        MSDA_TAKE_KEYAWARE c.out = out; c.attn_out = attn;                                                       \
+        return msda::run_keyaware_fwd<T>(c);                                                                     \
+    }                                                                                                            \
+    extern "C" int msda_keyaware_bwd_##SUF(const void *grad_out, const void *query, const void *key,            \
+                                           const void *value, const int64_t *img_shapes,                         \
+                                           const void *sampling_points, const void *attn, void *grad_query,      \
+                                           void *grad_key, void *grad_value, void *grad_loc, int64_t B,          \
+                                           int64_t I, int64_t H, int64_t D, int64_t L, int64_t P, int64_t Q,     \
+                                           int padding_mode, int align_corners, double scale,                    \
+                                           int64_t max_level_cells, int64_t value_row_stride, void *workspace,   \
+                                           int64_t workspace_bytes, void *stream)                                \
+    {                                                                                                            \
+        MSDA_TAKE_KEYAWARE MSDA_TAKE_WORKSPACE c.grad_out = grad_out; c.attn = attn; c.grad_query = grad_query;  \
+        c.grad_key = grad_key; c.grad_value = grad_value; c.grad_loc = grad_loc;                                 \
+        return msda::run_keyaware_bwd<T>(c);                                                                     \
+    }
+
 // one storage type for every tensor
-#define MSDA_DEFINE_ENTRY_POINTS(SUF, T) MSDA_DEFINE_ENTRY_POINTS2(SUF, T, T)
+#define MSDA_DEFINE_ENTRY_POINTS(SUF, T) MSDA_DEFINE_ENTRY_POINTS2(SUF, T, T) MSDA_DEFINE_KEYAWARE_ENTRY_POINTS(SUF, T)

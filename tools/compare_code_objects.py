@@ -9,7 +9,7 @@ branch-target comments and the padding behind a symbol's last instruction are dr
 symbol by symbol.  Prints the number of identical / different / missing / added symbols and, for every different one,
 both sides' VGPR / SGPR / spill / scratch / LDS figures from the metadata notes and the instruction counts.
 Exit status 0 only when no symbol is different or missing: a refactor of device code that claims "same machine code"
-is checked with one command.  Limitation: the padding is recognised by name (trailing s_nop / s_code_end lines), so two
+is checked with one command.  Limitation: the padding is recognised by name (trailing s_nop / s_code_end / "..." lines), so two
 symbols that differ ONLY in such trailing instructions compare equal.
 """
 import argparse
@@ -24,7 +24,7 @@ import tempfile
 LLVM = os.environ.get("MSDA_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 NOTE_KEYS = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
              "group_segment_fixed_size")
-PADDING = ("s_nop", "s_code_end")
+PADDING = ("s_nop", "s_code_end", "...")  # ("...": llvm-objdump's mark for a run of zero bytes in front of the next symbol)
 
 
 def code_objects(lib, workdir):
