@@ -895,6 +895,70 @@ MSDA_KEYAWARE_QUERY(bwd_workspace_bytes, int64_t B, int64_t I, int64_t H, int64_
 MSDA_KEYAWARE_QUERY(trip_samples, int64_t D, int elem_size)
 #undef MSDA_KEYAWARE_QUERY
 
+/* ---- the deformable convolution core of DCNv3 / DCNv4 (additions within ABI 12, found by symbol: msda_dcn_bwd_workspace_bytes) ----
+ * input [N, Hi, Wi, G, D] channels-last; offsets, logical shape [N, Ho, Wo, G, K, 2] in (x, y) order; mask [N, Ho, Wo, G, K];
+ * K = kh * kw; Ho = (Hi + 2 ph - (dh (kh - 1) + 1)) / sh + 1, Wo likewise.  Tap k = i * kh + j, i in [0, kw) the window's
+ * COLUMN (the outer index), j in [0, kh) its row.  With cx = (dw (kw - 1)) / 2, cy = (dh (kh - 1)) / 2, in pixel coordinates
+ * whose integers are pixel centres:
+ *   lx = wo sw - pw + cx + offset_scale (i dw - cx + ox_k)      ly = ho sh - ph + cy + offset_scale (j dh - cy + oy_k)
+ *   m = softmax_k(mask) if `softmax` else mask       out[n, ho, wo, g, :] = sum_k m_k bilinear(input[n, :, :, g, :], lx, ly)
+ * a bilinear corner outside the image contributes zero — msda_fwd's point ((lx + 0.5) / Wi, (ly + 0.5) / Hi) under
+ * MSDA_PADDING_ZEROS, align_corners = 0.  One storage type for every tensor (f32, f64, bf16, f16), arithmetic and the softmax
+ * in the accumulate type.
+ *
+ * Offsets and mask are read IN PLACE through strides in elements: element (n, ho, wo, g, k) of the offsets is the pair at
+ * offset[((n Ho + ho) Wo + wo) * offset_row_stride + g * offset_group_stride + 2 k], of the mask the scalar at
+ * mask[(...) * mask_row_stride + g * mask_group_stride + k].  Two dense tensors: (G * 2K, 2K) and (G * K, K).  DCNv4's packed
+ * offset_mask [N, Ho, Wo, C] — per group 2K offsets, then K mask values; C = G * 3K rounded up to a multiple of 8 — is
+ * offset = base, mask = base + 2K with (C, 3K) for both.  Group strides below 2K / K and negative row strides are
+ * MSDA_ERR_BAD_ARG.  The gradients are written through the same strides; elements between the groups' data (the packed
+ * layout's tail) are not written.
+ *
+ * msda_dcn_fwd_<dtype> writes out [N, Ho, Wo, G, D], fully, no memset, no host synchronisation, graph-capturable.  Checks in
+ * msda_fwd_<dtype>'s order: an empty `out` returns 0; sizes and the size limits of DESIGN.md 2 with B = N, I = Hi Wi, H = G,
+ * Q = Ho Wo, L = 1, P = K (Hi, Wi, Ho, Wo < 2^24: 24-bit pixel indices); kernel, strides and dilations >= 1, paddings >= 0,
+ * Ho x Wo must be the formula's; `out`; an empty input stores zeros; the inputs; alignment (every buffer on its element
+ * size).  MSDA_ERR_UNSUPPORTED where no kernel exists: a group of more than 64 lanes x 16 bytes (64 channels when D is no
+ * multiple of 16 bytes or a row buffer is not 16-byte aligned), or K so large that the records of a workgroup's units
+ * (all K samples of a unit are parked in LDS together) exceed it — 7 x 7 kernels fit in every type.
+ *
+ * msda_dcn_bwd_<dtype>: from grad_out [N, Ho, Wo, G, D] to
+ *   grad_offset = offset_scale * d out / d (lx, ly) and grad_mask (through the softmax when it is on) — both given or both
+ *     NULL (MSDA_ERR_BAD_ARG otherwise); every element has one writer, no atomics;
+ *   grad_input [N, Hi, Wi, G, D], written dense — NULL for a frozen input, which skips the pipeline and needs no workspace.
+ * grad_input is msda_bwd's grad_value for one level, the post-softmax mask as weights and the rows of grad_out: the same
+ * route (single-launch kernel or sorted pipeline, max_level_cells as there; I < 2^22), reproducible as msda_bwd's outputs
+ * are.  The sample kernel parks every sample's normalised point and weight at the head of the workspace (float32 for the
+ * 16-bit operators, which run the float32 grad_value passes on their 16-bit rows) — the ONE value from which the forward,
+ * the sample kernel and the pipeline derive a sample's bilinear cell, so the three agree on it bit for bit.  The workspace
+ * is 256-byte aligned and of msda_dcn_bwd_workspace_bytes(...) bytes (flags: MSDA_WS_PASSES(n) only; 0 where the call would
+ * be refused).  A call for grad_input that has no route is refused before its first kernel.  An empty input or D = 0 with
+ * units to serve: MSDA_ERR_UNSUPPORTED.
+ *
+ * Option "dcn_window" (default 1): a workgroup serves an 8 x 8 tile of output pixels and a block of groups, and stages the
+ * input window under the tile in LDS when it fits; 0: every corner through the buffer descriptor.  The results are the same
+ * bits either way.  msda_last_launch_info: "fwd_variant" 6 and "sample_variant" 5 are this family's kernels; "dcn_window" 1
+ * when the last of them staged the window; the instantiation keys and "value_path" (the route of grad_input) as elsewhere. */
+#define MSDA_DCN_GEOMETRY                                                                                \
+    int64_t N, int64_t Hi, int64_t Wi, int64_t G, int64_t D, int64_t Ho, int64_t Wo, int kh, int kw,     \
+    int sh, int sw, int ph, int pw, int dh, int dw, double offset_scale, int softmax,                    \
+    int64_t offset_row_stride, int64_t offset_group_stride, int64_t mask_row_stride,                     \
+    int64_t mask_group_stride
+#define MSDA_DCN(SUF)                                                                                    \
+    MSDA_API int msda_dcn_fwd_##SUF(const void *input, const void *offset, const void *mask, void *out,  \
+        MSDA_DCN_GEOMETRY, void *stream);                                                                \
+    MSDA_API int msda_dcn_bwd_##SUF(const void *grad_out, const void *input, const void *offset,         \
+        const void *mask, void *grad_input, void *grad_offset, void *grad_mask, MSDA_DCN_GEOMETRY,       \
+        int64_t max_level_cells, void *workspace, int64_t workspace_bytes, void *stream);
+MSDA_DCN(f32)
+MSDA_DCN(f16)
+MSDA_DCN(bf16)
+MSDA_DCN(f64)
+#undef MSDA_DCN
+#undef MSDA_DCN_GEOMETRY
+MSDA_API int64_t msda_dcn_bwd_workspace_bytes(int64_t N, int64_t Hi, int64_t Wi, int64_t G, int64_t D, int64_t Ho,
+                                              int64_t Wo, int64_t K, int elem_size, int flags);
+
 #ifdef __cplusplus
 }
 #endif

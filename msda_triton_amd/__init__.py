@@ -14,6 +14,7 @@ from .functional import (  # noqa: F401
     multiscale_deformable_attention,
     native_multiscale_deformable_attention,
 )
+from .dcn import DeformableConv, deformable_conv_core, deformable_conv_core_packed  # noqa: F401
 from .key_aware import KeyAwareDeformableAttention, key_aware_deformable_attention  # noqa: F401
 from .module import MultiscaleDeformableAttention  # noqa: F401
 
@@ -28,4 +29,7 @@ __all__ = [
     "msda_hip_bwd",
     "key_aware_deformable_attention",
     "KeyAwareDeformableAttention",
+    "deformable_conv_core",
+    "deformable_conv_core_packed",
+    "DeformableConv",
 ]

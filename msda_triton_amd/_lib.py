@@ -84,7 +84,7 @@ EXPORTED_SYMBOLS = tuple(
     + _pair("fused_levelref") + _pair("fused_hfbox") + _pair("masked") + _pair("fused_levelref_masked")
     + ["msda_abi_version", "msda_last_error", "msda_set_option", "msda_get_option", "msda_bwd_workspace_bytes",
        "msda_bwd_fused_workspace_bytes", "msda_bwd_supported", "msda_fused_lp_limit", "msda_profile_read",
-       "msda_last_launch_info"]
+       "msda_last_launch_info", "msda_dcn_bwd_workspace_bytes"]
 )
 # ... and the additions within ABI 12 that came after it, each found by its probe:
 # the query-mask entry points (has_query_mask)
@@ -115,6 +115,21 @@ def _keyaware_signatures():
     yield "msda_keyaware_trip_samples", _I64, [_I64, _CI]
 
 
+# the deformable convolution core (has_dcn).  As key-aware attention, not a _FAMILIES row: the table composes
+# msda_{fwd,bwd}_<infix>_<suffix> over (B, I, H, D, Q, L, P); this family's lists carry the lattice's geometry instead.
+# (its size query, declared in the header by name, is in EXPORTED_SYMBOLS)
+DCN_SYMBOLS = tuple(f"msda_dcn_{d}_{s}" for d in ("fwd", "bwd") for s in KEYAWARE_SUFFIXES)
+
+
+def _dcn_signatures():
+    # N, Hi, Wi, G, D, Ho, Wo | kh, kw, sh, sw, ph, pw, dh, dw | offset_scale, softmax | the four strides
+    geometry = [_I64] * 7 + [_CI] * 8 + [_CD, _CI] + [_I64] * 4
+    for suf in KEYAWARE_SUFFIXES:
+        yield f"msda_dcn_fwd_{suf}", _CI, [_VP] * 4 + geometry + [_VP]
+        yield f"msda_dcn_bwd_{suf}", _CI, [_VP] * 7 + geometry + [_I64, _VP, _I64, _VP]
+    yield "msda_dcn_bwd_workspace_bytes", _I64, [_I64] * 8 + [_CI, _CI]
+
+
 def _signatures(lib):
     """(symbol, restype, argtypes) of every kernel entry point and size query the loaded library has."""
     for infix, probe, suffixes, fwd_ptrs, bwd_ptrs, last_dim, extras, mode, queries in _FAMILIES:
@@ -134,6 +149,8 @@ def _signatures(lib):
             yield f"msda_bwd_{stem}supported", _CI, dims + [_CI]
     if hasattr(lib, "msda_keyaware_bwd_workspace_bytes"):
         yield from _keyaware_signatures()
+    if hasattr(lib, "msda_dcn_bwd_workspace_bytes"):
+        yield from _dcn_signatures()
 
 
 def _has(infix: str) -> bool:
@@ -255,6 +272,12 @@ def has_keyaware() -> bool:
     """Does the loaded library have the key-aware attention kernels (msda_keyaware_fwd_<dtype> ..., additions within ABI 12,
     found by symbol)?  Without them ``key_aware_deformable_attention`` runs its PyTorch formulation."""
     return hasattr(load(), "msda_keyaware_bwd_workspace_bytes")
+
+
+def has_dcn() -> bool:
+    """Does the loaded library have the deformable convolution core (msda_dcn_fwd_<dtype> ..., additions within ABI 12, found
+    by symbol)?  Without them ``deformable_conv_core`` runs its PyTorch formulation."""
+    return hasattr(load(), "msda_dcn_bwd_workspace_bytes")
 
 
 def has_value_mask() -> bool:

@@ -197,6 +197,23 @@ extern "C" int64_t msda_keyaware_bwd_workspace_bytes(int64_t B, int64_t I, int64
            msda::sorted_ws_bytes(d, park, false, 0, msda::passes_of(flags));
 }
 
+// the deformable convolution core (include/msda_hip.h): the head of the workspace — the level table's (Hi, Wi), the parked
+// points and weights — then what a grad_value-only call of the plain operator needs (the 16-bit operators': of the float pipeline)
+extern "C" int64_t msda_dcn_bwd_workspace_bytes(int64_t N, int64_t Hi, int64_t Wi, int64_t G, int64_t D, int64_t Ho, int64_t Wo,
+                                                int64_t K, int elem_size, int flags)
+{
+    const int64_t lim = (int64_t)1 << 24;
+    if (msda::any_negative(N, Hi, G, D, Ho, Wi, Wo) || K < 1 || Hi >= lim || Wi >= lim || Ho >= lim || Wo >= lim ||
+        (elem_size != 2 && elem_size != 4 && elem_size != 8))
+        return 0;
+    const msda::Dims d{N, Hi * Wi, G, D, Ho * Wo, 1, K};
+    const int park = elem_size == 2 ? 4 : elem_size;
+    if (msda::common_limits_exceeded(d, elem_size) || msda::common_limits_exceeded(d, park) || !msda::bwd_supported(d, park)) return 0;
+    if (msda::nothing_sampled(d)) return 0;
+    return (int64_t)msda::dcn_head((size_t)(N * Ho * Wo * G * K), (size_t)elem_size).bytes +
+           msda::sorted_ws_bytes(d, park, false, 0, msda::passes_of(flags));
+}
+
 extern "C" int64_t msda_keyaware_trip_samples(int64_t D, int elem_size)
 {
     if (D <= 0 || (elem_size != 2 && elem_size != 4 && elem_size != 8)) return 0;

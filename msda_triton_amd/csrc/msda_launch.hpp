@@ -13,6 +13,7 @@
 #include "msda_discrete.hpp"
 #include "msda_hfbox_discrete.hpp"
 #include "msda_keyaware.hpp"
+#include "msda_dcn.hpp"
 #include "msda_options.hpp"
 
 namespace msda {
@@ -1087,6 +1088,14 @@ struct Call {
     const void *query = nullptr, *key = nullptr;
     void *attn_out = nullptr, *grad_query = nullptr, *grad_key = nullptr;
     double scale = 0.0;
+    // the deformable convolution core (msda_dcn_*_<dtype>): offsets and mask with their (row, group) strides in elements and
+    // their gradients; the geometry {Hi, Wi, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw}; `offset_scale` below is its s.  The
+    // input is `value`, its gradient `grad_value`; B = N, I = Hi Wi, H = G, Q = Ho Wo, L = 1, P = K.
+    const void *dcn_offset = nullptr, *dcn_mask = nullptr;
+    void *grad_dcn_offset = nullptr, *grad_dcn_mask = nullptr;
+    int64_t dcn_strides[4] = {0, 0, 0, 0};  // offset row, offset group, mask row, mask group
+    int64_t dcn_geom[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int dcn_softmax = 0;
     int64_t B = 0, I = 0, H = 0, D = 0, Q = 0, L = 0;
     int64_t P = 0, S = 0;  // per-level counts: their maximum and sum (take_counts); else the uniform P and 0
     const int32_t *points_per_level = nullptr;  // host, L counts
@@ -1817,6 +1826,243 @@ template <typename T> int run_keyaware_bwd(const Call &c)
     return 0;
 }
 
+// ---- the deformable convolution core: msda_dcn_{fwd,bwd}_<dtype>, kernels in msda_dcn.hpp ----
+constexpr int kDcnGroupBlock = 4;               // groups per workgroup: four trips of a D = 16 stage's 64-unit rounds
+constexpr size_t kDcnWindowBudget = 64 * 1024;  // LDS bytes the staged window may take
+// bytes of a workgroup's records: NU units x K slots of {4 offsets, 4 scalars, z} (+ the backward's point, + one scalar per unit)
+inline size_t dcn_record_bytes(int NU, int K, size_t acc, bool bwd)
+{
+    return align_up((size_t)NU * K * (16 + 5 * acc + (bwd ? 2 * acc : 0)) + (bwd ? (size_t)NU * acc : 0), 16);
+}
+// MODE 0: the forward, 1: the sample half of the backward.  Tiles, group blocks and the window are decided here.
+template <typename T, int VEC, int G, int MODE> inline int launch_dcn(DcnParams &p, hipStream_t stream)
+{
+    using A = typename Traits<T>::acc;
+    constexpr int NU = kBlock / G;
+    const size_t rec = dcn_record_bytes(NU, p.P, sizeof(A), MODE == 1);
+    if (rec > (size_t)kMaxDynLds) {
+        set_error("the deformable convolution core parks all K = %d samples of %d units in LDS (%zu bytes): K is too large here", p.P, NU, rec);
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    p.gblk = p.H < kDcnGroupBlock ? p.H : kDcnGroupBlock;
+    // the window under a tile at zero offsets: the taps' span, the second corner, the halo on both sides
+    p.win_w = (kDcnTile - 1) * p.sw + p.dw * (p.kw - 1) + 2 + 2 * kDcnHalo;
+    p.win_h = (kDcnTile - 1) * p.sh + p.dh * (p.kh - 1) + 2 + 2 * kDcnHalo;
+    p.win = option_dcn_window();
+    const size_t pixel = (size_t)p.D * sizeof(T), budget = std::min(kDcnWindowBudget, (size_t)kMaxDynLds - rec);
+    if (p.win) {  // the largest group block whose window fits; none: no window
+        int gb = p.gblk;
+        while (gb > 0 && (size_t)p.win_w * p.win_h * gb * pixel > budget) --gb;
+        if (gb > 0 && (int64_t)p.win_w * p.win_h < (1 << 20)) p.gblk = gb;
+        else p.win = 0;
+    }
+    p.ngb = (p.H + p.gblk - 1) / p.gblk;
+    p.tiles_x = (p.Wo + kDcnTile - 1) / kDcnTile;
+    const int64_t slots = (int64_t)p.tiles_x * ((p.Ho + kDcnTile - 1) / kDcnTile) * p.ngb;
+    p.win_off = (uint32_t)rec;
+    p.win_row = (uint32_t)(p.gblk * pixel);
+    const size_t lds = rec + (p.win ? (size_t)p.win_w * p.win_h * p.win_row : 0);
+    p.nqc = (int)slots;
+    dim3 grid;
+    if (slots >= ((int64_t)1 << 31) || !plane_grid(p, p.B, slots, grid)) {
+        set_error("grid too large");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    static std::atomic<uint64_t> big_lds_done{0};
+    note_launch(25, p.win);
+    if (MODE == 0) {
+        note_launch(0, 6);
+        note_launch(1, 0);
+        note_launch(2, 1);
+        note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, G, p.D);
+        note_trips(23, p.P, p.P);
+        const ProfileScope prof("msda_dcn_fwd_kernel", stream);
+        allow_big_lds(msda_dcn_fwd_kernel<T, VEC, G>, big_lds_done);
+        hipLaunchKernelGGL((msda_dcn_fwd_kernel<T, VEC, G>), grid, dim3(kBlock), lds, stream, p);
+    } else {
+        note_launch(4, 5);
+        note_launch(5, 0);
+        note_instance(11, VEC, G, p.D);
+        note_trips(24, p.P, p.P);
+        const ProfileScope prof("msda_dcn_bwd_sample_kernel", stream);
+        allow_big_lds(msda_dcn_bwd_sample_kernel<T, VEC, G>, big_lds_done);
+        hipLaunchKernelGGL((msda_dcn_bwd_sample_kernel<T, VEC, G>), grid, dim3(kBlock), lds, stream, p);
+    }
+    return (int)hipGetLastError();
+}
+template <typename T, int VEC, int MODE> inline int dispatch_dcn_group(DcnParams &p, hipStream_t stream)
+{
+    const int lanes = (p.D + VEC - 1) / VEC;
+    if (lanes > kWave) {  // (a unit's rows stay in registers: one channel chunk)
+        set_error("the deformable convolution core serves groups of at most %d channels here, got D = %d", kWave * VEC, p.D);
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    switch (pick_group(lanes)) {
+    case 4: return launch_dcn<T, VEC, 4, MODE>(p, stream);
+    case 8: return launch_dcn<T, VEC, 8, MODE>(p, stream);
+    case 16: return launch_dcn<T, VEC, 16, MODE>(p, stream);
+    case 32: return launch_dcn<T, VEC, 32, MODE>(p, stream);
+    default: return launch_dcn<T, VEC, 64, MODE>(p, stream);
+    }
+}
+template <typename T, int MODE> inline int dispatch_dcn(DcnParams &p, bool vec_ok, hipStream_t stream)
+{
+    constexpr int VECF = 16 / sizeof(T);
+    if (vec_ok && (p.D % VECF) == 0) return dispatch_dcn_group<T, VECF, MODE>(p, stream);
+    return dispatch_dcn_group<T, 1, MODE>(p, stream);
+}
+
+// the family's own argument checks, behind check_common: kernel, strides, dilations, the output size, the element strides
+inline int check_dcn(const Call &c)
+{
+    const int64_t *g = c.dcn_geom;  // Hi, Wi, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw
+    const int64_t lim = (int64_t)1 << 24;
+    if (g[4] < 1 || g[5] < 1 || g[6] < 1 || g[7] < 1 || g[10] < 1 || g[11] < 1 || g[8] < 0 || g[9] < 0) {
+        set_error("deformable convolution: kernel, stride and dilation must be >= 1 and padding >= 0");
+        return MSDA_ERR_BAD_ARG;
+    }
+    for (int i = 0; i < 12; ++i)
+        if (g[i] < 0 || g[i] >= lim) {
+            set_error("deformable convolution: geometry argument %d out of range", i);
+            return g[i] < 0 ? MSDA_ERR_BAD_ARG : MSDA_ERR_TOO_LARGE;
+        }
+    const int64_t eh = g[0] + 2 * g[8] - (g[10] * (g[4] - 1) + 1), ew = g[1] + 2 * g[9] - (g[11] * (g[5] - 1) + 1);
+    const int64_t ho = eh < 0 ? 0 : eh / g[6] + 1, wo = ew < 0 ? 0 : ew / g[7] + 1;
+    if (g[2] != ho || g[3] != wo) {
+        set_error("deformable convolution: the output is %lld x %lld for this geometry, got %lld x %lld", (long long)ho, (long long)wo,
+                  (long long)g[2], (long long)g[3]);
+        return MSDA_ERR_BAD_ARG;
+    }
+    const int64_t K = g[4] * g[5];
+    if (c.dcn_strides[1] < 2 * K || c.dcn_strides[3] < K || c.dcn_strides[0] < 0 || c.dcn_strides[2] < 0 ||
+        c.dcn_strides[0] >= ((int64_t)1 << 31) || c.dcn_strides[2] >= ((int64_t)1 << 31)) {
+        set_error("deformable convolution: a group's offsets take 2 K and its mask values K elements; row strides in [0, 2^31)");
+        return MSDA_ERR_BAD_ARG;
+    }
+    return 0;
+}
+template <typename T> inline int fill_dcn(DcnParams &p, const Call &c, const Dims &d)
+{
+    const int rc = fill_kernarg<T>(p, c, d);
+    if (rc) return rc;
+    const int64_t *g = c.dcn_geom;
+    p.off = c.dcn_offset;
+    p.msk = c.dcn_mask;
+    p.g_off = c.grad_dcn_offset;
+    p.g_msk = c.grad_dcn_mask;
+    p.off_row = c.dcn_strides[0];
+    p.off_grp = c.dcn_strides[1];
+    p.msk_row = c.dcn_strides[2];
+    p.msk_grp = c.dcn_strides[3];
+    p.park_shapes = nullptr;
+    p.s = c.offset_scale;
+    p.inv_w = 1.0 / (double)g[1];
+    p.inv_h = 1.0 / (double)g[0];
+    p.Hi = (int)g[0], p.Wi = (int)g[1], p.Ho = (int)g[2], p.Wo = (int)g[3];
+    p.kh = (int)g[4], p.kw = (int)g[5], p.sh = (int)g[6], p.sw = (int)g[7];
+    p.ph = (int)g[8], p.pw = (int)g[9], p.dh = (int)g[10], p.dw = (int)g[11];
+    p.softmax = c.dcn_softmax;
+    return 0;
+}
+
+template <typename T> int run_dcn_fwd(const Call &c)
+{
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    const size_t out_bytes = (size_t)(d.B * d.Q * d.H * d.D) * sizeof(T);
+    if (out_bytes == 0) return 0;  // nothing to produce
+    int rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc == 0) rc = check_dcn(c);
+    if (rc == 0) rc = require_buffers({c.out});
+    if (rc) return rc;
+    if (d.I == 0) return zero_outputs({{c.out, out_bytes}}, stream);  // every tap is padding
+    if ((rc = require_buffers({c.value, c.dcn_offset, c.dcn_mask})) != 0) return rc;
+    if ((rc = check_aligned({{c.value, sizeof(T)}, {c.out, sizeof(T)}, {c.dcn_offset, sizeof(T)}, {c.dcn_mask, sizeof(T)}})) != 0) return rc;
+    DcnParams p{};
+    if ((rc = fill_dcn<T>(p, c, d)) != 0) return rc;
+    return launched(dispatch_dcn<T, 0>(p, rows_vec_ok(p, c.out), stream), "deformable convolution forward");
+}
+
+// The head of the backward's workspace: (Hi, Wi) as the pipeline's level table reads them, the points [N, Q, G, K, 2] and
+// the weights [N, Q, G, K] in ParkType; each part rounded up to 256 bytes.
+struct DcnHead {
+    size_t off_loc, off_attn, bytes;
+};
+inline DcnHead dcn_head(size_t ns, size_t elem)
+{
+    const size_t park = elem == 2 ? 4 : elem;
+    DcnHead hd;
+    hd.off_loc = 256;
+    hd.off_attn = hd.off_loc + align_up(ns * 2 * park, 256);
+    hd.bytes = hd.off_attn + align_up(ns * park, 256);
+    return hd;
+}
+
+// grad_offset and grad_mask come from the sample kernel (both or neither), which also parks points and weights; grad_input
+// from the grad_value route run_value picks, behind the head.  A frozen input: the sample kernel alone, no workspace.
+template <typename T> int run_dcn_bwd(const Call &c)
+{
+    using MT = ParkType<T>;
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    int rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc == 0) rc = check_dcn(c);
+    if (rc) return rc;
+    const bool want_input = c.grad_value != nullptr, want_sample = c.grad_dcn_offset != nullptr || c.grad_dcn_mask != nullptr;
+    if (want_sample && (c.grad_dcn_offset == nullptr || c.grad_dcn_mask == nullptr)) {
+        set_error("grad_offset and grad_mask must be both null or both non-null");
+        return MSDA_ERR_BAD_ARG;
+    }
+    const size_t input_bytes = (size_t)(d.B * d.I * d.H * d.D) * sizeof(T);
+    if (d.B * d.Q * d.H == 0) return zero_outputs({{c.grad_value, input_bytes}}, stream);  // no unit: nothing else to write
+    if (d.D == 0 || d.I == 0) {  // (the strided gradients cannot be cleared with one fill)
+        set_error("deformable convolution backward: an empty input or D = 0 is not served");
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    if (!want_input && !want_sample) return 0;
+    if ((rc = require_buffers({c.grad_out, c.value, c.dcn_offset, c.dcn_mask})) != 0) return rc;
+    if ((rc = check_aligned({{c.grad_out, sizeof(T)}, {c.value, sizeof(T)}, {c.dcn_offset, sizeof(T)}, {c.dcn_mask, sizeof(T)},
+                             {c.grad_value, sizeof(T)}, {c.grad_dcn_offset, sizeof(T)}, {c.grad_dcn_mask, sizeof(T)}})) != 0)
+        return rc;
+    if (want_input && sizeof(MT) != sizeof(T) && common_limits_exceeded(d, (int64_t)sizeof(MT))) {
+        set_error("tensor too large for the deformable convolution backward's float32 grad_value passes");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    const size_t ns = (size_t)(d.B * d.Q * d.H * samples(d));
+    const DcnHead hd = dcn_head(ns, sizeof(T));
+    if (want_input && (c.workspace == nullptr || !aligned_to(c.workspace, 256) || (uint64_t)c.workspace_bytes < hd.bytes)) {
+        set_error("the deformable convolution backward needs a 256-byte aligned workspace of msda_dcn_bwd_workspace_bytes(...) "
+                  "bytes (at least %zu) for grad_input", hd.bytes);
+        return MSDA_ERR_BAD_ARG;
+    }
+    DcnParams p{};
+    if ((rc = fill_dcn<T>(p, c, d)) != 0) return rc;
+    p.out = nullptr;
+    p.grad_value = nullptr;
+    unsigned char *ws = static_cast<unsigned char *>(c.workspace);
+    unsigned char *rest = want_input ? ws + hd.bytes : nullptr;
+    const int64_t rest_bytes = want_input ? c.workspace_bytes - (int64_t)hd.bytes : 0;
+    Params pv = p;  // the plain operator's kernarg for the pipeline: its own instantiations, one level, the parked inputs
+    if (want_input) {
+        p.park_shapes = reinterpret_cast<int64_t *>(ws);
+        p.mat_loc = ws + hd.off_loc;
+        p.mat_attn = ws + hd.off_attn;
+        pv.shapes = p.park_shapes;
+        pv.loc = p.mat_loc;
+        pv.attn = p.mat_attn;
+        pv.grad_value = c.grad_value;
+        pv.grad_loc = pv.grad_attn = nullptr;
+        // a call for grad_input it cannot finish is refused before its first kernel
+        if ((rc = value_route_status<MT, T>(pv, d, rest, rest_bytes)) != 0) return rc;
+    }
+    if ((rc = launched(dispatch_dcn<T, 1>(p, rows_vec_ok(p, c.grad_out), stream), "deformable convolution backward (grad_offset/grad_mask)")) != 0)
+        return rc;
+    if (!want_input) return 0;
+    if constexpr (sizeof(MT) != sizeof(T)) return run_value_float<T, T>(pv, d, rest, rest_bytes, stream);
+    else return run_value<T, T, T>(pv, d, rest, rest_bytes, stream);
+}
+
 }  // namespace msda
 
 // ---- the extern "C" entry points (include/msda_hip.h has the argument lists): each fills a Call by name — the groups
@@ -2317,5 +2563,41 @@ template <typename T> int run_keyaware_bwd(const Call &c)
         return msda::run_keyaware_bwd<T>(c);                                                                     \
     }
 
+// the deformable convolution core: msda_dcn_{fwd,bwd}_<dtype> — one storage type for every tensor, zero padding
+#define MSDA_DCN_GEOMETRY                                                                                        \
+    int64_t N, int64_t Hi, int64_t Wi, int64_t G, int64_t D, int64_t Ho, int64_t Wo, int kh, int kw, int sh,     \
+    int sw, int ph, int pw, int dh, int dw, double offset_scale, int softmax, int64_t offset_row_stride,        \
+    int64_t offset_group_stride, int64_t mask_row_stride, int64_t mask_group_stride
+#define MSDA_TAKE_DCN                                                                                            \
+    msda::Call c; c.value = input; c.dcn_offset = offset; c.dcn_mask = mask; c.B = N; c.I = Hi * Wi; c.H = G;    \
+    c.D = D; c.Q = Ho * Wo; c.L = 1; c.P = (int64_t)kh * kw; c.padding_mode = MSDA_PADDING_ZEROS;               \
+    c.offset_scale = offset_scale; c.dcn_softmax = softmax != 0; c.stream = stream;                              \
+    { const int64_t g_[12] = {Hi, Wi, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw};                                   \
+      for (int i_ = 0; i_ < 12; ++i_) c.dcn_geom[i_] = g_[i_]; }                                                 \
+    c.dcn_strides[0] = offset_row_stride; c.dcn_strides[1] = offset_group_stride;                                \
+    c.dcn_strides[2] = mask_row_stride; c.dcn_strides[3] = mask_group_stride;                                    \
+    if (Hi < 0 || Wi < 0 || Ho < 0 || Wo < 0 || Hi >= (1 << 24) || Wi >= (1 << 24) || Ho >= (1 << 24) ||        \
+        Wo >= (1 << 24) || kh < 0 || kw < 0) {                                                                   \
+        msda::set_error("deformable convolution: image or kernel size out of range");                            \
+        return MSDA_ERR_BAD_ARG;                                                                                 \
+    }
+#define MSDA_DEFINE_DCN_ENTRY_POINTS(SUF, T)                                                                     \
+    extern "C" int msda_dcn_fwd_##SUF(const void *input, const void *offset, const void *mask, void *out,        \
+                                      MSDA_DCN_GEOMETRY, void *stream)                                           \
+    {                                                                                                            \
+        MSDA_TAKE_DCN c.out = out;                                                                               \
+        return msda::run_dcn_fwd<T>(c);                                                                          \
+    }                                                                                                            \
+    extern "C" int msda_dcn_bwd_##SUF(const void *grad_out, const void *input, const void *offset,               \
+                                      const void *mask, void *grad_input, void *grad_offset, void *grad_mask,    \
+                                      MSDA_DCN_GEOMETRY, int64_t max_level_cells, void *workspace,               \
+                                      int64_t workspace_bytes, void *stream)                                     \
+    {                                                                                                            \
+        MSDA_TAKE_DCN MSDA_TAKE_WORKSPACE c.grad_out = grad_out; c.grad_value = grad_input;                      \
+        c.grad_dcn_offset = grad_offset; c.grad_dcn_mask = grad_mask;                                            \
+        return msda::run_dcn_bwd<T>(c);                                                                          \
+    }
+
 // one storage type for every tensor
-#define MSDA_DEFINE_ENTRY_POINTS(SUF, T) MSDA_DEFINE_ENTRY_POINTS2(SUF, T, T) MSDA_DEFINE_KEYAWARE_ENTRY_POINTS(SUF, T)
+#define MSDA_DEFINE_ENTRY_POINTS(SUF, T) \
+    MSDA_DEFINE_ENTRY_POINTS2(SUF, T, T) MSDA_DEFINE_KEYAWARE_ENTRY_POINTS(SUF, T) MSDA_DEFINE_DCN_ENTRY_POINTS(SUF, T)

@@ -52,7 +52,10 @@
     /* 1: one unit per wave of the one-wave-per-unit forward; 2: two wherever the variant exists */                  \
     X(unit_waves, 1, 1, 2, false)                                                                                    \
     /* passes over the batch a workspace query sizes for when its flags name none (MSDA_WS_PASSES) */                \
-    X(ws_passes, 1, 1, 128, false)
+    X(ws_passes, 1, 1, 128, false)                                                                                   \
+    /* deformable convolution core — 1: stage the input window under a tile in LDS where it fits; 0: never (the */   \
+    /* default: the window lost at every measured shape) */                                            \
+    X(dcn_window, 0, 0, 1, false)
 
 namespace msda {
 #define MSDA_OPTION_GETTER(key, def, lo, hi, dev) int option_##key();
