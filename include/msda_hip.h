@@ -959,6 +959,69 @@ MSDA_DCN(f64)
 MSDA_API int64_t msda_dcn_bwd_workspace_bytes(int64_t N, int64_t Hi, int64_t Wi, int64_t G, int64_t D, int64_t Ho,
                                               int64_t Wo, int64_t K, int elem_size, int flags);
 
+/* ---- deformable feature aggregation, Sparse4D-style multi-view sampling (additions within ABI 12, found by symbol:
+ *      msda_dfa_bwd_workspace_bytes) ----
+ * feature_maps [B, I, G, D] channels-last, C = G * D: the cams * levels maps packed camera-major, level-minor,
+ *   I = sum_{c,l} h_cl * w_cl — bit for bit msda_fwd's value [B, I, H, D] with H = G; value_row_stride as there.
+ * spatial_shapes [cams, levels, 2] int64 (h, w), device memory; cameras may differ in size; level starts are derived in the
+ *   kernels.  cams * levels <= MSDA_MAX_LEVELS, else MSDA_ERR_UNSUPPORTED.
+ * sampling_locations [B, A, P, cams, 2]: (x, y) normalised to the camera's image.
+ * weights [B, A, P, cams, levels, G].
+ *
+ *   out[b, a, g, :] = sum_{p, c, l}  valid(b, a, p, c) * weights[b, a, p, c, l, g]
+ *                                     * bilinear(feature_maps[b, map(c, l), g, :], x * w_cl - 0.5, y * h_cl - 0.5)
+ *   valid = 0 < x < 1 and 0 < y < 1        (strict; a dropped pair — NaN included — contributes nothing on any level)
+ *
+ * `bilinear` is MSDA_PADDING_ZEROS with align_corners = 0: pixel centres at half-integers, a corner outside the map
+ * contributes zero.  One storage type for every tensor (f32, f64, bf16, f16), arithmetic in the accumulate type.
+ *
+ * msda_dfa_fwd_<dtype> writes out [B, A, G, D], fully, no memset, no host synchronisation, graph-capturable.  Checks in
+ * msda_fwd_<dtype>'s order with H = G, Q = A, L = cams * levels (the size limits of DESIGN.md 2): an empty `out` returns 0;
+ * sizes; `out`; P = 0 or I = 0 stores zeros; the inputs; alignment (every buffer on its element size, locations on a pair).
+ * A lane holds 16 bytes of a pixel row when D * sizeof is a multiple of 16, every row buffer is 16-byte aligned and
+ * value_row_stride is a multiple of 16; one element otherwise.  Rows wider than one wave's 64 lanes are served in channel
+ * chunks: no C is refused.  MSDA_ERR_UNSUPPORTED only where the records of ONE point (cams * levels, with G sums each in the
+ * backward) exceed the LDS.
+ *
+ * msda_dfa_bwd_<dtype>: from grad_out [B, A, G, D] to
+ *   grad_sampling_locations [B, A, P, cams, 2] — with respect to the normalised location, summed over levels and all
+ *     channels — and grad_weights [B, A, P, cams, levels, G]; both given or both NULL (MSDA_ERR_BAD_ARG otherwise); every
+ *     element has one writer, no atomics; zeros where the pair is dropped;
+ *   grad_feature_maps [B, I, G, D], written dense — NULL for frozen maps, which skips the pipeline and needs no workspace.
+ * grad_feature_maps is msda_bwd's grad_value for H = G, Q = A, L = cams * levels, P: the sample kernel parks, at the head
+ * of the workspace, the points [B, A, G, L, P, 2] and the weights [B, A, G, L, P] (float32 for the 16-bit operators; a
+ * dropped pair as a point outside every map with weight 0), and the grad_value route (single-launch kernel or sorted
+ * pipeline, max_level_cells as there) runs on them with the rows of grad_out — reproducible as msda_bwd's outputs are.  The
+ * forward, the sample kernel and the pipeline derive a sample's cell from the same location with the same expression.  The
+ * workspace is 256-byte aligned and of msda_dfa_bwd_workspace_bytes(...) bytes (flags: MSDA_WS_PASSES(n) only; 0 where the
+ * call would be refused).  A call for grad_feature_maps that has no route is refused before its first kernel.
+ *
+ * Out-of-view pairs are compacted away before any record is made.  When P * cams * levels records exceed the LDS area the
+ * kernels make trips over whole points; msda_dfa_trip_records(C, G, cams, levels, elem_size, backward) is the number of
+ * records one trip holds (a multiple of cams * levels) on the 16-byte path.  msda_last_launch_info: "fwd_variant" 7 and
+ * "sample_variant" 6 are this family's kernels; "fwd_group" / "sample_group" the lanes per unit, "fwd_chunks" /
+ * "sample_chunks" the channel chunks, "fwd_trips" / "sample_trips" the trips. */
+#define MSDA_DFA_SIZES int64_t B, int64_t I, int64_t G, int64_t D, int64_t A, int64_t P, int64_t cams, int64_t levels
+#define MSDA_DFA(SUF)                                                                                    \
+    MSDA_API int msda_dfa_fwd_##SUF(const void *feature_maps, const int64_t *spatial_shapes,             \
+        const void *sampling_locations, const void *weights, void *out, MSDA_DFA_SIZES,                  \
+        int64_t value_row_stride, void *stream);                                                         \
+    MSDA_API int msda_dfa_bwd_##SUF(const void *grad_out, const void *feature_maps,                      \
+        const int64_t *spatial_shapes, const void *sampling_locations, const void *weights,              \
+        void *grad_feature_maps, void *grad_sampling_locations, void *grad_weights, MSDA_DFA_SIZES,      \
+        int64_t max_level_cells, int64_t value_row_stride, void *workspace, int64_t workspace_bytes,     \
+        void *stream);
+MSDA_DFA(f32)
+MSDA_DFA(f16)
+MSDA_DFA(bf16)
+MSDA_DFA(f64)
+#undef MSDA_DFA
+#define MSDA_DFA_QUERY(WHAT, ...) MSDA_API int64_t msda_dfa_##WHAT(__VA_ARGS__);
+MSDA_DFA_QUERY(bwd_workspace_bytes, MSDA_DFA_SIZES, int elem_size, int flags)
+MSDA_DFA_QUERY(trip_records, int64_t C, int64_t G, int64_t cams, int64_t levels, int elem_size, int backward)
+#undef MSDA_DFA_QUERY
+#undef MSDA_DFA_SIZES
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ from .functional import (  # noqa: F401
     native_multiscale_deformable_attention,
 )
 from .dcn import DeformableConv, deformable_conv_core, deformable_conv_core_packed  # noqa: F401
+from .dfa import deformable_aggregation, native_deformable_aggregation  # noqa: F401
 from .key_aware import KeyAwareDeformableAttention, key_aware_deformable_attention  # noqa: F401
 from .module import MultiscaleDeformableAttention  # noqa: F401
 
@@ -32,4 +33,6 @@ __all__ = [
     "deformable_conv_core",
     "deformable_conv_core_packed",
     "DeformableConv",
+    "deformable_aggregation",
+    "native_deformable_aggregation",
 ]

@@ -130,6 +130,20 @@ def _dcn_signatures():
     yield "msda_dcn_bwd_workspace_bytes", _I64, [_I64] * 8 + [_CI, _CI]
 
 
+# deformable feature aggregation (has_dfa).  Not a _FAMILIES row either: its sizes are (B, I, G, D, A, P, cams, levels).
+DFA_SYMBOLS = tuple([f"msda_dfa_{d}_{s}" for d in ("fwd", "bwd") for s in KEYAWARE_SUFFIXES]
+                    + ["msda_dfa_bwd_workspace_bytes", "msda_dfa_trip_records"])
+
+
+def _dfa_signatures():
+    sizes = [_I64] * 8  # B, I, G, D, A, P, cams, levels
+    for suf in KEYAWARE_SUFFIXES:
+        yield f"msda_dfa_fwd_{suf}", _CI, [_VP] * 5 + sizes + [_I64, _VP]
+        yield f"msda_dfa_bwd_{suf}", _CI, [_VP] * 8 + sizes + [_I64, _I64, _VP, _I64, _VP]
+    yield "msda_dfa_bwd_workspace_bytes", _I64, sizes + [_CI, _CI]
+    yield "msda_dfa_trip_records", _I64, [_I64] * 4 + [_CI, _CI]  # C, G, cams, levels, elem_size, backward
+
+
 def _signatures(lib):
     """(symbol, restype, argtypes) of every kernel entry point and size query the loaded library has."""
     for infix, probe, suffixes, fwd_ptrs, bwd_ptrs, last_dim, extras, mode, queries in _FAMILIES:
@@ -151,6 +165,8 @@ def _signatures(lib):
         yield from _keyaware_signatures()
     if hasattr(lib, "msda_dcn_bwd_workspace_bytes"):
         yield from _dcn_signatures()
+    if hasattr(lib, "msda_dfa_bwd_workspace_bytes"):
+        yield from _dfa_signatures()
 
 
 def _has(infix: str) -> bool:
@@ -278,6 +294,12 @@ def has_dcn() -> bool:
     """Does the loaded library have the deformable convolution core (msda_dcn_fwd_<dtype> ..., additions within ABI 12, found
     by symbol)?  Without them ``deformable_conv_core`` runs its PyTorch formulation."""
     return hasattr(load(), "msda_dcn_bwd_workspace_bytes")
+
+
+def has_dfa() -> bool:
+    """Does the loaded library have deformable feature aggregation (msda_dfa_fwd_<dtype> ..., additions within ABI 12, found
+    by symbol)?  Without them ``deformable_aggregation`` runs its PyTorch formulation."""
+    return hasattr(load(), "msda_dfa_bwd_workspace_bytes")
 
 
 def has_value_mask() -> bool:

@@ -214,6 +214,31 @@ extern "C" int64_t msda_dcn_bwd_workspace_bytes(int64_t N, int64_t Hi, int64_t W
            msda::sorted_ws_bytes(d, park, false, 0, msda::passes_of(flags));
 }
 
+// deformable feature aggregation (include/msda_hip.h): the parked points and weights, then what a grad_value-only call of the
+// plain operator needs with H = G, Q = A, L = cams * levels (the 16-bit operators': of the float pipeline)
+extern "C" int64_t msda_dfa_bwd_workspace_bytes(int64_t B, int64_t I, int64_t G, int64_t D, int64_t A, int64_t P, int64_t cams,
+                                                int64_t levels, int elem_size, int flags)
+{
+    if (msda::any_negative(B, I, G, D, A, P, cams) || levels < 0 || cams * levels > MSDA_MAX_LEVELS || cams > MSDA_MAX_LEVELS ||
+        levels > MSDA_MAX_LEVELS || (elem_size != 2 && elem_size != 4 && elem_size != 8))
+        return 0;
+    const msda::Dims d{B, I, G, D, A, cams * levels, P};
+    const int park = elem_size == 2 ? 4 : elem_size;
+    if (msda::common_limits_exceeded(d, elem_size) || msda::common_limits_exceeded(d, park) || !msda::bwd_supported(d, park)) return 0;
+    if (msda::nothing_sampled(d)) return 0;
+    return (int64_t)msda::dfa_head((size_t)(B * A * G * msda::samples(d)), (size_t)elem_size).bytes +
+           msda::sorted_ws_bytes(d, park, false, 0, msda::passes_of(flags));
+}
+
+// records (surviving pairs x levels) of a unit one trip of the kernels holds, on the path dense aligned buffers take
+extern "C" int64_t msda_dfa_trip_records(int64_t C, int64_t G, int64_t cams, int64_t levels, int elem_size, int backward)
+{
+    if (C <= 0 || G <= 0 || C % G != 0 || cams <= 0 || levels <= 0 || cams * levels > MSDA_MAX_LEVELS || cams > MSDA_MAX_LEVELS ||
+        levels > MSDA_MAX_LEVELS || (elem_size != 2 && elem_size != 4 && elem_size != 8))
+        return 0;
+    return msda::dfa_trip_records(C, G, cams, levels, elem_size, backward != 0);
+}
+
 extern "C" int64_t msda_keyaware_trip_samples(int64_t D, int elem_size)
 {
     if (D <= 0 || (elem_size != 2 && elem_size != 4 && elem_size != 8)) return 0;

@@ -14,6 +14,7 @@
 #include "msda_hfbox_discrete.hpp"
 #include "msda_keyaware.hpp"
 #include "msda_dcn.hpp"
+#include "msda_dfa.hpp"
 #include "msda_options.hpp"
 
 namespace msda {
@@ -1096,6 +1097,9 @@ struct Call {
     int64_t dcn_strides[4] = {0, 0, 0, 0};  // offset row, offset group, mask row, mask group
     int64_t dcn_geom[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int dcn_softmax = 0;
+    // deformable feature aggregation (msda_dfa_*_<dtype>): cameras and levels per camera.  The maps are `value`, the locations
+    // `loc`, the weights `attn`, their gradients next to them; B, I, H = G, D, Q = A, L = cams * levels, P.
+    int64_t dfa_cams = 0, dfa_levels = 0;
     int64_t B = 0, I = 0, H = 0, D = 0, Q = 0, L = 0;
     int64_t P = 0, S = 0;  // per-level counts: their maximum and sum (take_counts); else the uniform P and 0
     const int32_t *points_per_level = nullptr;  // host, L counts
@@ -2063,6 +2067,220 @@ template <typename T> int run_dcn_bwd(const Call &c)
     else return run_value<T, T, T>(pv, d, rest, rest_bytes, stream);
 }
 
+// ---- deformable feature aggregation: msda_dfa_{fwd,bwd}_<dtype>, kernels in msda_dfa.hpp ----
+constexpr size_t kDfaLdsBudget = 48 * 1024;  // per workgroup while more than one point fits: three workgroups per CU
+// bytes of one unit's LDS slice with `pt` points per trip (DfaLds)
+inline size_t dfa_unit_bytes(int64_t pt, int64_t cams, int64_t levels, int64_t G, size_t acc, bool bwd)
+{
+    const size_t npc = (size_t)(pt * cams), rc = npc * (size_t)levels;
+    return rc * (16 + 4 * acc + 4 + (bwd ? (2 + (size_t)G) * acc : 0)) + npc * (2 * acc + 4 + (bwd ? 4 : 0)) + 4;
+}
+inline size_t dfa_lds_bytes(int NU, int64_t pt, int64_t cams, int64_t levels, int64_t G, size_t acc, bool bwd)
+{
+    return align_up(kGatherLdsFixed + (size_t)NU * dfa_unit_bytes(pt, cams, levels, G, acc, bwd), 16);
+}
+// points of a unit per trip: as many as the budget holds, at least one while the LDS holds it; 0: not even one
+inline int dfa_trip_points(int NU, int64_t P, int64_t cams, int64_t levels, int64_t G, size_t acc, bool bwd)
+{
+    if (dfa_lds_bytes(NU, 1, cams, levels, G, acc, bwd) > (size_t)kMaxDynLds) return 0;
+    int64_t pt = 1;
+    while (pt < P && dfa_lds_bytes(NU, pt + 1, cams, levels, G, acc, bwd) <= kDfaLdsBudget) ++pt;
+    return (int)pt;
+}
+// lanes per unit and channels per lane of a row of C = G D elements (vec_ok: the buffers allow 16-byte pieces)
+inline void dfa_shape(int64_t C, int64_t D, int elem_size, bool vec_ok, int &vec, int &ul)
+{
+    const int vf = 16 / elem_size;
+    vec = vec_ok && D % vf == 0 ? vf : 1;  // (a lane's channels lie in ONE group)
+    const int64_t lanes = (C + vec - 1) / vec;
+    ul = pick_group((int)(lanes < kWave ? lanes : kWave));
+}
+// records per trip (msda_dfa_trip_records): on the path dense, aligned buffers take
+inline int64_t dfa_trip_records(int64_t C, int64_t G, int64_t cams, int64_t levels, int elem_size, bool bwd)
+{
+    int vec, ul;
+    dfa_shape(C, C / G, elem_size, true, vec, ul);
+    return (int64_t)dfa_trip_points(kBlock / ul, (int64_t)1 << 20, cams, levels, G, elem_size == 8 ? 8 : 4, bwd) * cams * levels;
+}
+
+// MODE 0: the forward, 1: the sample half of the backward
+template <typename T, int VEC, int UL, int MODE> inline int launch_dfa(DfaParams &p, hipStream_t stream)
+{
+    using A = typename Traits<T>::acc;
+    constexpr int NU = kBlock / UL;
+    p.nch = (p.C + UL * VEC - 1) / (UL * VEC);
+    p.pt = dfa_trip_points(NU, p.P, p.cams, p.levels, p.H, sizeof(A), MODE == 1);
+    if (p.pt < 1) {
+        set_error("deformable aggregation: the records of one point (%d cameras x %d levels, %d groups) exceed the LDS", p.cams, p.levels, p.H);
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    p.npc = p.pt * p.cams;
+    p.rc = p.npc * p.levels;
+    const size_t lds = dfa_lds_bytes(NU, p.pt, p.cams, p.levels, p.H, sizeof(A), MODE == 1);
+    const int64_t slots = ((int64_t)p.Q + NU - 1) / NU;
+    p.nqc = (int)slots;
+    dim3 grid;
+    if (!plane_grid(p, p.B, slots, grid)) {
+        set_error("grid too large");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    static std::atomic<uint64_t> big_lds_done{0};
+    if (MODE == 0) {
+        note_launch(0, 7);
+        note_launch(1, 0);
+        note_launch(2, 1);
+        note_launch(3, (int)(grid.x * grid.y * grid.z));
+        note_instance(8, VEC, UL, p.C);
+        note_trips(23, p.P, p.pt);
+        const ProfileScope prof("msda_dfa_fwd_kernel", stream);
+        allow_big_lds(msda_dfa_fwd_kernel<T, VEC, UL>, big_lds_done);
+        hipLaunchKernelGGL((msda_dfa_fwd_kernel<T, VEC, UL>), grid, dim3(kBlock), lds, stream, p);
+    } else {
+        note_launch(4, 6);
+        note_launch(5, 0);
+        note_instance(11, VEC, UL, p.C);
+        note_trips(24, p.P, p.pt);
+        const ProfileScope prof("msda_dfa_bwd_sample_kernel", stream);
+        allow_big_lds(msda_dfa_bwd_sample_kernel<T, VEC, UL>, big_lds_done);
+        hipLaunchKernelGGL((msda_dfa_bwd_sample_kernel<T, VEC, UL>), grid, dim3(kBlock), lds, stream, p);
+    }
+    return (int)hipGetLastError();
+}
+template <typename T, int VEC, int MODE> inline int dispatch_dfa_lanes(DfaParams &p, int ul, hipStream_t stream)
+{
+    switch (ul) {
+    case 4: return launch_dfa<T, VEC, 4, MODE>(p, stream);
+    case 8: return launch_dfa<T, VEC, 8, MODE>(p, stream);
+    case 16: return launch_dfa<T, VEC, 16, MODE>(p, stream);
+    case 32: return launch_dfa<T, VEC, 32, MODE>(p, stream);
+    default: return launch_dfa<T, VEC, 64, MODE>(p, stream);
+    }
+}
+template <typename T, int MODE> inline int dispatch_dfa(DfaParams &p, bool vec_ok, hipStream_t stream)
+{
+    int vec, ul;
+    dfa_shape(p.C, p.D, (int)sizeof(T), vec_ok, vec, ul);
+    if (vec != 1) return dispatch_dfa_lanes<T, 16 / sizeof(T), MODE>(p, ul, stream);
+    return dispatch_dfa_lanes<T, 1, MODE>(p, ul, stream);
+}
+
+// the family's own argument checks, in front of check_common: cameras, levels, the table's size
+inline int check_dfa(const Call &c)
+{
+    if (c.dfa_cams < 0 || c.dfa_levels < 0) {
+        set_error("negative dimension");
+        return MSDA_ERR_BAD_ARG;
+    }
+    if (c.dfa_cams * c.dfa_levels > MSDA_MAX_LEVELS || c.dfa_cams > MSDA_MAX_LEVELS || c.dfa_levels > MSDA_MAX_LEVELS) {
+        set_error("deformable aggregation: cams * levels = %lld maps exceed MSDA_MAX_LEVELS = %d", (long long)(c.dfa_cams * c.dfa_levels),
+                  MSDA_MAX_LEVELS);
+        return MSDA_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+template <typename T> inline int fill_dfa(DfaParams &p, const Call &c, const Dims &d)
+{
+    const int rc = fill_kernarg<T>(p, c, d);
+    if (rc) return rc;
+    p.cams = (int)c.dfa_cams;
+    p.levels = (int)c.dfa_levels;
+    p.C = (int)(d.H * d.D);
+    return 0;
+}
+
+template <typename T> int run_dfa_fwd(const Call &c)
+{
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    int rc = check_dfa(c);
+    if (rc) return rc;
+    const size_t out_bytes = (size_t)(d.B * d.Q * d.H * d.D) * sizeof(T);
+    if (out_bytes == 0) return 0;  // nothing to produce
+    if ((rc = check_common(d, sizeof(T), c.padding_mode)) != 0) return rc;
+    if ((rc = require_buffers({c.out})) != 0) return rc;
+    if (samples(d) == 0 || d.I == 0) return zero_outputs({{c.out, out_bytes}}, stream);  // an empty sum
+    if ((rc = require_buffers({c.value, c.shapes, c.loc, c.attn})) != 0) return rc;
+    if ((rc = check_aligned({{c.value, sizeof(T)}, {c.out, sizeof(T)}, {c.loc, 2 * sizeof(T)}, {c.attn, sizeof(T)}, {c.shapes, 8}})) != 0) return rc;
+    DfaParams p{};
+    if ((rc = fill_dfa<T>(p, c, d)) != 0) return rc;
+    return launched(dispatch_dfa<T, 0>(p, rows_vec_ok(p, c.out), stream), "deformable aggregation forward");
+}
+
+// The head of the backward's workspace: the points [B, A, G, L, P, 2] and the weights [B, A, G, L, P] in ParkType, each
+// part rounded up to 256 bytes (`spatial_shapes` is the pipeline's level table as it is).
+struct DfaHead {
+    size_t off_attn, bytes;
+};
+inline DfaHead dfa_head(size_t ns, size_t elem)
+{
+    const size_t park = elem == 2 ? 4 : elem;
+    DfaHead hd;
+    hd.off_attn = align_up(ns * 2 * park, 256);
+    hd.bytes = hd.off_attn + align_up(ns * park, 256);
+    return hd;
+}
+
+// grad_weights and grad_sampling_locations come from the sample kernel (both or neither), which also parks points and weights;
+// grad_feature_maps from the grad_value route run_value picks, behind the head.  Frozen maps: the sample kernel alone, no
+// workspace.
+template <typename T> int run_dfa_bwd(const Call &c)
+{
+    using MT = ParkType<T>;
+    const Dims d = make_dims(c);
+    hipStream_t stream = static_cast<hipStream_t>(c.stream);
+    int rc = check_dfa(c);
+    if (rc == 0) rc = check_common(d, sizeof(T), c.padding_mode);
+    if (rc) return rc;
+    const bool want_maps = c.grad_value != nullptr, want_sample = c.grad_loc != nullptr || c.grad_attn != nullptr;
+    if (want_sample && (c.grad_loc == nullptr || c.grad_attn == nullptr)) {
+        set_error("grad_sampling_locations and grad_weights must be both null or both non-null");
+        return MSDA_ERR_BAD_ARG;
+    }
+    const size_t pairs = (size_t)(d.B * d.Q * d.P * c.dfa_cams);
+    const size_t ns = (size_t)(d.B * d.Q * d.H * samples(d));
+    if (nothing_sampled(d))
+        return zero_outputs({{c.grad_value, (size_t)(d.B * d.I * d.H * d.D) * sizeof(T)}, {c.grad_loc, pairs * 2 * sizeof(T)},
+                             {c.grad_attn, ns * sizeof(T)}}, stream);
+    if (!want_maps && !want_sample) return 0;
+    if ((rc = require_buffers({c.grad_out, c.value, c.shapes, c.loc, c.attn})) != 0) return rc;
+    if ((rc = check_aligned({{c.grad_out, sizeof(T)}, {c.value, sizeof(T)}, {c.loc, 2 * sizeof(T)}, {c.attn, sizeof(T)}, {c.shapes, 8},
+                             {c.grad_value, sizeof(T)}, {c.grad_loc, 2 * sizeof(T)}, {c.grad_attn, sizeof(T)}})) != 0)
+        return rc;
+    if (want_maps && sizeof(MT) != sizeof(T) && common_limits_exceeded(d, (int64_t)sizeof(MT))) {
+        set_error("tensor too large for the deformable aggregation backward's float32 grad_value passes");
+        return MSDA_ERR_TOO_LARGE;
+    }
+    const DfaHead hd = dfa_head(ns, sizeof(T));
+    if (want_maps && (c.workspace == nullptr || !aligned_to(c.workspace, 256) || (uint64_t)c.workspace_bytes < hd.bytes)) {
+        set_error("the deformable aggregation backward needs a 256-byte aligned workspace of msda_dfa_bwd_workspace_bytes(...) "
+                  "bytes (at least %zu) for grad_feature_maps", hd.bytes);
+        return MSDA_ERR_BAD_ARG;
+    }
+    DfaParams p{};
+    if ((rc = fill_dfa<T>(p, c, d)) != 0) return rc;
+    p.out = nullptr;
+    p.grad_value = nullptr;
+    unsigned char *ws = static_cast<unsigned char *>(c.workspace);
+    unsigned char *rest = want_maps ? ws + hd.bytes : nullptr;
+    const int64_t rest_bytes = want_maps ? c.workspace_bytes - (int64_t)hd.bytes : 0;
+    Params pv = p;  // the plain operator's kernarg for the pipeline: its own instantiations on the parked inputs
+    if (want_maps) {
+        p.mat_loc = ws;
+        p.mat_attn = ws + hd.off_attn;
+        pv.loc = p.mat_loc;
+        pv.attn = p.mat_attn;
+        pv.grad_value = c.grad_value;
+        pv.grad_loc = pv.grad_attn = nullptr;
+        // a call for grad_feature_maps it cannot finish is refused before its first kernel
+        if ((rc = value_route_status<MT, T>(pv, d, rest, rest_bytes)) != 0) return rc;
+    }
+    if ((rc = launched(dispatch_dfa<T, 1>(p, rows_vec_ok(p, c.grad_out), stream), "deformable aggregation backward (grad_weights/grad_sampling_locations)")) != 0)
+        return rc;
+    if (!want_maps) return 0;
+    if constexpr (sizeof(MT) != sizeof(T)) return run_value_float<T, T>(pv, d, rest, rest_bytes, stream);
+    else return run_value<T, T, T>(pv, d, rest, rest_bytes, stream);
+}
+
 }  // namespace msda
 
 // ---- the extern "C" entry points (include/msda_hip.h has the argument lists): each fills a Call by name — the groups
@@ -2598,6 +2816,34 @@ template <typename T> int run_dcn_bwd(const Call &c)
         return msda::run_dcn_bwd<T>(c);                                                                          \
     }
 
+// deformable feature aggregation: msda_dfa_{fwd,bwd}_<dtype> — one storage type for every tensor, zero padding
+#define MSDA_DFA_SIZES int64_t B, int64_t I, int64_t G, int64_t D, int64_t A, int64_t P, int64_t cams, int64_t levels
+#define MSDA_TAKE_DFA                                                                                            \
+    msda::Call c; c.value = feature_maps; c.shapes = spatial_shapes; c.loc = sampling_locations;                 \
+    c.attn = weights; c.B = B; c.I = I; c.H = G; c.D = D; c.Q = A; c.P = P; c.dfa_cams = cams;                   \
+    c.dfa_levels = levels; c.L = cams * levels; c.padding_mode = MSDA_PADDING_ZEROS;                             \
+    c.value_row_stride = value_row_stride; c.stream = stream;
+#define MSDA_DEFINE_DFA_ENTRY_POINTS(SUF, T)                                                                     \
+    extern "C" int msda_dfa_fwd_##SUF(const void *feature_maps, const int64_t *spatial_shapes,                   \
+                                      const void *sampling_locations, const void *weights, void *out,            \
+                                      MSDA_DFA_SIZES, int64_t value_row_stride, void *stream)                    \
+    {                                                                                                            \
+        MSDA_TAKE_DFA c.out = out;                                                                               \
+        return msda::run_dfa_fwd<T>(c);                                                                          \
+    }                                                                                                            \
+    extern "C" int msda_dfa_bwd_##SUF(const void *grad_out, const void *feature_maps,                            \
+                                      const int64_t *spatial_shapes, const void *sampling_locations,             \
+                                      const void *weights, void *grad_feature_maps,                              \
+                                      void *grad_sampling_locations, void *grad_weights, MSDA_DFA_SIZES,         \
+                                      int64_t max_level_cells, int64_t value_row_stride, void *workspace,        \
+                                      int64_t workspace_bytes, void *stream)                                     \
+    {                                                                                                            \
+        MSDA_TAKE_DFA MSDA_TAKE_WORKSPACE c.grad_out = grad_out; c.grad_value = grad_feature_maps;               \
+        c.grad_loc = grad_sampling_locations; c.grad_attn = grad_weights;                                        \
+        return msda::run_dfa_bwd<T>(c);                                                                          \
+    }
+
 // one storage type for every tensor
-#define MSDA_DEFINE_ENTRY_POINTS(SUF, T) \
-    MSDA_DEFINE_ENTRY_POINTS2(SUF, T, T) MSDA_DEFINE_KEYAWARE_ENTRY_POINTS(SUF, T) MSDA_DEFINE_DCN_ENTRY_POINTS(SUF, T)
+#define MSDA_DEFINE_ENTRY_POINTS(SUF, T)                                                                        \
+    MSDA_DEFINE_ENTRY_POINTS2(SUF, T, T) MSDA_DEFINE_KEYAWARE_ENTRY_POINTS(SUF, T) MSDA_DEFINE_DCN_ENTRY_POINTS(SUF, T) \
+    MSDA_DEFINE_DFA_ENTRY_POINTS(SUF, T)
